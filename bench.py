@@ -26,7 +26,7 @@ timed region starts with nothing but that file and ends after the cross-rank exc
   host    per-site vote -> VCF body lines + scores
 
 A *step* is one collection window of the reference driver (10 Mb, SVision:88) -- on every rank at once under weak scaling.
-`value` is the median of --repeats (3) timed repeats of the whole job, each between its own barriers.  value = candidate sites (distinct region
+`value` is the median of --repeats (1; --full: 3) timed repeats of the whole job, each between its own barriers.  value = candidate sites (distinct region
 keys of the chromosomes' segment TSVs: a site spanning a window boundary counts once) per second, whole job; ms_per_step
 follows it.  `config.resident_sites_per_s` is the same job with the alignments already decoded and resident in HBM (the
 headline of rounds 1-3): what the device pipeline does once ingestion is out of the way.  No data-path collective; one
@@ -36,6 +36,19 @@ to --detail (bench_detail.json).  After the timed legs the windows the CPU basel
 once more (untimed) with the helpers returning their TSV text and the owner keeping the predictions: `parity_check` compares them
 with the CPU port's (TSV and site keys bit-exact, softmax within 1e-3) and the process exits 3 on a mismatch.
 `--gpus N` without a launcher environment starts the N ranks itself (torch.distributed.run, one per GPU, RCCL).
+
+Plain run and --full.  `bench.py --gpus 1 --steps K --warmup W` does only what `value` needs: set-up, the warm-up, ONE timed run of
+K steps per rank (the file-inclusive leg), --dump-outputs if given, the line.  Its workload is the job of min(K, PLAIN_WINDOWS)
+windows per rank (a bounded set-up), timed once as built when K <= PLAIN_WINDOWS; when K is larger the timed region passes over that
+BAM again -- every pass a file-inclusive run of its own, from opening the file to the exchange -- until exactly K windows per rank are
+through (on N ranks every pass is a prefix of the smallest rank's file, so that the ranks meet at the same barriers).  `--full` adds everything else as before: the
+job of K windows itself (the genome once K x N reaches 322, a file of at most MAX_FILE_WINDOWS windows), --repeats (3) timed repeats,
+the resident leg, the cold-cache leg, the other ingest engine, the per-kernel calibration, the parity leg and the CPU baseline, and the
+--detail record (bench_detail.json).
+`--dump-outputs DIR` writes what the timed path returned for its last step (the last window of the last pass) as DIR/<name>.npy:
+probs (float32 [images, 5], the softmax of every candidate image, TSV order), classes (float32 [images]), and the vote of that
+window's chromosome run: scores (float64 [records]) and vcf (float64 [records, 3]: POS, INFO END, INFO SVLEN; NaN where absent).
+The only work a dumping run adds inside its timed region is a host copy of every launch's classes / softmax in the last pass.
 """
 import argparse
 import json
@@ -53,7 +66,7 @@ sys.path.insert(0, ROOT)
 from svision_amd import build_host, dist as sdist, kernels, synth  # noqa: E402
 from svision_amd.io import bam  # noqa: E402
 from svision_amd.network.alexnet import AlexNet, checkpoint_shapes  # noqa: E402
-from svision_amd.pipeline import HelperPool, PooledHotPath  # noqa: E402
+from svision_amd.pipeline import HelperPool, PooledHotPath, distinct_sites, stitch_windows  # noqa: E402
 from svision_amd.sample import Sample  # noqa: E402
 
 IMG_BYTES = 227 * 227 * 3 * 4 + 48            # 618,348 B written + 48 B read per image
@@ -192,7 +205,7 @@ def build_workload(args, rank, world, cores):
         # wg with --steps K: K windows PER RANK -- the job is K x N windows of the genome (a prefix of every chromosome), sharded by
         # chromosome: weak scaling, as a path that partitions with no data-path collective is to be reported.  Without --steps (or
         # once K x N reaches the genome's 322 windows) the job is the genome whatever N: strong scaling.
-        wg_contigs, wg_strong = wg_job(args.steps, world)
+        wg_contigs, wg_strong = wg_job(args.job_steps, world)
         contigs = list(GRCH38) if args.workload == "contig" else wg_contigs
         shards = sdist.shard_chromosomes([n for n, _l in contigs], [l for _n, l in contigs], world)
         shard = shards[rank]
@@ -250,17 +263,23 @@ def build_workload(args, rank, world, cores):
 
 
 MAX_FILE_WINDOWS = 100                        # 19 GB of BAM (46 GB inflated) written during set-up: what a default-sized run may cost (an explicit --e2e-windows may ask for more)
+PLAIN_WINDOWS = 20                            # windows per rank a plain run builds (~3.9 GB of BAM): its set-up stays bounded whatever --steps
 
 
 def resolve_defaults(args):
-    """--steps / --e2e-windows / --contig-len defaults per workload (see the module docstring)."""
+    """--steps / --e2e-windows / --contig-len / --repeats defaults per workload (see the module docstring).  Sets args.job_steps, the
+    windows per rank the wg workload is built from: --steps under --full, at most PLAIN_WINDOWS in a plain run."""
+    full = getattr(args, "full", False)
     if args.workload == "cfg1" and args.contig_len == CHR21:
         args.contig_len = CFG1_LEN
     if args.workload == "wg" and args.steps is None and not args.resident:
         args.steps = 20
+    args.job_steps = args.steps if full or args.steps is None or args.workload != "wg" else min(args.steps, PLAIN_WINDOWS)
+    if getattr(args, "repeats", None) is None:
+        args.repeats = 3 if full else 1
     if args.e2e_windows is None:
         if args.workload == "wg" and not args.resident:
-            args.e2e_windows = min(args.steps, MAX_FILE_WINDOWS)
+            args.e2e_windows = min(args.job_steps, MAX_FILE_WINDOWS)
         elif args.workload in ("cfg1", "cfg2", "ont"):
             args.e2e_windows = min(-(-args.contig_len // WINDOW), 20)
         else:
@@ -280,6 +299,87 @@ def repeats_summary(legs, rate):
     vals = sorted(rate(l) for l in legs)
     return {"n": len(legs), "min": vals[0], "median": rate(median_leg(legs)), "max": vals[-1],
             "seconds": [round(l["seconds"], 4) for l in legs]}
+
+
+def pass_steps(args, strong):
+    """The windows per rank the timed region runs over a job built smaller than --steps (a plain wg run whose --steps exceed
+    PLAIN_WINDOWS: passes over its file / cycles over its resident windows), or None: the job is timed once, as built."""
+    if args.steps and not strong and args.job_steps is not None and args.job_steps < args.steps:
+        return args.steps
+    return None
+
+
+def file_passes(e2e, steps=None, size=None):
+    """The passes over the file of one timed run of `steps` windows: the first `size` (default: all) of the file's windows in
+    task order, again and again until `steps` are through (the last pass cut at a window, its chromosomes only); None: the file
+    once.  Every rank makes as many passes (each one ends with a barrier): `size` is the smallest file of the ranks."""
+    wins = e2e["windows"]
+    if not steps:
+        return [e2e]
+    size = min(size or len(wins), len(wins))
+    out = []
+    while steps > 0:
+        k = min(steps, size)
+        if k == len(wins):
+            out.append(e2e)
+        else:
+            sub = dict(e2e, header_references=e2e["references"], windows=wins[:k])
+            sub["references"] = [n for n in e2e["references"] if any(w[0] == n for w in wins[:k])]
+            out.append(sub)
+        steps -= k
+    return out
+
+
+def merge_passes(legs):
+    """One timed run made of passes over the file (run_from_file records) -> one record: seconds, sites, images and windows
+    added up, the device stage's time and images added up (its executed-pixel counters already run over the whole repeat),
+    the rest from the last pass."""
+    if len(legs) == 1:
+        return legs[0]
+    out = dict(legs[-1])
+    for k in ("seconds", "sites", "images", "windows"):
+        out[k] = sum(l[k] for l in legs)
+    out["value"] = out["sites"] / out["seconds"]
+    out["device_busy_frac"] = sum(l["device_busy_frac"] * l["seconds"] for l in legs) / out["seconds"]
+    out["stage"] = dict(legs[-1]["stage"], dev_ms=sum(l["stage"]["dev_ms"] for l in legs), dev_images=sum(l["stage"]["dev_images"] for l in legs))
+    out["passes"] = [{"windows": l["windows"], "seconds": round(l["seconds"], 4), "sites": l["sites"]} for l in legs]
+    return out
+
+
+def _vcf_numbers(text):
+    """VCF body lines -> float64 [records, 3]: POS, INFO END, INFO SVLEN (NaN where a record has none)."""
+    rows = []
+    for ln in text.splitlines():
+        f = ln.split("\t")
+        if len(f) < 8 or ln.startswith("#"):
+            continue
+        info = dict(kv.split("=", 1) for kv in f[7].split(";") if "=" in kv)
+
+        def num(v):
+            try:
+                return float(v)
+            except (TypeError, ValueError):
+                return np.nan
+        rows.append((num(f[1]), num(info.get("END")), num(info.get("SVLEN"))))
+    return np.asarray(rows, np.float64).reshape(-1, 3)
+
+
+def dump_outputs(path, last):
+    """--dump-outputs: what the timed path returned for its last step (run()'s `last`) as path/<name>.npy."""
+    os.makedirs(path, exist_ok=True)
+    res, voted = last.get("window"), last.get("vote") or {}
+    vcf_text = "".join(v for v, _sc in voted.values())
+    arrays = {
+        "probs": np.asarray(res.probs if res is not None and res.probs is not None else np.empty((0, 5)), np.float32).reshape(-1, 5),
+        "classes": np.asarray(res.classes if res is not None and res.classes is not None else np.empty(0), np.float32),
+        "scores": np.asarray([float(x) for _v, sc in voted.values() for x in sc.split()], np.float64),
+        "vcf": _vcf_numbers(vcf_text),
+    }
+    for name, a in arrays.items():
+        if a.nbytes > 16 << 20:                                       # at most 64 MB in all: a fixed, seeded sample of the rows, in order
+            rows = max(1, (16 << 20) // max(1, a.nbytes // len(a)))
+            a = a[np.sort(np.random.default_rng(0).choice(len(a), rows, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def _clip(text, n):
@@ -389,6 +489,51 @@ def first_contact(world, grouped, backend, rank_mb, rank_file_bytes, identities)
             "rank_bam_bytes": [int(v) for v in rank_file_bytes] if rank_file_bytes else None}
 
 
+def make_runner(hot, opts):
+    """-> run(seq, rescan, sink, last): the windows of seq through the pooled hot path, voted per chromosome run."""
+
+    def run(seq, rescan=True, sink=None, last=None):
+        """seq: windows in task order (a chromosome's windows contiguous).  Windows complete in any order; a run of
+        consecutive windows of one chromosome is one per-chromosome vote (sites spanning a window boundary are written once).
+        last: a dict that receives the WindowResult of seq's last window ("window") and the vote of its run ("vote")."""
+        sites = images = records = 0
+        scores = []
+        hot.reset_timing()
+        done = {}
+        sample = lambda chrom, start: hot.feed.get(chrom, block=True, start=start)[1]     # noqa: E731  (the resident Sample, or the one that served the window)
+        # maximal runs of ascending windows of one chromosome; a run is voted and stitched as soon as its last window is through
+        # (as the command line writes a chromosome when its last window is done, cli._run_pooled), while the device works on the others
+        runs, run_of, lo = [], {}, 0
+        while lo < len(seq):
+            hi = lo + 1
+            while hi < len(seq) and seq[hi][0] == seq[hi - 1][0] and seq[hi][1] == seq[hi - 1][2]:
+                hi += 1
+            for w in range(lo, hi):
+                run_of[w] = len(runs)
+            runs.append([lo, hi, hi - lo])
+            lo = hi
+        for res in hot.run_windows(seq, rescan=rescan):
+            images += res.n_images
+            done[res.wid] = res
+            if sink is not None:                                                  # the parity leg: the window's TSV text and predictions
+                sink[(res.chrom, res.start, res.end)] = (res.tsv, res.classes, res.probs)
+            if last is not None and res.wid == len(seq) - 1:
+                last["window"] = res
+            run = runs[run_of[res.wid]]
+            run[2] -= 1
+            if run[2] == 0:
+                part = [done.pop(w) for w in range(run[0], run[1])]
+                sites += distinct_sites(part)                                  # a site spanning a window boundary counts once
+                voted = stitch_windows(part, opts, sample)
+                for vcf_text, score_text in voted.values():
+                    records += vcf_text.count("\n")
+                    scores += [float(s_) for s_ in score_text.split()]
+                if last is not None and run[1] == len(seq):
+                    last["vote"] = voted
+        return sites, images, records, scores
+    return run
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -421,18 +566,27 @@ def main():
     ap.add_argument("--no-cold-leg", action="store_true", help="skip the file-inclusive leg with the BAM's pages dropped from the page cache first (`e2e_cold_cache`)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-calibration", action="store_true", help="skip the per-kernel timings outside the timed region")
-    ap.add_argument("--repeats", type=int, default=3, help="timed repeats of the job (each one times exactly --steps windows between its own barriers); "
-                                                           "`value` / `ms_per_step` are the repeat with the MEDIAN wall time, value_repeats holds min / median / max")
-    ap.add_argument("--detail", default="bench_detail.json", help="where the full record goes (decoder traces, per-kernel rooflines, the other legs, notes); "
-                                                                  "stdout carries ONE compact JSON line (< 4 KB) whose numbers are a subset of it")
+    ap.add_argument("--repeats", type=int, default=None, help="timed repeats of the job (each one times exactly --steps windows between its own barriers); "
+                                                              "`value` / `ms_per_step` are the repeat with the MEDIAN wall time, value_repeats holds min / median / max "
+                                                              "(default: 1, with --full 3)")
+    ap.add_argument("--detail", default=None, help="where the full record goes (decoder traces, per-kernel rooflines, the other legs, notes); "
+                                                   "stdout carries ONE compact JSON line (< 4 KB) whose numbers are a subset of it (default: none, with --full "
+                                                   "bench_detail.json)")
     ap.add_argument("--host-cpus", type=int, default=0, help="pin this rank and everything it forks or starts afterwards (host helpers, pread / decode threads, the runtime's own threads) "
                                                              "to K CPUs (sched_setaffinity after the workload is built, before the first fork): the host budget an N-rank run on "
                                                              "this box leaves a rank (VERDICT r5 item 5).  0: no pinning")
     ap.add_argument("--no-parity", action="store_true", help="skip the parity leg (the device path's TSV / site keys / softmax against the CPU port's on the windows the CPU baseline runs)")
+    ap.add_argument("--full", action="store_true", help="everything besides `value` (see the module docstring): the job of --steps windows itself, "
+                                                        "3 repeats, the resident / cold-cache / other-engine legs, the per-kernel calibration, the parity leg, "
+                                                        "the CPU baseline and the --detail record.  Without it a run times --steps windows once and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the timed path returned for its last step "
+                                                                        "as DIR/<name>.npy (float32 / float64; see the module docstring)")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args))
     resolve_defaults(args)
+    if args.detail is None:
+        args.detail = "bench_detail.json" if args.full else ""
 
     rank, world = sdist.env_rank()
     from svision_amd.ingest import decode_threads, effective_cpus
@@ -453,7 +607,7 @@ def main():
         opts.contig, opts.min_support = True, 1
     table = bam.concat_tables([t for _n, _l, t, _g in parts]) if len(parts) > 1 else parts[0][2]
     fasta = bam.Fasta(sequences={n: g for n, _l, _t, g in parts})
-    want_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline
+    want_cpu = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
     cpu_pool = CpuBaselinePool(cores, table, fasta, opts, visible_cpus) if want_cpu else None
     pool = HelperPool(workers, opts, table=table, fasta=fasta)
     torch.cuda.set_device(sdist.local_device_index())
@@ -484,46 +638,15 @@ def main():
             tdist.barrier()
         torch.cuda.synchronize()
 
-    from svision_amd.pipeline import distinct_sites, stitch_windows
-
-    def run(seq, rescan=True, sink=None):
-        """seq: windows in task order (a chromosome's windows contiguous).  Windows complete in any order; a run of
-        consecutive windows of one chromosome is one per-chromosome vote (sites spanning a window boundary are written once)."""
-        sites = images = records = 0
-        scores = []
-        hot.reset_timing()
-        done = {}
-        sample = lambda chrom, start: hot.feed.get(chrom, block=True, start=start)[1]     # noqa: E731  (the resident Sample, or the one that served the window)
-        # maximal runs of ascending windows of one chromosome; a run is voted and stitched as soon as its last window is through
-        # (as the command line writes a chromosome when its last window is done, cli._run_pooled), while the device works on the others
-        runs, run_of, lo = [], {}, 0
-        while lo < len(seq):
-            hi = lo + 1
-            while hi < len(seq) and seq[hi][0] == seq[hi - 1][0] and seq[hi][1] == seq[hi - 1][2]:
-                hi += 1
-            for w in range(lo, hi):
-                run_of[w] = len(runs)
-            runs.append([lo, hi, hi - lo])
-            lo = hi
-        for res in hot.run_windows(seq, rescan=rescan):
-            images += res.n_images
-            done[res.wid] = res
-            if sink is not None:                                                  # the parity leg: the window's TSV text and predictions
-                sink[(res.chrom, res.start, res.end)] = (res.tsv, res.classes, res.probs)
-            run = runs[run_of[res.wid]]
-            run[2] -= 1
-            if run[2] == 0:
-                part = [done.pop(w) for w in range(run[0], run[1])]
-                sites += distinct_sites(part)                                  # a site spanning a window boundary counts once
-                for vcf_text, score_text in stitch_windows(part, opts, sample).values():
-                    records += vcf_text.count("\n")
-                    scores += [float(s_) for s_ in score_text.split()]
-        return sites, images, records, scores
+    run = make_runner(hot, opts)
 
     sharded = args.workload in ("wg", "contig")                       # the rank runs its LPT shard of one job (the others: a job of its own per rank)
     if sharded:
         timed = list(windows)                                         # this rank's share of the job
         steps_job = total_windows
+        if pass_steps(args, strong):                                 # a plain run's bounded job: --steps windows per rank over it
+            timed = [windows[i % len(windows)] for i in range(args.steps)]
+            steps_job = args.steps * world
     else:
         k = args.steps or (len(windows) if args.workload == "cfg1" else 200)
         timed = [windows[i % len(windows)] for i in range(k)]
@@ -560,24 +683,43 @@ def main():
         return {"dev_ms": float(tot[0]), "dev_images": float(tot[1]), "pix": tot[2:6], "images": max(float(tot[6]), 1.0)}
 
     # ---- the timed region of `value`: the job from its BAM (file-inclusive).  Its own barrier + synchronize on both sides,
-    # max over ranks (run_from_file).
+    # max over ranks (run_from_file).  A plain run whose job was built smaller than --steps (pass_steps): passes over the file until
+    # exactly --steps windows per rank are through, every pass a file-inclusive run of its own, their seconds and sites added up.
+    # --dump-outputs: what the timed path returns for its last step.  The pipeline then keeps every window's predictions on the host
+    # (a copy of each launch's classes / softmax) during the last pass over the file -- the only host work a dumping run adds.
+    last = {} if args.dump_outputs else None
     e2e_block = e2e_other = None
     e2e_legs = []
-    if e2e is not None and not args.resident:
+    headline_e2e = e2e is not None and not args.resident
+    if headline_e2e:
+        per_rank, n_file = pass_steps(args, strong), len(e2e["windows"])
+        if per_rank and grouped:                                      # the same passes on every rank: the smallest file of the ranks
+            t = torch.tensor([n_file], dtype=torch.int64, device=dev)
+            tdist.all_reduce(t, op=tdist.ReduceOp.MIN)
+            n_file = int(t.item())
+        passes = file_passes(e2e, per_rank, n_file)
         for _r in range(max(1, args.repeats)):
             net.executed.zero_()
-            leg = run_from_file(args, e2e, hot, run, fasta, opts, dev, sync_all, cores, world, workers, grouped, engine=os.environ.get("SVX_INGEST", "auto"), keep=True)
-            leg["stage"] = stage_stats()
-            e2e_legs.append(leg)
+            legs = []
+            for i, sub in enumerate(passes):
+                final = i == len(passes) - 1
+                hot.keep_predictions = last is not None and final
+                leg = run_from_file(args, sub, hot, run, fasta, opts, dev, sync_all, cores, world, workers, grouped, engine=os.environ.get("SVX_INGEST", "auto"),
+                                    keep=True, last=last if final else None)
+                leg["stage"] = stage_stats()
+                legs.append(leg)
+            e2e_legs.append(merge_passes(legs))
         e2e_block = median_leg(e2e_legs)
-    # ---- the same job with the alignments decoded and resident in HBM (the headline of rounds 1-3; --resident: `value`)
+    # ---- the same job with the alignments decoded and resident in HBM (the headline of rounds 1-3; --resident: `value`;
+    # beside a file-inclusive `value` only with --full)
     res_legs = []
-    for _r in range(max(1, args.repeats)):
+    for _r in range(max(1, args.repeats) if args.full or not headline_e2e else 0):
+        hot.keep_predictions = last is not None and not headline_e2e
         sync_all()
         net.executed.zero_()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        sites, images, records, scores = run(timed)
+        sites, images, records, scores = run(timed, last=None if headline_e2e else last)
         # the single cross-shard exchange of the job: score range + record gather (dist.py)
         sdist.exchange_score_range(scores)
         sdist.gather_texts({"rank%d" % rank: "%d records" % records})
@@ -588,8 +730,13 @@ def main():
         st = stage_stats()
         tot, tmax = reduce_sum_max([sites, images, dt])
         res_legs.append({"seconds": float(tmax[2]), "sites": float(tot[0]), "images": float(tot[1]), "stage": st})
-    res_leg = median_leg(res_legs)
-    res_stage, res_sites, res_images, dt = res_leg["stage"], res_leg["sites"], res_leg["images"], res_leg["seconds"]
+    hot.keep_predictions = False
+    res_stage = res_sites = res_images = dt = None
+    if res_legs:
+        res_leg = median_leg(res_legs)
+        res_stage, res_sites, res_images, dt = res_leg["stage"], res_leg["sites"], res_leg["images"], res_leg["seconds"]
+    if last is not None and rank == 0:
+        dump_outputs(args.dump_outputs, last)
     sweep = []
     if e2e is not None and args.e2e_sweep:
         for spec in args.e2e_sweep.split(";"):
@@ -612,11 +759,11 @@ def main():
                 print("e2e sweep %s: %.3f s (read %s, pread %s, slot wait %s, last chromosome ready %s)" % (
                     spec or "(default)", leg["seconds"], dd.get("read_s"), dd.get("pread_s"), dd.get("slot_wait_s"), leg["rank0_feed"].get("last_ready_s")), file=sys.stderr)
     e2e_cold = None
-    if e2e is not None and not args.resident and not args.no_cold_leg:
+    if args.full and headline_e2e and not args.no_cold_leg:
         # the same leg on a cold file: the BAM's pages are written back and dropped from the page cache first ("BAM on
         # local NVMe"; `value` reads it from the page cache it was written through).  Reported beside `value`, never as `value`.
         e2e_cold = run_from_file(args, e2e, hot, run, fasta, opts, dev, sync_all, cores, world, workers, grouped, engine=os.environ.get("SVX_INGEST", "auto"), keep=True, cold=True)
-    if e2e is not None and not args.no_other_engine:
+    if args.full and e2e is not None and not args.no_other_engine:
         # the file-inclusive leg with the other ingest engine, reported beside it (default engine: BGZF inflate + record packing
         # on the device; the other: libdeflate on the host's threads)
         first = e2e_block["ingest_engine"] if e2e_block is not None else None
@@ -633,7 +780,6 @@ def main():
     if rank == 0 and world > 1:
         print("first contact: %s" % json.dumps(contact), file=sys.stderr)
     B = args.batch
-    headline_e2e = e2e_block is not None
     stage = e2e_block["stage"] if headline_e2e else res_stage       # the device stage over the timed region of `value`
     job_s = e2e_block["seconds"] if headline_e2e else dt
     job_sites = e2e_block["sites"] if headline_e2e else res_sites
@@ -652,8 +798,8 @@ def main():
                 "algorithmic_tflops": CNN_FLOP * st["dev_images"] / world / max(dev_s, 1e-9) / 1e12,
                 "ms_batch": st["dev_ms"] / max(st["dev_images"] / B, 1), "batches": st["dev_images"] / B, "busy": dev_s / max(wall, 1e-9)}
     rep = stage_report(stage, job_s)
-    rep_res = stage_report(res_stage, dt)
-    calib = kernel_calibration(hot, sample, net, dev, B * max(1, args.launch_batches), windows[0]) if rank == 0 and not args.no_calibration and windows else {}
+    rep_res = stage_report(res_stage, dt) if res_legs else None
+    calib = kernel_calibration(hot, sample, net, dev, B * max(1, args.launch_batches), windows[0]) if args.full and rank == 0 and not args.no_calibration and windows else {}
     dense = calib.get("device_stage_eager_1_stream_dense_convolutions", {})
     workload = (("cfg5 stand-in: --contig mode, two haplotypes of N(2 Mb, 0.6 Mb) assembly contigs (0.1 % small events) on 24 "
                  "chromosomes of GRCh38 length, one task per chromosome, chromosomes LPT-sharded over the ranks")
@@ -695,9 +841,9 @@ def main():
                    "batch": B, "alignments_rank0": len(table), "cigar_ops_rank0": int(table.cigar.size),
                    "windows_rank0": len(windows), "windows": job_windows, "sites_per_step": job_sites / max(job_windows, 1),
                    "images_per_site": job_images / max(job_sites, 1), "images_per_s": job_images / job_s,
-                   "resident_sites_per_s": res_sites / dt, "resident_seconds": dt, "resident_steps": steps_job,
-                   "resident_ms_per_step": dt / max(steps_job, 1) * 1e3,
-                   "file_inclusive_over_resident": (job_sites / job_s) / max(res_sites / dt, 1e-9) if headline_e2e else None,
+                   "resident_sites_per_s": res_sites / dt if res_legs else None, "resident_seconds": dt, "resident_steps": steps_job if res_legs else None,
+                   "resident_ms_per_step": dt / max(steps_job, 1) * 1e3 if res_legs else None,
+                   "file_inclusive_over_resident": (job_sites / job_s) / max(res_sites / dt, 1e-9) if headline_e2e and res_legs else None,
                    "rccl_world": world if grouped and tdist.get_backend() == "nccl" else 0, "dist_backend": (tdist.get_backend() if grouped else None),
                    "first_contact": contact,
                    "rank_mb": [round(v, 1) for v in getattr(args, "rank_mb", [])] or None,
@@ -716,7 +862,7 @@ def main():
                      "frac_algorithmic": rep["algorithmic_tflops"] * 1e12 / F32_MFMA_PEAK,
                      "dense_stage_frac": dense.get("frac"),
                      # the same launches with the device to themselves (the resident leg of this run): the kernels' own figure
-                     "frac_stage_alone": rep_res["executed_tflops"] * 1e12 / F32_MFMA_PEAK,
+                     "frac_stage_alone": rep_res["executed_tflops"] * 1e12 / F32_MFMA_PEAK if rep_res else None,
                      "note": ("In the file-inclusive leg -- the timed region of `value` -- the CNN's launches share the chip with the inflate kernels "
                               "(a tokens launch owns every CU while it runs, an LZ launch slows the convolutions next to it) and their "
                               "intervals include that; frac_stage_alone is the same stage with the device to itself, timed in this run "
@@ -739,7 +885,7 @@ def main():
                                       + TRAFFIC["source"]) if TRAFFIC else "no PMC summary under profiles/",
                      "ms_per_batch": rep["ms_batch"], "batches": rep["batches"], "device_busy_frac": rep["busy"],
                      "resident_leg": {"frac_executed": rep_res["executed_tflops"] * 1e12 / F32_MFMA_PEAK, "ms_per_batch": rep_res["ms_batch"],
-                                      "batches": rep_res["batches"], "device_busy_frac": rep_res["busy"]}},
+                                      "batches": rep_res["batches"], "device_busy_frac": rep_res["busy"]} if rep_res else None},
     }
     line["config"]["timed_region_kind"] = (("file-inclusive: BAM on local disk (%.2f GB, page cache warm) -> read, device BGZF inflate + record walk, scan, collection, "
                                             "encode + CNN, vote, cross-rank exchange" % (e2e_block["bam_bytes"] / 1e9)) if headline_e2e else
@@ -748,12 +894,14 @@ def main():
                                         "fc_splitk x2 + fc8_softmax; HIP events around every launch of the timed region" % B)
     legs = e2e_legs if headline_e2e else res_legs
     line["value_repeats"] = repeats_summary(legs, lambda l: l["sites"] / l["seconds"])
-    line["resident_repeats"] = repeats_summary(res_legs, lambda l: l["sites"] / l["seconds"])
+    if res_legs:
+        line["resident_repeats"] = repeats_summary(res_legs, lambda l: l["sites"] / l["seconds"])
     if e2e_block is not None:
         for l in e2e_legs:
             l.pop("stage", None)
-        e2e_block["resident_sites_per_s"] = res_sites / dt
-        e2e_block["ratio_to_resident"] = e2e_block["value"] / max(res_sites / dt, 1e-9)
+        if res_legs:
+            e2e_block["resident_sites_per_s"] = res_sites / dt
+            e2e_block["ratio_to_resident"] = e2e_block["value"] / max(res_sites / dt, 1e-9)
         line["e2e"] = e2e_block
         line["e2e_repeats"] = [l for l in e2e_legs if l is not e2e_block]
     if e2e_cold is not None:
@@ -936,7 +1084,7 @@ def filesystem_of(path):
     return best[1]
 
 
-def run_from_file(args, e2e, hot, run, fasta, opts, dev, sync_all, cores, world, workers, grouped, engine="cpu", keep=False, cold=False, sink=None):
+def run_from_file(args, e2e, hot, run, fasta, opts, dev, sync_all, cores, world, workers, grouped, engine="cpu", keep=False, cold=False, sink=None, last=None):
     """The file-inclusive leg (wall of Step 1 + Step 2 with the BAM on local disk): a timed region of its
     own that starts with nothing but the file -- svx_bam_stream_* reads and inflates it on host threads chromosome by
     chromosome, every chromosome is uploaded and scanned on the device when it arrives and handed to the helpers through
@@ -961,7 +1109,7 @@ def run_from_file(args, e2e, hot, run, fasta, opts, dev, sync_all, cores, world,
     feed = ChromosomeFeed(e2e["path"], fasta, opts, refs, header_refs, lens, device=dev, index=e2e["path"] + ".bai", threads=threads, engine=engine, tasks=tasks)
     hot.feed = feed
     try:
-        sites, images, records, scores = run(e2e["windows"], rescan=False, sink=sink)
+        sites, images, records, scores = run(e2e["windows"], rescan=False, sink=sink, last=last)
         sdist.exchange_score_range(scores)
         sdist.gather_texts({"rank%d" % sdist.world()[0]: "%d records" % records})
         sync_all()

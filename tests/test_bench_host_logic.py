@@ -105,7 +105,7 @@ def test_defaults_make_the_file_inclusive_job_the_timed_one():
     """VERDICT r3 item 1: `value` is timed from the job's BAM; the file is written for the job's own windows (bounded)."""
     import argparse
     def ns(**kw):
-        base = dict(workload="wg", steps=None, resident=False, e2e_windows=None, contig_len=bench.CHR21)
+        base = dict(workload="wg", steps=None, resident=False, e2e_windows=None, contig_len=bench.CHR21, full=True)
         base.update(kw)
         return bench.resolve_defaults(argparse.Namespace(**base))
     a = ns()
@@ -122,6 +122,54 @@ def test_defaults_make_the_file_inclusive_job_the_timed_one():
     assert a.e2e_windows == 5
     a = ns(e2e_windows=0)
     assert a.e2e_windows == 0
+    assert ns().repeats == 3 and ns(steps=40).job_steps == 40 and ns(steps=322).job_steps == 322
+    # a plain run (no --full): one timed repeat; the job it builds and writes is bounded, its --steps stay what was asked
+    a = ns(full=False)
+    assert (a.steps, a.job_steps, a.e2e_windows, a.repeats) == (20, 20, 20, 1)
+    a = ns(full=False, steps=5)
+    assert (a.steps, a.job_steps, a.e2e_windows) == (5, 5, 5)
+    a = ns(full=False, steps=322)
+    assert (a.steps, a.job_steps, a.e2e_windows) == (322, bench.PLAIN_WINDOWS, bench.PLAIN_WINDOWS)
+    assert not bench.wg_job(a.job_steps, 1)[1]                # weak scaling: no whole-genome job behind a plain run
+    assert ns(full=False, repeats=2).repeats == 2
+
+
+def test_timed_steps_pass_over_the_file_until_exactly_k():
+    """--steps K beyond the file's windows: passes over the file (each a prefix of its windows in task order), K windows in all."""
+    b = _bench()
+    e2e = {"windows": [("chr1", 0, 10), ("chr1", 10, 20), ("chr2", 0, 10), ("chr3", 0, 10)], "references": ["chr1", "chr2", "chr3"]}
+    assert b.file_passes(e2e) == [e2e] and b.file_passes(e2e, None, 2) == [e2e]
+    for k, size, want in ((4, None, [4]), (9, None, [4, 4, 1]), (10, 3, [3, 3, 3, 1]), (2, 3, [2])):
+        passes = b.file_passes(e2e, k, size)
+        assert [len(p["windows"]) for p in passes] == want, (k, size)
+        for p in passes:
+            assert p["windows"] == e2e["windows"][:len(p["windows"])]
+            assert p["references"] == [r for r in e2e["references"] if any(w[0] == r for w in p["windows"])]
+            assert p.get("header_references", p["references"]) == e2e["references"]
+    legs = [{"seconds": 0.2, "sites": 100, "images": 2000, "windows": 4, "device_busy_frac": 0.5, "bam_bytes": 7,
+             "stage": {"dev_ms": 100.0, "dev_images": 2000.0, "pix": [1.0], "images": 2000.0}},
+            {"seconds": 0.1, "sites": 30, "images": 600, "windows": 1, "device_busy_frac": 0.8, "bam_bytes": 7,
+             "stage": {"dev_ms": 80.0, "dev_images": 600.0, "pix": [2.0], "images": 2600.0}}]
+    m = b.merge_passes(legs)
+    assert (m["seconds"], m["sites"], m["images"], m["windows"]) == (0.2 + 0.1, 130, 2600, 5) and m["value"] == 130 / (0.2 + 0.1)
+    assert abs(m["device_busy_frac"] - (0.5 * 0.2 + 0.8 * 0.1) / 0.3) < 1e-12
+    assert m["stage"] == {"dev_ms": 180.0, "dev_images": 2600.0, "pix": [2.0], "images": 2600.0} and len(m["passes"]) == 2
+    assert b.merge_passes(legs[:1]) is legs[0]
+
+
+def test_dumped_outputs_are_the_last_steps_arrays(tmp_path):
+    b = _bench()
+    import types as t_
+    res = t_.SimpleNamespace(probs=np.full((3, 5), 0.2, np.float32), classes=np.array([0, 4, 1]))
+    vote = {"chr2": ("chr2\t100\tS1\tN\t<DEL>\t9\tCovered\tEND=250;SVLEN=-150;SUPPORT=6\tGT\t0/1\n"
+                     "chr2\t900\tS2\tN\t<CSV>\t4\tCovered\tEND=990;BKPS=x\tGT\t1/1\n", "0.5\n0.25\n")}
+    b.dump_outputs(str(tmp_path / "out"), {"window": res, "vote": vote})
+    got = {n: np.load(str(tmp_path / "out" / (n + ".npy"))) for n in ("probs", "classes", "scores", "vcf")}
+    assert got["probs"].dtype == np.float32 and got["probs"].shape == (3, 5) and (got["probs"] == np.float32(0.2)).all()
+    assert got["classes"].dtype == np.float32 and got["classes"].tolist() == [0.0, 4.0, 1.0]
+    assert got["scores"].dtype == np.float64 and got["scores"].tolist() == [0.5, 0.25]
+    assert got["vcf"].dtype == np.float64 and got["vcf"][0].tolist() == [100.0, 250.0, -150.0]
+    assert got["vcf"][1, :2].tolist() == [900.0, 990.0] and np.isnan(got["vcf"][1, 2])
 
 
 def test_rank_launcher_line_and_the_first_contact_block():
@@ -244,3 +292,78 @@ def test_wg_steps_are_windows_per_rank():
     for k, world in ((None, 1), (None, 8), (322, 1), (100, 4), (50, 8)):
         contigs, strong = b.wg_job(k, world)
         assert strong and contigs == list(b.GRCH38)
+
+
+def test_passes_only_where_a_plain_run_capped_the_job():
+    """Which runs time their job once as built and which pass over a smaller one: only a plain wg run whose --steps exceed
+    PLAIN_WINDOWS.  Pinned for (full, K, world) with the per-rank file windows the LPT sharding really gives."""
+    import argparse
+    from svision_amd import dist as sdist
+    b = _bench()
+
+    def decide(full, k, world):
+        a = b.resolve_defaults(argparse.Namespace(workload="wg", steps=k, resident=False, e2e_windows=None, contig_len=b.CHR21, full=full))
+        contigs, strong = b.wg_job(a.job_steps, world)
+        # the file of every rank: its shard of the e2e job (what build_workload writes)
+        small = dict(b.job_contigs(a.e2e_windows * world))
+        length = dict(contigs)
+        shards = sdist.shard_chromosomes([c for c, _l in contigs], [l for _c, l in contigs], world)
+        files = [sum(len(b.windows_of(c, min(small[c], length[c]))) for c in sh if c in small) for sh in shards]
+        per_rank = b.pass_steps(a, strong)
+        sizes = []
+        for n in files:
+            e2e = {"windows": [("c", i, i + 1) for i in range(n)], "references": ["c"]}
+            sizes.append([len(p["windows"]) for p in b.file_passes(e2e, per_rank, min(files))])
+        return per_rank, files, sizes
+
+    for full, k, world in ((False, 20, 1), (True, 20, 1), (False, 5, 1), (False, 20, 8), (True, 20, 8), (True, 40, 1), (True, 150, 1)):
+        per_rank, files, sizes = decide(full, k, world)
+        assert per_rank is None, (full, k, world)                               # the job built for K windows is timed once
+        assert all(s == [n] for s, n in zip(sizes, files)), (full, k, world)
+    per_rank, files, sizes = decide(False, 50, 1)
+    assert (per_rank, files, sizes) == (50, [b.PLAIN_WINDOWS], [[20, 20, 10]])
+    per_rank, files, sizes = decide(False, 50, 8)                               # uneven rank files: prefixes of the smallest one
+    assert per_rank == 50 and sum(files) == b.PLAIN_WINDOWS * 8 and min(files) < max(files)
+    assert all(sum(s) == 50 and max(s) <= min(files) for s in sizes) and len({len(s) for s in sizes}) == 1
+    a = b.resolve_defaults(argparse.Namespace(workload="cfg2", steps=50, resident=False, e2e_windows=None, contig_len=b.CHR21, full=False))
+    assert b.pass_steps(a, False) is None                                       # only the wg job is built from --steps
+
+
+def test_runner_captures_the_last_step_and_its_vote(monkeypatch):
+    """make_runner's `last`: the WindowResult of seq's LAST window (whatever order the windows complete in) and the vote of the
+    chromosome run that window closes -- not the run voted last."""
+    b = _bench()
+    seq = [("chr1", 0, 10), ("chr1", 10, 20), ("chr2", 0, 10), ("chr3", 0, 10), ("chr3", 10, 20)]
+
+    def result(wid):
+        c, s, e = seq[wid]
+        return types.SimpleNamespace(wid=wid, chrom=c, start=s, end=e, n_images=wid + 1, n_sites=1, edges=(None, None), tsv=None,
+                                     classes=None, probs=None)
+
+    class Hot:
+        feed = None
+
+        def reset_timing(self):
+            pass
+
+        def run_windows(self, windows, rescan=True):
+            assert windows == seq
+            for wid in (4, 0, 2, 3, 1):                                         # chr3 completes before chr1
+                yield result(wid)
+
+    votes = []
+
+    def stitch(part, opts, sample):
+        v = {part[0].chrom: ("%s\t%d\t.\tN\t<DEL>\t1\tPASS\tEND=9;SVLEN=-5\n" % (part[0].chrom, len(part)), "0.5\n")}
+        votes.append(v)
+        return v
+    monkeypatch.setattr(b, "stitch_windows", stitch)
+    last = {}
+    sites, images, records, scores = b.make_runner(Hot(), None)(seq, last=last)
+    assert (sites, images, records, scores) == (5, 15, 3, [0.5, 0.5, 0.5])
+    assert last["window"].wid == 4 and last["window"].chrom == "chr3"
+    assert [list(v) for v in votes] == [["chr2"], ["chr3"], ["chr1"]]             # voted as the runs complete
+    assert last["vote"] is votes[1] and last["vote"]["chr3"][0].split("\t")[1] == "2"   # chr3's run of two windows, not chr1's
+    last = {}
+    b.make_runner(Hot(), None)(seq, last=None)                                  # no capture asked: nothing kept
+    assert last == {}

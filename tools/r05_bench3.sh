@@ -1,8 +1,8 @@
 set -u
 O=gpurun_out/${1:-r05c}
 mkdir -p $O
-for w in cfg1 ont; do SVX_TIMING=1 python bench.py --gpus 1 --workload $w --no-cpu-baseline --no-calibration --no-other-engine --no-cold-leg > $O/$w.json 2> $O/$w.err; done
-python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-calibration --no-other-engine > $O/steps20.json 2> $O/steps20.err
+for w in cfg1 ont; do SVX_TIMING=1 python bench.py --full --gpus 1 --workload $w --no-cpu-baseline --no-calibration --no-other-engine --no-cold-leg > $O/$w.json 2> $O/$w.err; done
+python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-calibration --no-other-engine > $O/steps20.json 2> $O/steps20.err
 for f in $O/*.json; do python - "$f" <<'P'
 import json,sys
 try:

@@ -1,10 +1,10 @@
 set -u
 O=gpurun_out/${1:-r05final}
 mkdir -p $O
-python bench.py --gpus 1 --steps 20 --warmup 5 > $O/steps20_a.json 2> $O/steps20_a.err
-python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-calibration --no-other-engine > $O/steps20_b.json 2> $O/steps20_b.err
-for w in cfg1 cfg2 ont contig; do python bench.py --gpus 1 --workload $w --no-calibration > $O/$w.json 2> $O/$w.err; done
-python bench.py --gpus 1 --steps 100 --warmup 5 --no-calibration > $O/e2e_100windows.json 2> $O/e2e_100windows.err
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/steps20_a.json 2> $O/steps20_a.err
+python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-calibration --no-other-engine > $O/steps20_b.json 2> $O/steps20_b.err
+for w in cfg1 cfg2 ont contig; do python bench.py --full --gpus 1 --workload $w --no-calibration > $O/$w.json 2> $O/$w.err; done
+python bench.py --full --gpus 1 --steps 100 --warmup 5 --no-calibration > $O/e2e_100windows.json 2> $O/e2e_100windows.err
 for f in $O/*.json; do python - "$f" <<'P'
 import json,sys
 try:

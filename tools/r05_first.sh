@@ -3,9 +3,9 @@ O=gpurun_out/r05a
 mkdir -p $O
 python -m pytest tests/test_slices_gpu.py tests/test_gpu_inflate.py tests/test_htslike_bam.py -x -q -m gpu > $O/pytest_slices.log 2>&1; echo "pytest slices rc $?" >> $O/pytest_slices.log
 tail -5 $O/pytest_slices.log
-for w in cfg1 ont; do SVX_TIMING=1 python bench.py --gpus 1 --workload $w --no-cpu-baseline --no-calibration --no-other-engine > $O/$w.json 2> $O/$w.err; done
-SVX_TIMING=1 python bench.py --gpus 1 --workload cfg1 --no-cpu-baseline --no-calibration --no-other-engine --e2e-sweep "SVX_SLICES=0;SVX_SLICES=1;SVX_SLICES=0;SVX_SLICES=1" > $O/cfg1_sweep.json 2> $O/cfg1_sweep.err
-python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-calibration --no-other-engine > $O/steps20.json 2> $O/steps20.err
+for w in cfg1 ont; do SVX_TIMING=1 python bench.py --full --gpus 1 --workload $w --no-cpu-baseline --no-calibration --no-other-engine > $O/$w.json 2> $O/$w.err; done
+SVX_TIMING=1 python bench.py --full --gpus 1 --workload cfg1 --no-cpu-baseline --no-calibration --no-other-engine --e2e-sweep "SVX_SLICES=0;SVX_SLICES=1;SVX_SLICES=0;SVX_SLICES=1" > $O/cfg1_sweep.json 2> $O/cfg1_sweep.err
+python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-calibration --no-other-engine > $O/steps20.json 2> $O/steps20.err
 for f in $O/*.json; do python - "$f" <<'P'
 import json,sys
 try:

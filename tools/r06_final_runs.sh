@@ -4,9 +4,9 @@
 set -u
 O=gpurun_out/${1:-r06final}
 mkdir -p $O
-python bench.py --gpus 1 --steps 20 --warmup 5 --detail $O/steps20_a.detail.json > $O/steps20_a.json 2> $O/steps20_a.err
-for w in ${WORKLOADS:-cfg1 cfg2 ont contig}; do python bench.py --gpus 1 --workload $w --no-calibration --detail $O/$w.detail.json > $O/$w.json 2> $O/$w.err; echo "$w rc=$?"; done
-if [ "${BIG:-1}" = 1 ]; then python bench.py --gpus 1 --steps 100 --warmup 5 --no-calibration --detail $O/e2e_100windows.detail.json > $O/e2e_100windows.json 2> $O/e2e_100windows.err; fi
+python bench.py --full --gpus 1 --steps 20 --warmup 5 --detail $O/steps20_a.detail.json > $O/steps20_a.json 2> $O/steps20_a.err
+for w in ${WORKLOADS:-cfg1 cfg2 ont contig}; do python bench.py --full --gpus 1 --workload $w --no-calibration --detail $O/$w.detail.json > $O/$w.json 2> $O/$w.err; echo "$w rc=$?"; done
+if [ "${BIG:-1}" = 1 ]; then python bench.py --full --gpus 1 --steps 100 --warmup 5 --no-calibration --detail $O/e2e_100windows.detail.json > $O/e2e_100windows.json 2> $O/e2e_100windows.err; fi
 for f in $O/*.json; do case $f in *.detail.json) continue;; esac; python - "$f" <<'P'
 import json,sys
 try:
@@ -21,6 +21,6 @@ P
 done
 # multi-rank rehearsals on ONE GPU (gloo: RCCL refuses two ranks on a device): the N-rank code path of the line, not a measurement
 if [ "${RANKS:-1}" = 1 ]; then
-  SVX_DIST_BACKEND=gloo python bench.py --gpus 2 --steps 10 --warmup 3 --no-cpu-baseline --no-calibration --no-cold-leg --no-other-engine --detail $O/2ranks.detail.json > $O/2ranks.json 2> $O/2ranks.err; echo "2 ranks rc=$?"; cut -c1-900 $O/2ranks.json
-  SVX_DIST_BACKEND=gloo python bench.py --gpus 8 --steps 5 --warmup 2 --no-cpu-baseline --no-calibration --no-cold-leg --no-other-engine --detail $O/8ranks.detail.json > $O/8ranks.json 2> $O/8ranks.err; echo "8 ranks rc=$?"; cut -c1-900 $O/8ranks.json
+  SVX_DIST_BACKEND=gloo python bench.py --full --gpus 2 --steps 10 --warmup 3 --no-cpu-baseline --no-calibration --no-cold-leg --no-other-engine --detail $O/2ranks.detail.json > $O/2ranks.json 2> $O/2ranks.err; echo "2 ranks rc=$?"; cut -c1-900 $O/2ranks.json
+  SVX_DIST_BACKEND=gloo python bench.py --full --gpus 8 --steps 5 --warmup 2 --no-cpu-baseline --no-calibration --no-cold-leg --no-other-engine --detail $O/8ranks.detail.json > $O/8ranks.json 2> $O/8ranks.err; echo "8 ranks rc=$?"; cut -c1-900 $O/8ranks.json
 fi

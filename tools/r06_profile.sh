@@ -11,7 +11,7 @@ run() { name=$1; shift; rm -rf /tmp/rp_$name; timeout 400 "$@" > $OUT/$name.log 
 stats() { f=$(find /tmp/rp_$1 -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $OUT/$2; }
 pmc() { tag=$1; shift; counters=$1; shift; rm -rf /tmp/rp_pmc_$tag; timeout 400 rocprofv3 --pmc $counters --output-format csv -d /tmp/rp_pmc_$tag -- "$@" > $OUT/pmc_$tag.log 2>&1; python $REPO/tools/pmc_summary.py /tmp/rp_pmc_$tag > $OUT/pmc_$tag.txt; }
 # 1. the bench command itself (file-inclusive headline leg x3 + resident leg x3 + parity leg)
-run bench_trace rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/rp_bench_trace -- python $REPO/bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-calibration --no-other-engine --no-cold-leg --detail $OUT/bench_trace.detail.json
+run bench_trace rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/rp_bench_trace -- python $REPO/bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-calibration --no-other-engine --no-cold-leg --detail $OUT/bench_trace.detail.json
 stats bench_trace a_bench_kernel_stats.csv
 # 2. eager device stage on the records of real candidate sites, per-kernel time
 REAL=1 run stage_trace rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/rp_stage_trace -- python $REPO/tools/prof_cnn.py 30
@@ -31,6 +31,6 @@ pmc write_raster "WRITE_SIZE" python $REPO/tools/microbench.py
 pmc fetch_raster "FETCH_SIZE" python $REPO/tools/microbench.py
 timeout 120 $REPO/tools/exp/raster_bw 2048 21 > $OUT/raster_bw.txt 2>&1
 # 5. the file-inclusive leg kernel by kernel
-run e2e_trace rocprofv3 --kernel-trace --output-format csv -d /tmp/rp_e2e_trace -- python $REPO/bench.py --gpus 1 --steps 20 --warmup 5 --repeats 1 --no-cpu-baseline --no-calibration --no-other-engine --no-cold-leg --detail $OUT/e2e_trace.detail.json
+run e2e_trace rocprofv3 --kernel-trace --output-format csv -d /tmp/rp_e2e_trace -- python $REPO/bench.py --full --gpus 1 --steps 20 --warmup 5 --repeats 1 --no-cpu-baseline --no-calibration --no-other-engine --no-cold-leg --detail $OUT/e2e_trace.detail.json
 timeout 120 python $REPO/tools/e2e_kernel_timeline.py /tmp/rp_e2e_trace 7 > $OUT/e2e_kernel_timeline.txt
 ls -la $OUT

@@ -7,6 +7,6 @@ out=gpurun_out/r06_wg_file; mkdir -p $out
 ( echo "memory.max $(cat /sys/fs/cgroup/memory.max 2>/dev/null)"; df -h /tmp ) > $out/box.txt 2>&1
 ( while sleep 20; do echo "$(date +%T) mem $(cat /sys/fs/cgroup/memory.current 2>/dev/null) disk $(df --output=used /tmp | tail -1)"; done ) >> $out/box.txt 2>&1 &
 mon=$!
-timeout 2700 python bench.py --gpus 1 --steps 322 --e2e-windows 322 --warmup 5 --bam-dir /tmp --sim-procs 6 --no-cold-leg --no-other-engine --no-calibration \
+timeout 2700 python bench.py --full --gpus 1 --steps 322 --e2e-windows 322 --warmup 5 --bam-dir /tmp --sim-procs 6 --no-cold-leg --no-other-engine --no-calibration \
     --detail $out/wg_file.detail.json > $out/wg_file.json 2> $out/wg_file.err
 echo "rc=$?"; kill $mon; cat $out/wg_file.json; tail -c 1500 $out/wg_file.err
