@@ -214,6 +214,51 @@ int svx_conv2d_same(const float* d_in, const float* d_w_packed, const float* d_b
                     uint32_t groups, int relu, const int32_t* d_pixels, const uint32_t* d_pixel_count,
                     const float* d_background, void* stream);
 
+/* One network pass per distinct similarity image of a launch.  An image depends only on the two line set-ups the
+ * rasteriser derives from a record (fp64 scaling, clipLine, LineIterator set-up) and the two strand flags; records
+ * that agree on them give the same bit planes.
+ *   d_records [n][12] int32 as for svx_rasterize
+ *   d_unique  out [n][12]: the first occurrence of every distinct image, in input order, in rows [0, *d_live); the
+ *             rows behind them repeat record 0 (a consumer without the live count still computes valid images)
+ *   d_inv     out [n]: the row of d_unique that holds record i's image
+ *   d_live    out, device [1]: the number of distinct images (>= 1 when n >= 1)
+ *   d_keys    NULL, or out [n][4] uint32 (16-B aligned): the exact 128-bit image key of every record -- the two Lines
+ *             (x0 | y0 << 8 | dx << 16 | dy << 24 each), (sy < 0) | steep << 1 | rev << 2 per line in bytes 0 and 1 of
+ *             the third word, count0 | count1 << 16 -- equal keys, equal images; no hash
+ *   d_ws      scratch, 4 * n bytes
+ * Deterministic (no atomics); n <= 2^26. */
+int svx_image_dedup(const int32_t* d_records, uint32_t n, int32_t* d_unique, uint32_t* d_inv, uint32_t* d_live,
+                    uint32_t* d_keys, uint32_t* d_ws, void* stream);
+
+/* d_dst[i][c] = d_src[d_inv[i]][c] for i < n, c < width (float32 rows): the packed results of the distinct images
+ * expanded to one row per record of the launch. */
+int svx_gather_rows(const float* d_src, const uint32_t* d_inv, float* d_dst, uint32_t n, uint32_t width, void* stream);
+
+/* Live-count variants of the CNN stage: as the functions without the suffix, plus d_live (NULL, or a device count of
+ * the leading images to compute, e.g. svx_image_dedup's).  Rows >= *d_live are neither read nor written (their
+ * outputs keep whatever they held); the launch geometry -- and with it every per-row result, bit for bit, including
+ * the split-K grouping of svx_fc_bias_act, which is a function of m -- stays that of n / m.  svx_alexnet_active_sets_live
+ * builds the lists over the live images only (d_counts and the pixel totals count those; the image total of d_totals
+ * still adds n), and svx_conv2d_same_live (list mode only) follows, and back-fills, those images' pixels only. */
+int svx_encode_conv1_live(const int32_t* d_records, uint32_t n, const float* d_w1, const float* d_base, float* d_y,
+                          int lrn, uint32_t radius, float alpha, float beta, float k, uint32_t* d_touched,
+                          const uint32_t* d_live, void* stream);
+int svx_alexnet_active_sets_live(const uint32_t* d_touched, uint32_t n, int32_t* d_list2, int32_t* d_list3,
+                                 int32_t* d_list4, int32_t* d_list5, uint32_t* d_counts, uint32_t* d_ws,
+                                 uint64_t* d_totals, uint32_t* d_active2, const uint32_t* d_live, void* stream);
+int svx_conv2d_same_live(const float* d_in, const float* d_w_packed, const float* d_bias, float* d_out, uint32_t n,
+                         uint32_t cin, uint32_t cout, uint32_t height, uint32_t width, uint32_t ksize,
+                         uint32_t groups, int relu, const int32_t* d_pixels, const uint32_t* d_pixel_count,
+                         const float* d_background, const uint32_t* d_live, void* stream);
+int svx_bias_relu_pool_lrn_live(const float* d_x, const float* d_bias, float* d_y, uint32_t n, uint32_t channels,
+                                uint32_t height, uint32_t width, int lrn, uint32_t radius, float alpha, float beta,
+                                float k, const uint32_t* d_active_rows, const float* d_background,
+                                const uint32_t* d_live, void* stream);
+int svx_fc_bias_act_live(const float* d_x, const float* d_w_packed, const float* d_bias, float* d_out, float* d_ws,
+                         uint32_t m, uint32_t n, uint32_t k, int relu, const uint32_t* d_live, void* stream);
+int svx_fc8_softmax_live(const float* d_x, const float* d_w, const float* d_bias, float* d_out, uint32_t n,
+                         const uint32_t* d_live, void* stream);
+
 /* Pairwise signature distances of the clustering step, all partitions of a window in one launch (fp64).
  * Replaces the Python-callback pdist inside linkage(data, method="average", metric=span_position_distance)
  * (reference src/collection/cluster_signatures.py:114 with the metric of :132-141):

@@ -38,7 +38,18 @@ SYMBOLS = {
     "svx_fc8_softmax": (ctypes.c_int, [_vp, _vp, _vp, _vp, _u32, _vp]),
     "svx_bias_relu_pool_lrn": (ctypes.c_int, [_vp, _vp, _vp, _u32, _u32, _u32, _u32, ctypes.c_int, _u32,
                                               ctypes.c_float, ctypes.c_float, ctypes.c_float, _vp, _vp, _vp]),
-    "svx_span_position_distance": (ctypes.c_int, [_vp, _vp, _vp, _u32, _vp, _u64, ctypes.c_double, _vp, _vp]),
+    "svx_image_dedup": (ctypes.c_int, [_vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "svx_gather_rows": (ctypes.c_int, [_vp, _vp, _vp, _u32, _u32, _vp]),
+    "svx_encode_conv1_live": (ctypes.c_int, [_vp, _u32, _vp, _vp, _vp, ctypes.c_int, _u32, ctypes.c_float, ctypes.c_float,
+                                             ctypes.c_float, _vp, _vp, _vp]),
+    "svx_alexnet_active_sets_live": (ctypes.c_int, [_vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "svx_conv2d_same_live": (ctypes.c_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _u32, _u32, ctypes.c_int, _vp, _vp, _vp,
+                                            _vp, _vp]),
+    "svx_bias_relu_pool_lrn_live": (ctypes.c_int, [_vp, _vp, _vp, _u32, _u32, _u32, _u32, ctypes.c_int, _u32,
+                                                   ctypes.c_float, ctypes.c_float, ctypes.c_float, _vp, _vp, _vp, _vp]),
+    "svx_fc_bias_act_live": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, ctypes.c_int, _vp, _vp]),
+    "svx_fc8_softmax_live": (ctypes.c_int, [_vp, _vp, _vp, _vp, _u32, _vp, _vp]),
+    "svx_span_position_distance":(ctypes.c_int, [_vp, _vp, _vp, _u32, _vp, _u64, ctypes.c_double, _vp, _vp]),
     "svx_hash_seeds": (ctypes.c_int, [_vp, _vp, _u32, _vp, _vp, _vp, _u32, _u32, _u32, _vp]),
     "svx_bam_open": (_vp, [ctypes.c_char_p, ctypes.c_int, ctypes.c_int]),
     "svx_bam_open_range": (_vp, [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, _u64, _u64]),

@@ -33,10 +33,12 @@ __device__ inline float4 max4(float4 a, float4 b) { return make_float4(fmaxf(a.x
 __global__ __launch_bounds__(BLOCK)
 void bias_relu_pool_lrn_kernel(const float* __restrict__ x, const float* __restrict__ bias, float* __restrict__ y,
                                int C, int H, int W, int OH, int OW, int lrn, int radius, float alpha, float beta, float k,
-                               const uint32_t* __restrict__ active_rows, const float* __restrict__ background)
+                               const uint32_t* __restrict__ active_rows, const float* __restrict__ background,
+                               const uint32_t* __restrict__ live)
 {
     extern __shared__ __attribute__((aligned(16))) float pooled[];    // [OW][C + 1]
     const int b = blockIdx.x / OH;
+    if (live && (uint32_t)b >= *live) return;                        // a row behind the launch's distinct images
     const int oy = blockIdx.x - b * OH;
     const int CP = C + 1, HW = H * W;
     const float* xb = x + ((size_t)b * (C / 8) * HW + (size_t)(2 * oy) * W) * 8;
@@ -148,7 +150,7 @@ struct EncLds {
 __global__ __launch_bounds__(ENC_BLOCK)
 void encode_conv1_kernel(const int32_t* __restrict__ records, const float* __restrict__ w1, const float* __restrict__ base,
                          float* __restrict__ y, int lrn, int radius, float alpha, float beta, float kk,
-                         uint32_t* __restrict__ touched)
+                         uint32_t* __restrict__ touched, const uint32_t* __restrict__ live)
 {
     using namespace svx_raster;
     // The LDS is taken as DYNAMIC shared memory although its size is a constant: for a kernel whose occupancy its static LDS
@@ -170,6 +172,7 @@ void encode_conv1_kernel(const int32_t* __restrict__ records, const float* __res
     constexpr int STRIPS = P1 / ENC_ROWS;
     const int img = blockIdx.x / STRIPS;
     const int oyp0 = (blockIdx.x - img * STRIPS) * ENC_ROWS;          // first pooled row of this workgroup
+    if (live && (uint32_t)img >= *live) return;                      // a row behind the launch's distinct images
 #ifdef SVX_ENC_PROFILE
     unsigned long long t_prev = wall_clock64();
 #endif
@@ -296,15 +299,22 @@ extern "C" int svx_debug_enc_prof(unsigned long long* out, int reset)
 }
 #endif
 
-extern "C" int svx_encode_conv1(const int32_t* d_records, uint32_t n, const float* d_w1, const float* d_base, float* d_y,
-                                int lrn, uint32_t radius, float alpha, float beta, float k, uint32_t* d_touched, void* stream)
+extern "C" int svx_encode_conv1_live(const int32_t* d_records, uint32_t n, const float* d_w1, const float* d_base, float* d_y,
+                                     int lrn, uint32_t radius, float alpha, float beta, float k, uint32_t* d_touched,
+                                     const uint32_t* d_live, void* stream)
 {
     if (n == 0) return SVX_OK;
     if (!d_records || !d_w1 || !d_base || !d_y) return SVX_EINVAL;
     if ((reinterpret_cast<uintptr_t>(d_w1) & 15u) || (reinterpret_cast<uintptr_t>(d_base) & 15u)) return SVX_EINVAL;
     hipLaunchKernelGGL(encode_conv1_kernel, dim3(n * (P1 / ENC_ROWS)), dim3(ENC_BLOCK), sizeof(EncLds), static_cast<hipStream_t>(stream),
-                       d_records, d_w1, d_base, d_y, lrn, (int)radius, alpha, beta, k, d_touched);
+                       d_records, d_w1, d_base, d_y, lrn, (int)radius, alpha, beta, k, d_touched, d_live);
     return hipGetLastError() == hipSuccess ? SVX_OK : SVX_ELAUNCH;
+}
+
+extern "C" int svx_encode_conv1(const int32_t* d_records, uint32_t n, const float* d_w1, const float* d_base, float* d_y,
+                                int lrn, uint32_t radius, float alpha, float beta, float k, uint32_t* d_touched, void* stream)
+{
+    return svx_encode_conv1_live(d_records, n, d_w1, d_base, d_y, lrn, radius, alpha, beta, k, d_touched, nullptr, stream);
 }
 
 namespace {
@@ -358,10 +368,11 @@ __device__ inline void image_masks(const uint32_t* __restrict__ touched_rows, ui
 
 // pass 1: a workgroup per image: the number of active pixels of the four layers
 __global__ __launch_bounds__(64)
-void active_counts_kernel(const uint32_t* __restrict__ touched, uint32_t* __restrict__ per_image)
+void active_counts_kernel(const uint32_t* __restrict__ touched, uint32_t* __restrict__ per_image, const uint32_t* __restrict__ live)
 {
     __shared__ uint32_t masks[MASK_ROWS], tmp[A1];
     const int t = threadIdx.x;
+    if (live && blockIdx.x >= *live) return;
     image_masks(touched + (size_t)blockIdx.x * A1, masks, tmp, t);
     if (t < 4) {
         const int lo = t == 0 ? 0 : A1 + (t - 1) * A2, hi = t == 0 ? A1 : lo + A2;
@@ -376,13 +387,16 @@ __global__ __launch_bounds__(BLOCK)
 void active_lists_kernel(const uint32_t* __restrict__ touched, const uint32_t* __restrict__ per_image, uint32_t n,
                          int32_t* __restrict__ list2, int32_t* __restrict__ list3, int32_t* __restrict__ list4,
                          int32_t* __restrict__ list5, uint32_t* __restrict__ counts, unsigned long long* __restrict__ totals,
-                         uint32_t* __restrict__ active2)
+                         uint32_t* __restrict__ active2, const uint32_t* __restrict__ live)
 {
     __shared__ uint32_t masks[MASK_ROWS], tmp[A1], rowoff[MASK_ROWS];
     __shared__ uint32_t s_part[8][BLOCK / WAVE];
     __shared__ uint32_t inoff[MASK_ROWS];                    // first slot of every mask row's inactive pixels
     const int t = threadIdx.x, lane = t & (WAVE - 1), wv = t >> 6;
     const uint32_t img = blockIdx.x;
+    const uint32_t n_all = n;                                // images launched (the image counter of d_totals)
+    if (live) n = min(n, *live);                             // lists over the launch's distinct images only
+    if (img >= n) return;
     uint32_t part[8] = {0, 0, 0, 0, 0, 0, 0, 0};             // [0..4): images before this one, [4..8): all images
     for (uint32_t i = t; i < n; i += BLOCK) {
         const uint4 c = reinterpret_cast<const uint4*>(per_image)[i];
@@ -413,7 +427,7 @@ void active_lists_kernel(const uint32_t* __restrict__ touched, const uint32_t* _
                 const unsigned long long all = (unsigned long long)n * hw;
                 // what svx_conv2d_same will compute: every pixel once the list is SVX_CONV_DENSE_PCT full
                 atomicAdd(&totals[t], (unsigned long long)total * 100ull >= all * SVX_CONV_DENSE_PCT ? all : (unsigned long long)total);
-                if (t == 0) atomicAdd(&totals[4], (unsigned long long)n);
+                if (t == 0) atomicAdd(&totals[4], (unsigned long long)n_all);
             }
         }
     }
@@ -436,18 +450,25 @@ void active_lists_kernel(const uint32_t* __restrict__ touched, const uint32_t* _
 }
 }  // namespace
 
-extern "C" int svx_alexnet_active_sets(const uint32_t* d_touched, uint32_t n, int32_t* d_list2, int32_t* d_list3,
-                                       int32_t* d_list4, int32_t* d_list5, uint32_t* d_counts, uint32_t* d_ws,
-                                       uint64_t* d_totals, uint32_t* d_active2, void* stream)
+extern "C" int svx_alexnet_active_sets_live(const uint32_t* d_touched, uint32_t n, int32_t* d_list2, int32_t* d_list3,
+                                            int32_t* d_list4, int32_t* d_list5, uint32_t* d_counts, uint32_t* d_ws,
+                                            uint64_t* d_totals, uint32_t* d_active2, const uint32_t* d_live, void* stream)
 {
     if (!d_counts) return SVX_EINVAL;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (n == 0) return hipMemsetAsync(d_counts, 0, 4 * sizeof(uint32_t), st) == hipSuccess ? SVX_OK : SVX_ELAUNCH;
     if (!d_touched || !d_list2 || !d_list3 || !d_list4 || !d_list5 || !d_ws || (reinterpret_cast<uintptr_t>(d_ws) & 15u)) return SVX_EINVAL;
-    hipLaunchKernelGGL(active_counts_kernel, dim3(n), dim3(64), 0, st, d_touched, d_ws);
+    hipLaunchKernelGGL(active_counts_kernel, dim3(n), dim3(64), 0, st, d_touched, d_ws, d_live);
     hipLaunchKernelGGL(active_lists_kernel, dim3(n), dim3(BLOCK), 0, st, d_touched, d_ws, n, d_list2, d_list3, d_list4, d_list5, d_counts,
-                       reinterpret_cast<unsigned long long*>(d_totals), d_active2);
+                       reinterpret_cast<unsigned long long*>(d_totals), d_active2, d_live);
     return hipGetLastError() == hipSuccess ? SVX_OK : SVX_ELAUNCH;
+}
+
+extern "C" int svx_alexnet_active_sets(const uint32_t* d_touched, uint32_t n, int32_t* d_list2, int32_t* d_list3,
+                                       int32_t* d_list4, int32_t* d_list5, uint32_t* d_counts, uint32_t* d_ws,
+                                       uint64_t* d_totals, uint32_t* d_active2, void* stream)
+{
+    return svx_alexnet_active_sets_live(d_touched, n, d_list2, d_list3, d_list4, d_list5, d_counts, d_ws, d_totals, d_active2, nullptr, stream);
 }
 
 namespace {
@@ -457,10 +478,11 @@ namespace {
 constexpr int FC8_IN = 4096, FC8_OUT = 5;
 __global__ __launch_bounds__(64 * FC8_OUT)
 void fc8_softmax_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
-                        float* __restrict__ out)
+                        float* __restrict__ out, const uint32_t* __restrict__ live)
 {
     __shared__ float logit[FC8_OUT];
     const int img = blockIdx.x, cls = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (live && (uint32_t)img >= *live) return;              // a row behind the launch's distinct images
     const float4* xv = reinterpret_cast<const float4*>(x + (size_t)img * FC8_IN);
     const float4* wv = reinterpret_cast<const float4*>(w + (size_t)cls * FC8_IN);
     float acc = 0.0f;
@@ -487,18 +509,25 @@ void fc8_softmax_kernel(const float* __restrict__ x, const float* __restrict__ w
 }
 }  // namespace
 
-extern "C" int svx_fc8_softmax(const float* d_x, const float* d_w, const float* d_bias, float* d_out, uint32_t n, void* stream)
+extern "C" int svx_fc8_softmax_live(const float* d_x, const float* d_w, const float* d_bias, float* d_out, uint32_t n,
+                                    const uint32_t* d_live, void* stream)
 {
     if (n == 0) return SVX_OK;
     if (!d_x || !d_w || !d_bias || !d_out) return SVX_EINVAL;
     if ((reinterpret_cast<uintptr_t>(d_x) & 15u) || (reinterpret_cast<uintptr_t>(d_w) & 15u)) return SVX_EINVAL;
-    hipLaunchKernelGGL(fc8_softmax_kernel, dim3(n), dim3(64 * FC8_OUT), 0, static_cast<hipStream_t>(stream), d_x, d_w, d_bias, d_out);
+    hipLaunchKernelGGL(fc8_softmax_kernel, dim3(n), dim3(64 * FC8_OUT), 0, static_cast<hipStream_t>(stream), d_x, d_w, d_bias, d_out, d_live);
     return hipGetLastError() == hipSuccess ? SVX_OK : SVX_ELAUNCH;
 }
 
-extern "C" int svx_bias_relu_pool_lrn(const float* d_x, const float* d_bias, float* d_y, uint32_t n, uint32_t channels,
-                                      uint32_t height, uint32_t width, int lrn, uint32_t radius, float alpha, float beta,
-                                      float k, const uint32_t* d_active_rows, const float* d_background, void* stream)
+extern "C" int svx_fc8_softmax(const float* d_x, const float* d_w, const float* d_bias, float* d_out, uint32_t n, void* stream)
+{
+    return svx_fc8_softmax_live(d_x, d_w, d_bias, d_out, n, nullptr, stream);
+}
+
+extern "C" int svx_bias_relu_pool_lrn_live(const float* d_x, const float* d_bias, float* d_y, uint32_t n, uint32_t channels,
+                                           uint32_t height, uint32_t width, int lrn, uint32_t radius, float alpha, float beta,
+                                           float k, const uint32_t* d_active_rows, const float* d_background,
+                                           const uint32_t* d_live, void* stream)
 {
     if (n == 0) return SVX_OK;
     if (!d_x || !d_bias || !d_y || channels == 0 || channels % 8 || height < 3 || width < 3) return SVX_EINVAL;
@@ -509,6 +538,14 @@ extern "C" int svx_bias_relu_pool_lrn(const float* d_x, const float* d_bias, flo
     if (lds > 64 * 1024) return SVX_EINVAL;
     hipLaunchKernelGGL(bias_relu_pool_lrn_kernel, dim3(n * OH), dim3(BLOCK), lds, static_cast<hipStream_t>(stream),
                        d_x, d_bias, d_y, (int)channels, (int)height, (int)width, OH, OW, lrn, (int)radius, alpha, beta, k,
-                       d_active_rows, d_background);
+                       d_active_rows, d_background, d_live);
     return hipGetLastError() == hipSuccess ? SVX_OK : SVX_ELAUNCH;
+}
+
+extern "C" int svx_bias_relu_pool_lrn(const float* d_x, const float* d_bias, float* d_y, uint32_t n, uint32_t channels,
+                                      uint32_t height, uint32_t width, int lrn, uint32_t radius, float alpha, float beta,
+                                      float k, const uint32_t* d_active_rows, const float* d_background, void* stream)
+{
+    return svx_bias_relu_pool_lrn_live(d_x, d_bias, d_y, n, channels, height, width, lrn, radius, alpha, beta, k, d_active_rows,
+                                       d_background, nullptr, stream);
 }

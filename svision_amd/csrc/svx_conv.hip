@@ -72,6 +72,7 @@ struct ConvArgs {
     int nimg, Cin, Cout, H, W, groups, relu;
     const int32_t* pixels; const uint32_t* pixel_count; const float* background;
     int n_simd;                                   // SIMDs of the device (4 per CU)
+    const uint32_t* live;                         // list mode: NULL, or the number of leading images the lists cover (device)
 };
 
 // all counts fit 32 bits: the input tensor is < 2 GB, so there are < 2^25 pixels and < 2^24 tiles of any kind
@@ -353,7 +354,7 @@ __global__ __launch_bounds__(THREADS, 2)
 void conv_wave_list_kernel(const ConvArgs a, int shape)
 {
     SVX_SHADOW_ROOM();
-    const int Mall = a.nimg * a.H * a.W;
+    const int Mall = (a.live ? min((int)*a.live, a.nimg) : a.nimg) * a.H * a.W;
     int Mtot = Mall;
     { const long long c = (long long)*a.pixel_count; if (c * 100 < (long long)Mall * SVX_CONV_DENSE_PCT) Mtot = (int)c; }
     if (shape < 0) shape = conv_pick_shape(Mtot, a.Cout / a.groups, a.groups, a.n_simd, LIST_SHAPES);
@@ -391,14 +392,14 @@ int device_simds()
 
 }  // namespace
 
-extern "C" int svx_conv2d_same(const float* d_in, const float* d_w_packed, const float* d_bias, float* d_out, uint32_t n,
-                               uint32_t cin, uint32_t cout, uint32_t height, uint32_t width, uint32_t ksize,
-                               uint32_t groups, int relu, const int32_t* d_pixels, const uint32_t* d_pixel_count,
-                               const float* d_background, void* stream)
+extern "C" int svx_conv2d_same_live(const float* d_in, const float* d_w_packed, const float* d_bias, float* d_out, uint32_t n,
+                                    uint32_t cin, uint32_t cout, uint32_t height, uint32_t width, uint32_t ksize,
+                                    uint32_t groups, int relu, const int32_t* d_pixels, const uint32_t* d_pixel_count,
+                                    const float* d_background, const uint32_t* d_live, void* stream)
 {
     if (n == 0) return SVX_OK;
     if (!d_in || !d_w_packed || !d_out || groups == 0 || cin % groups || cout % groups) return SVX_EINVAL;
-    if ((d_pixels == nullptr) != (d_pixel_count == nullptr) || (d_background && !d_pixels)) return SVX_EINVAL;
+    if ((d_pixels == nullptr) != (d_pixel_count == nullptr) || (d_background && !d_pixels) || (d_live && !d_pixels)) return SVX_EINVAL;
     const uint32_t cin_g = cin / groups, cout_g = cout / groups;
     if (cin_g % 16 || cout_g % 64 || (ksize != 3 && ksize != 5)) return SVX_EINVAL;
     for (const void* p : {(const void*)d_in, (const void*)d_w_packed, (const void*)d_out, (const void*)d_bias, (const void*)d_background})
@@ -408,7 +409,7 @@ extern "C" int svx_conv2d_same(const float* d_in, const float* d_w_packed, const
     const int mall = (int)(n * height * width);
     hipStream_t st = static_cast<hipStream_t>(stream);
     ConvArgs a{d_in, d_w_packed, d_bias, d_out, (int)n, (int)cin, (int)cout, (int)height, (int)width, (int)groups, relu,
-               d_pixels, d_pixel_count, d_background, device_simds()};
+               d_pixels, d_pixel_count, d_background, device_simds(), d_live};
     int shape = d_pixels ? -1 : conv_pick_shape(mall, (int)cout_g, (int)groups, a.n_simd, N_SHAPES);
 #ifdef SVX_CONV_EXPERIMENT
     if (const char* e = getenv("SVX_CONV_SHAPE")) if (atoi(e) >= 0 && atoi(e) < (d_pixels ? LIST_SHAPES : N_SHAPES)) shape = atoi(e);
@@ -425,4 +426,13 @@ extern "C" int svx_conv2d_same(const float* d_in, const float* d_w_packed, const
         else            launch_conv<5>(shape, wgs, st, a);
     }
     return hipGetLastError() == hipSuccess ? SVX_OK : SVX_ELAUNCH;
+}
+
+extern "C" int svx_conv2d_same(const float* d_in, const float* d_w_packed, const float* d_bias, float* d_out, uint32_t n,
+                               uint32_t cin, uint32_t cout, uint32_t height, uint32_t width, uint32_t ksize,
+                               uint32_t groups, int relu, const int32_t* d_pixels, const uint32_t* d_pixel_count,
+                               const float* d_background, void* stream)
+{
+    return svx_conv2d_same_live(d_in, d_w_packed, d_bias, d_out, n, cin, cout, height, width, ksize, groups, relu, d_pixels,
+                                d_pixel_count, d_background, nullptr, stream);
 }

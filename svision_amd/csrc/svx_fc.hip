@@ -51,7 +51,8 @@ __device__ __forceinline__ void svx_tail_stages(F& f, int left)
     }
 }
 
-struct FcArgs { const float* x; const float* w; float* part; int M, N, K, splits; };
+// live: NULL, or the number of leading rows to compute (device); the tiling and the split count stay those of M
+struct FcArgs { const float* x; const float* w; float* part; int M, N, K, splits; const uint32_t* live; };
 
 template <int NA, int NB>
 __global__ __launch_bounds__(THREADS, 2)
@@ -64,6 +65,8 @@ void fc_splitk_kernel(const FcArgs a)
     if (wt >= total) return;
     const int nt = wt % n_tiles, rest = wt / n_tiles;
     const int s = rest % a.splits, mt = rest / a.splits;
+    const int m_live = a.live ? min((int)*a.live, a.M) : a.M;
+    if (mt * 32 * NB >= m_live) return;                              // a tile behind the launch's distinct images
     const int lane = threadIdx.x & 63, hi = lane >> 5, lo = lane & 31;
     const int KQ = a.K / 8;
     const int q0 = (int)((long long)KQ * s / a.splits), q1 = (int)((long long)KQ * (s + 1) / a.splits);
@@ -133,7 +136,7 @@ void fc_splitk_kernel(const FcArgs a)
 #pragma unroll
         for (int t = 0; t < NB; ++t) {
             const int m = (mt * NB + t) * 32 + lo;
-            if (m >= a.M) continue;
+            if (m >= m_live) continue;
             float* o = a.part + ((size_t)s * a.M + m) * a.N + (nt * NA + i) * 32 + 4 * hi;
 #pragma unroll
             for (int u = 0; u < 4; ++u)
@@ -143,10 +146,11 @@ void fc_splitk_kernel(const FcArgs a)
 
 // out[m][n] = act(bias[n] + part[0][m][n] + part[1][m][n] + ...): fixed order, one float4 per lane
 __global__ __launch_bounds__(THREADS)
-void fc_reduce_kernel(const float* __restrict__ part, const float* __restrict__ bias, float* __restrict__ out, int MN4, int N4, int splits, int relu)
+void fc_reduce_kernel(const float* __restrict__ part, const float* __restrict__ bias, float* __restrict__ out, int MN4, int N4, int splits, int relu,
+                      const uint32_t* __restrict__ live)
 {
     const int e = blockIdx.x * THREADS + threadIdx.x;
-    if (e >= MN4) return;
+    if (e >= MN4 || (live && (uint32_t)(e / N4) >= *live)) return;
     const float4* p = reinterpret_cast<const float4*>(part);
     float4 v = reinterpret_cast<const float4*>(bias)[e % N4];
     for (int s = 0; s < splits; ++s) { const float4 q = p[(size_t)s * MN4 + e]; v.x += q.x; v.y += q.y; v.z += q.z; v.w += q.w; }
@@ -186,8 +190,8 @@ extern "C" size_t svx_fc_ws_bytes(uint32_t m, uint32_t n, uint32_t k)
     return (size_t)fc_splits(m, n, k) * m * n * sizeof(float);
 }
 
-extern "C" int svx_fc_bias_act(const float* d_x, const float* d_w_packed, const float* d_bias, float* d_out, float* d_ws,
-                               uint32_t m, uint32_t n, uint32_t k, int relu, void* stream)
+extern "C" int svx_fc_bias_act_live(const float* d_x, const float* d_w_packed, const float* d_bias, float* d_out, float* d_ws,
+                                    uint32_t m, uint32_t n, uint32_t k, int relu, const uint32_t* d_live, void* stream)
 {
     if (m == 0) return SVX_OK;
     if (!d_x || !d_w_packed || !d_bias || !d_out || !d_ws || n % 32 || k % 8 || k < 24 * 8) return SVX_EINVAL;
@@ -195,7 +199,7 @@ extern "C" int svx_fc_bias_act(const float* d_x, const float* d_w_packed, const 
         if (reinterpret_cast<uintptr_t>(p) & 15u) return SVX_EINVAL;
     if ((uint64_t)n * k * 4 > 0x7fffffffull || (uint64_t)m * k * 4 > 0x7fffffffull) return SVX_EINVAL;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    FcArgs a{d_x, d_w_packed, d_ws, (int)m, (int)n, (int)k, fc_splits(m, n, k)};
+    FcArgs a{d_x, d_w_packed, d_ws, (int)m, (int)n, (int)k, fc_splits(m, n, k), d_live};
     const int m_tiles = (int)((m + 63) / 64);
     const int na = fc_na(m, n);
     const int waves = m_tiles * a.splits * (int)(n / (32 * na));
@@ -204,6 +208,12 @@ extern "C" int svx_fc_bias_act(const float* d_x, const float* d_w_packed, const 
     else if (m <= 32) hipLaunchKernelGGL((fc_splitk_kernel<1, 1>), grid, dim3(THREADS), 0, st, a);
     else              hipLaunchKernelGGL((fc_splitk_kernel<1, 2>), grid, dim3(THREADS), 0, st, a);
     const int mn4 = (int)((uint64_t)m * n / 4);
-    hipLaunchKernelGGL(fc_reduce_kernel, dim3((mn4 + THREADS - 1) / THREADS), dim3(THREADS), 0, st, d_ws, d_bias, d_out, mn4, (int)(n / 4), a.splits, relu);
+    hipLaunchKernelGGL(fc_reduce_kernel, dim3((mn4 + THREADS - 1) / THREADS), dim3(THREADS), 0, st, d_ws, d_bias, d_out, mn4, (int)(n / 4), a.splits, relu, d_live);
     return hipGetLastError() == hipSuccess ? SVX_OK : SVX_ELAUNCH;
+}
+
+extern "C" int svx_fc_bias_act(const float* d_x, const float* d_w_packed, const float* d_bias, float* d_out, float* d_ws,
+                               uint32_t m, uint32_t n, uint32_t k, int relu, void* stream)
+{
+    return svx_fc_bias_act_live(d_x, d_w_packed, d_bias, d_out, d_ws, m, n, k, relu, nullptr, stream);
 }

@@ -101,6 +101,51 @@ __device__ inline void line_pixel(const Line& l, int k, int& col, int& row)
 __device__ inline long long scale_coord(int v, double ratio) { return (long long)((double)v / ratio); }
 
 
+// Line set-up of segment s (0 or 1) of a 12-int record: fp64 scaling by the record's ratio, then clipLine + LineIterator
+// set-up; rev = the segment is reverse (drawn into the reverse-segment plane too).  The ONE source of the geometry: the
+// rasterisers draw from it and svx_image_dedup keys images on it (same Lines + same rev flags = same bit planes).
+__device__ inline Line record_line(const int32_t* __restrict__ r, int s, int& rev)
+{
+    const int read_len = r[10], ref_len = r[11];
+    double ratio = (double)(read_len > ref_len ? read_len : ref_len) / 227.0;
+    if (ratio < 1) ratio = 1;
+    const int xs = r[s * 5 + 0], ys = r[s * 5 + 2];
+    const long long len = (long long)r[s * 5 + 3] - (long long)ys;
+    const int fwd = r[s * 5 + 4] != 0;
+    const long long xe = fwd ? (long long)xs + (len - 1) : (long long)xs - (len - 1);
+    const long long ye = (long long)ys + (len - 1);
+    const long long cs = scale_coord(ys, ratio), rs = scale_coord(xs, ratio);
+    const long long ce = (long long)((double)ye / ratio), re = (long long)((double)xe / ratio);
+    rev = !fwd;
+    return fwd ? setup_line(cs, rs, ce, re) : setup_line(ce, re, cs, rs);
+}
+
+__device__ inline void record_lines(const int32_t* __restrict__ r, Line lines[2], int rev[2])
+{
+    lines[0] = record_line(r, 0, rev[0]);
+    lines[1] = record_line(r, 1, rev[1]);
+}
+
+// Exact 128-bit image key: the two canonical Lines and the two reverse flags, every field packed losslessly (after
+// clipLine every coordinate and extent lies in [0, IMG), count in [0, IMG]).  Equal keys = equal bit planes by construction;
+// no hash, so no collision can merge two different images.
+//   x: x0 | y0 << 8 | dx << 16 | dy << 24 of line 0,  y: the same of line 1,
+//   z: (sy < 0) | steep << 1 | rev << 2 of line 0, the same << 8 of line 1,  w: count0 | count1 << 16
+static_assert(IMG <= 256, "the image key packs a coordinate into 8 bits");
+__device__ inline uint4 image_key(const int32_t* __restrict__ r)
+{
+    Line l[2];
+    int rev[2];
+    record_lines(r, l, rev);
+    uint4 k;
+    k.x = (unsigned)l[0].x0 | (unsigned)l[0].y0 << 8 | (unsigned)l[0].dx << 16 | (unsigned)l[0].dy << 24;
+    k.y = (unsigned)l[1].x0 | (unsigned)l[1].y0 << 8 | (unsigned)l[1].dx << 16 | (unsigned)l[1].dy << 24;
+    k.z = (unsigned)(l[0].sy < 0) | (unsigned)l[0].steep << 1 | (unsigned)rev[0] << 2 |
+          ((unsigned)(l[1].sy < 0) | (unsigned)l[1].steep << 1 | (unsigned)rev[1] << 2) << 8;
+    k.w = (unsigned)l[0].count | (unsigned)l[1].count << 16;
+    return k;
+}
+
 // Draw one record's three bit planes into LDS.  bits: 3 * PLANE_WORDS words (plane 0: all segments,
 // plane 1: columns with >= 2 hits, plane 2: reverse segments), colcnt: IMG words, colmask: ROW_WORDS
 // words.  Must be called by every thread of the block; ends with a barrier.
@@ -118,21 +163,7 @@ __device__ inline void draw_planes(const int32_t* __restrict__ r, unsigned* bits
     // two lanes derive the two line set-ups (fp64 scaling + clipLine) and publish them through LDS
     __shared__ Line sh_lines[2];
     __shared__ int sh_rev[2];
-    if (tid < 2) {
-        const int s = tid;
-        const int read_len = r[10], ref_len = r[11];
-        double ratio = (double)(read_len > ref_len ? read_len : ref_len) / 227.0;
-        if (ratio < 1) ratio = 1;
-        const int xs = r[s * 5 + 0], ys = r[s * 5 + 2];
-        const long long len = (long long)r[s * 5 + 3] - (long long)ys;
-        const int fwd = r[s * 5 + 4] != 0;
-        const long long xe = fwd ? (long long)xs + (len - 1) : (long long)xs - (len - 1);
-        const long long ye = (long long)ys + (len - 1);
-        const long long cs = scale_coord(ys, ratio), rs = scale_coord(xs, ratio);
-        const long long ce = (long long)((double)ye / ratio), re = (long long)((double)xe / ratio);
-        sh_rev[s] = !fwd;
-        sh_lines[s] = fwd ? setup_line(cs, rs, ce, re) : setup_line(ce, re, cs, rs);
-    }
+    if (tid < 2) sh_lines[tid] = record_line(r, tid, sh_rev[tid]);
     __syncthreads();
     Line lines[2] = {sh_lines[0], sh_lines[1]};
     const int rev[2] = {sh_rev[0], sh_rev[1]};

@@ -152,10 +152,56 @@ def cigar_scan(cigar, cig_off, ref_start, min_sv, gaps_cap=None, mode=None, n_wo
     return res
 
 
-def bias_relu_pool_lrn(x, bias, lrn=True, radius=2, alpha=2e-05, beta=0.75, k=1.0, active_rows=None, background=None):
+def _check_live(live):
+    """``live``: None, or a one-element int32 device tensor (:func:`image_dedup`): the leading rows a *_live kernel computes."""
+    if live is not None and (not live.is_cuda or live.dtype != torch.int32 or live.numel() != 1):
+        raise _lib.SvxError("live must be a one-element int32 device tensor")
+    return live.data_ptr() if live is not None else None
+
+
+def image_dedup(records, keys=False):
+    """records int32 [n,12] -> (unique int32 [n,12], inv int32 [n], live int32 [1]) device tensors: the first occurrence of
+    every distinct image in input order (rows >= live repeat record 0), the row of ``unique`` that holds each record's
+    image, and the number of distinct images -- all on the device, no synchronisation.  ``keys=True``: also the exact
+    128-bit image keys, int32 [n,4].  See include/svx.h svx_image_dedup."""
+    lib = _lib.load()
+    _require_cuda(records, "records")
+    if records.dtype != torch.int32 or records.dim() != 2 or records.shape[1] != 12:
+        raise _lib.SvxError("records must be int32 [n,12]")
+    n, dev = records.shape[0], records.device
+    unique = torch.empty((n, 12), dtype=torch.int32, device=dev)
+    inv = torch.empty(n, dtype=torch.int32, device=dev)
+    live = torch.empty(1, dtype=torch.int32, device=dev)
+    ws = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+    k = torch.empty((n, 4), dtype=torch.int32, device=dev) if keys else None
+    rc = lib.svx_image_dedup(records.data_ptr(), n, unique.data_ptr(), inv.data_ptr(), live.data_ptr(),
+                             k.data_ptr() if keys else None, ws.data_ptr(), _stream_ptr(dev))
+    _lib.check(rc, "svx_image_dedup")
+    return (unique, inv, live, k) if keys else (unique, inv, live)
+
+
+def gather_rows(src, inv, out=None):
+    """out[i] = src[inv[i]]: float32 [m,w] rows, inv int32 [n] -> float32 [n,w].  See include/svx.h svx_gather_rows."""
+    lib = _lib.load()
+    _require_cuda(src, "src")
+    _require_cuda(inv, "inv")
+    if src.dtype != torch.float32 or src.dim() != 2 or inv.dtype != torch.int32 or inv.dim() != 1:
+        raise _lib.SvxError("src must be float32 [m,w] and inv int32 [n]")
+    n, w = inv.shape[0], src.shape[1]
+    if out is None:
+        out = torch.empty((n, w), dtype=torch.float32, device=src.device)
+    elif tuple(out.shape) != (n, w) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise _lib.SvxError("out must be a contiguous float32 [n,w] tensor")
+    rc = lib.svx_gather_rows(src.data_ptr(), inv.data_ptr(), out.data_ptr(), n, w, _stream_ptr(src.device))
+    _lib.check(rc, "svx_gather_rows")
+    return out
+
+
+def bias_relu_pool_lrn(x, bias, lrn=True, radius=2, alpha=2e-05, beta=0.75, k=1.0, active_rows=None, background=None, live=None):
     """x: float32 C8 [n,C/8,H,W,8] raw conv output -> relu(x+bias) -> max-pool 3x3/2 -> (LRN) as one kernel, C8 out.
     ``active_rows`` (int32 [n,H] row masks) + ``background`` (C8 [C/8,H,W,8]): pixels whose bit is clear are read from the
-    background instead of ``x`` (an active-set convolution that did not write them).  See include/svx.h svx_bias_relu_pool_lrn."""
+    background instead of ``x`` (an active-set convolution that did not write them).  ``live``: rows >= live are skipped
+    (:func:`image_dedup`).  See include/svx.h svx_bias_relu_pool_lrn."""
     lib = _lib.load()
     _require_cuda(x, "x")
     _require_cuda(bias, "bias")
@@ -172,17 +218,19 @@ def bias_relu_pool_lrn(x, bias, lrn=True, radius=2, alpha=2e-05, beta=0.75, k=1.
                 or tuple(background.shape)[-4:] != (o, h, w, 8) or background.numel() != o * h * w * 8 \
                 or not background.is_contiguous() or not active_rows.is_contiguous():
             raise _lib.SvxError("active_rows must be int32 [n,H] and background float32 C8 [C/8,H,W,8]")
-    rc = lib.svx_bias_relu_pool_lrn(x.data_ptr(), bias.data_ptr(), y.data_ptr(), n, o * 8, h, w, 1 if lrn else 0, radius,
-                                    alpha, beta, k, active_rows.data_ptr() if active_rows is not None else None,
-                                    background.data_ptr() if background is not None else None, _stream_ptr(x.device))
+    rc = lib.svx_bias_relu_pool_lrn_live(x.data_ptr(), bias.data_ptr(), y.data_ptr(), n, o * 8, h, w, 1 if lrn else 0, radius,
+                                         alpha, beta, k, active_rows.data_ptr() if active_rows is not None else None,
+                                         background.data_ptr() if background is not None else None, _check_live(live),
+                                         _stream_ptr(x.device))
     _lib.check(rc, "svx_bias_relu_pool_lrn")
     return y
 
 
-def encode_conv1(records, w1_hwio, base, lrn=True, radius=2, alpha=2e-05, beta=0.75, k=1.0, touched=False):
+def encode_conv1(records, w1_hwio, base, lrn=True, radius=2, alpha=2e-05, beta=0.75, k=1.0, touched=False, live=None):
     """records int32 [n,12] -> float32 C8 [n,12,27,27,8]: rasterise + conv1 + relu + pool1 + norm1 in one
     kernel, exploiting the sparsity of the similarity image.  See include/svx.h svx_encode_conv1.
-    ``touched=True``: also return the int32 [n,27] row masks of the pooled pixels with a set tap under them."""
+    ``touched=True``: also return the int32 [n,27] row masks of the pooled pixels with a set tap under them.
+    ``live``: rows >= live are skipped (:func:`image_dedup`)."""
     lib = _lib.load()
     for t, nm in ((records, "records"), (w1_hwio, "w1"), (base, "base")):
         _require_cuda(t, nm)
@@ -193,16 +241,18 @@ def encode_conv1(records, w1_hwio, base, lrn=True, radius=2, alpha=2e-05, beta=0
     n = records.shape[0]
     y = torch.empty((n, 12, 27, 27, 8), dtype=torch.float32, device=records.device)
     mask = torch.empty((n, 27), dtype=torch.int32, device=records.device) if touched else None
-    rc = lib.svx_encode_conv1(records.data_ptr(), n, w1_hwio.data_ptr(), base.data_ptr(), y.data_ptr(), 1 if lrn else 0,
-                              radius, alpha, beta, k, mask.data_ptr() if touched else None, _stream_ptr(records.device))
+    rc = lib.svx_encode_conv1_live(records.data_ptr(), n, w1_hwio.data_ptr(), base.data_ptr(), y.data_ptr(), 1 if lrn else 0,
+                                   radius, alpha, beta, k, mask.data_ptr() if touched else None, _check_live(live),
+                                   _stream_ptr(records.device))
     _lib.check(rc, "svx_encode_conv1")
     return (y, mask) if touched else y
 
 
-def alexnet_active_sets(touched, totals=None, rows=False):
+def alexnet_active_sets(touched, totals=None, rows=False, live=None):
     """touched int32 [n,27] (encode_conv1) -> (list2 [n*729], list3, list4, list5 [n*169], counts [4]) int32 device
     tensors: the output pixels of conv2..conv5 that can differ from the response to an empty image.
     ``totals``: optional int64 device tensor [5] the launch adds its executed pixel counts (conv2..conv5) and image count to.
+    ``live``: the lists cover the leading ``live`` images only (:func:`image_dedup`).
     See include/svx.h svx_alexnet_active_sets."""
     lib = _lib.load()
     _require_cuda(touched, "touched")
@@ -215,22 +265,23 @@ def alexnet_active_sets(touched, totals=None, rows=False):
     counts = torch.empty(4, dtype=torch.int32, device=dev)
     ws = torch.empty(max(n, 1) * 4, dtype=torch.int32, device=dev)
     active2 = torch.empty((n, 27), dtype=torch.int32, device=dev) if rows else None
-    rc = lib.svx_alexnet_active_sets(touched.data_ptr(), n, lists[0].data_ptr(), lists[1].data_ptr(), lists[2].data_ptr(),
-                                     lists[3].data_ptr(), counts.data_ptr(), ws.data_ptr(),
-                                     totals.data_ptr() if totals is not None else None,
-                                     active2.data_ptr() if rows else None, _stream_ptr(dev))
+    rc = lib.svx_alexnet_active_sets_live(touched.data_ptr(), n, lists[0].data_ptr(), lists[1].data_ptr(), lists[2].data_ptr(),
+                                          lists[3].data_ptr(), counts.data_ptr(), ws.data_ptr(),
+                                          totals.data_ptr() if totals is not None else None,
+                                          active2.data_ptr() if rows else None, _check_live(live), _stream_ptr(dev))
     _lib.check(rc, "svx_alexnet_active_sets")
     if rows:                                                  # + int32 [n,27] row masks of conv2's active pixels
         return lists[0], lists[1], lists[2], lists[3], counts, active2
     return lists[0], lists[1], lists[2], lists[3], counts
 
 
-def conv2d_same(x, w_packed, bias=None, groups=1, relu=False, pixels=None, pixel_count=None, out=None, background=None):
+def conv2d_same(x, w_packed, bias=None, groups=1, relu=False, pixels=None, pixel_count=None, out=None, background=None, live=None):
     """x float32 C8 [n,Cin/8,H,W,8], w_packed float32 [k,k,Cin/groups/8,Cout,8] (:func:`pack_conv_weights`) -> C8
     [n,Cout/8,H,W,8]: stride-1 SAME convolution on the fp32 matrix cores, optional fused bias + ReLU.
     ``pixels`` / ``pixel_count`` (device int32 permutation of the pixel ids and the number of leading active entries,
     a one-element view): compute only the active output pixels; the others receive ``background`` (C8 [Cout/8,H,W,8]) or,
-    without it, keep what ``out`` holds.  See include/svx.h svx_conv2d_same."""
+    without it, keep what ``out`` holds.  ``live`` (list mode): the lists cover the leading ``live`` images only
+    (:func:`alexnet_active_sets`).  See include/svx.h svx_conv2d_same."""
     lib = _lib.load()
     _require_cuda(x, "x")
     _require_cuda(w_packed, "w_packed")
@@ -245,16 +296,19 @@ def conv2d_same(x, w_packed, bias=None, groups=1, relu=False, pixels=None, pixel
         _require_cuda(bias, "bias")
     if (pixels is None) != (pixel_count is None) or (pixels is not None and out is None and background is None):
         raise _lib.SvxError("pixels and pixel_count go together, with out or background")
+    if live is not None and pixels is None:
+        raise _lib.SvxError("live needs pixels")
     if background is not None and (pixels is None or tuple(background.shape[-4:]) != (cout // 8, h, w, 8) or not background.is_contiguous()):
         raise _lib.SvxError("background must be a contiguous float32 C8 [Cout/8,H,W,8] tensor and needs pixels")
     y = out if out is not None else torch.empty((n, cout // 8, h, w, 8), dtype=torch.float32, device=x.device)
     if tuple(y.shape) != (n, cout // 8, h, w, 8) or y.dtype != torch.float32 or not y.is_contiguous():
         raise _lib.SvxError("out must be a contiguous float32 C8 [n,Cout/8,H,W,8] tensor")
-    rc = lib.svx_conv2d_same(x.data_ptr(), w_packed.data_ptr(), bias.data_ptr() if bias is not None else None, y.data_ptr(),
-                             n, cin, cout, h, w, k, groups, 1 if relu else 0,
-                             pixels.data_ptr() if pixels is not None else None,
-                             pixel_count.data_ptr() if pixel_count is not None else None,
-                             background.data_ptr() if background is not None else None, _stream_ptr(x.device))
+    rc = lib.svx_conv2d_same_live(x.data_ptr(), w_packed.data_ptr(), bias.data_ptr() if bias is not None else None, y.data_ptr(),
+                                  n, cin, cout, h, w, k, groups, 1 if relu else 0,
+                                  pixels.data_ptr() if pixels is not None else None,
+                                  pixel_count.data_ptr() if pixel_count is not None else None,
+                                  background.data_ptr() if background is not None else None, _check_live(live),
+                                  _stream_ptr(x.device))
     _lib.check(rc, "svx_conv2d_same")
     return y
 
@@ -267,9 +321,10 @@ def pack_fc_weights(w_out_in):
     return w_out_in.reshape(n // 32, 32, k // 8, 8).permute(0, 2, 1, 3).contiguous()
 
 
-def fc_bias_act(x, w_packed, bias, relu=True, out=None, ws=None):
+def fc_bias_act(x, w_packed, bias, relu=True, out=None, ws=None, live=None):
     """x float32 [m,k], w_packed [n/32,k/8,32,8] (:func:`pack_fc_weights`), bias [n] -> act(x @ W^T + bias) [m,n] on the
-    fp32 matrix cores (split-K wave tiles + ordered reduction).  See include/svx.h svx_fc_bias_act."""
+    fp32 matrix cores (split-K wave tiles + ordered reduction).  ``live``: rows >= live are skipped; the split-K grouping
+    stays that of m.  See include/svx.h svx_fc_bias_act."""
     lib = _lib.load()
     for t, nm in ((x, "x"), (w_packed, "w_packed"), (bias, "bias")):
         _require_cuda(t, nm)
@@ -284,15 +339,15 @@ def fc_bias_act(x, w_packed, bias, relu=True, out=None, ws=None):
     need = lib.svx_fc_ws_bytes(m, n, k)
     if ws is None or ws.numel() * ws.element_size() < need:
         ws = torch.empty(max(need, 16) // 4, dtype=torch.float32, device=x.device)
-    rc = lib.svx_fc_bias_act(x.data_ptr(), w_packed.data_ptr(), bias.data_ptr(), out.data_ptr(), ws.data_ptr(), m, n, k, 1 if relu else 0,
-                             _stream_ptr(x.device))
+    rc = lib.svx_fc_bias_act_live(x.data_ptr(), w_packed.data_ptr(), bias.data_ptr(), out.data_ptr(), ws.data_ptr(), m, n, k,
+                                  1 if relu else 0, _check_live(live), _stream_ptr(x.device))
     _lib.check(rc, "svx_fc_bias_act")
     return out
 
 
-def fc8_softmax(x, w_out_in, bias, out=None):
+def fc8_softmax(x, w_out_in, bias, out=None, live=None):
     """x float32 [n,4096], w float32 [5,4096], bias [5] -> packed float32 [n,12] = softmax[5], class, logits[5], 0.
-    See include/svx.h svx_fc8_softmax."""
+    ``live``: rows >= live are skipped.  See include/svx.h svx_fc8_softmax."""
     lib = _lib.load()
     for t, nm in ((x, "x"), (w_out_in, "w"), (bias, "bias")):
         _require_cuda(t, nm)
@@ -301,7 +356,8 @@ def fc8_softmax(x, w_out_in, bias, out=None):
     n = x.shape[0]
     if out is None:
         out = torch.empty((n, 12), dtype=torch.float32, device=x.device)
-    rc = lib.svx_fc8_softmax(x.data_ptr(), w_out_in.data_ptr(), bias.data_ptr(), out.data_ptr(), n, _stream_ptr(x.device))
+    rc = lib.svx_fc8_softmax_live(x.data_ptr(), w_out_in.data_ptr(), bias.data_ptr(), out.data_ptr(), n, _check_live(live),
+                                  _stream_ptr(x.device))
     _lib.check(rc, "svx_fc8_softmax")
     return out
 

@@ -8,12 +8,18 @@ pool, LRN; conv3/4/5 3x3 SAME (g=1,2,2), pool; fc6/fc7 (ReLU), fc8 -> 5 logits
 candidate image (TSV columns 1..12), not the image: rasterisation and the first
 layer are one kernel.
 
+    svx_image_dedup           one pass per distinct image: equal line set-ups -> one row (exact key), device live count
     svx_encode_conv1          rasterise + conv1 + relu + pool1 + norm1 (sparse: the image is a few thin lines)
     svx_alexnet_active_sets   which outputs of conv2..conv5 can differ from the response to an empty image
     svx_conv2d_same           conv2..conv5 on the fp32 matrix cores, active pixels only (list mode), bias+relu fused
     svx_bias_relu_pool_lrn    conv2 / conv5 epilogues
     svx_fc_bias_act           fc6 / fc7 (+ bias + relu) as a weight stream feeding fp32 MFMAs, split-K, ordered reduce
     svx_fc8_softmax           fc8 + softmax + argmax + packing
+    svx_gather_rows           the packed rows of the distinct images back to one row per record
+
+With the image memo (default; ``memo=False`` or SVX_IMAGE_MEMO=0 turns it off) every stage after svx_image_dedup is
+the *_live variant of its kernel: a launch keeps its size (a captured graph is fixed) and the rows behind the distinct
+images cost nothing; every record still gets its own packed row, bit for bit the one it gets without the memo.
 
 Parameters keep the checkpoint's names and layouts (``convN/weights`` HWIO,
 ``fcN/weights`` [in,out]) at the ``-m`` boundary and are re-laid out once for the device:
@@ -62,14 +68,21 @@ def validate_params(params):
             raise ValueError(f"{k} has shape {tuple(np.shape(params[k]))}, expected {shp}")
 
 
+def memo_default():
+    """The image memo is on unless SVX_IMAGE_MEMO=0 (A/B runs of an unchanged command line)."""
+    import os
+    return os.environ.get("SVX_IMAGE_MEMO", "1") != "0"
+
+
 class AlexNet(torch.nn.Module):
     """Inference-only AlexNet holding device-layout parameters.  ``active=False`` computes conv2..conv5 at every pixel
     (same kernels in dense mode; the test suite requires both settings to agree bit for bit)."""
 
-    def __init__(self, params, device="cuda", mean=(104.0, 117.0, 124.0), active=True, packed=None):
+    def __init__(self, params, device="cuda", mean=(104.0, 117.0, 124.0), active=True, packed=None, memo=None):
         super().__init__()
         from .. import kernels
         self.active = bool(active)
+        self.memo = memo_default() if memo is None else bool(memo)       # one network pass per distinct image of a launch
         self._background = None
         self.executed = None            # optional int64 device tensor [5]: running executed-pixel / image counts (bench)
         if packed is not None:          # device-layout tensors of an earlier process (weight_cache.load): one upload, views
@@ -130,8 +143,9 @@ class AlexNet(torch.nn.Module):
         if all("background/" + k in names for k in self._BG):
             self._background = {k: view("background/" + k) for k in self._BG}
 
-    def _convs(self, records):
-        """records int32 [B,12] -> pool5 activations, C8 [B,32,6,6,8]."""
+    def _convs(self, records, live=None):
+        """records int32 [B,12] -> pool5 activations, C8 [B,32,6,6,8].  ``live`` (int32 device [1]): only the leading
+        ``live`` rows are computed (the dense path computes every row: its rows behind them hold valid records)."""
         from .. import kernels
         if not self.active:
             x = kernels.encode_conv1(records, self.conv1_hwio, self.conv1_base)
@@ -142,22 +156,22 @@ class AlexNet(torch.nn.Module):
             x = kernels.conv2d_same(x, self.conv5_w, None, groups=2)
             return kernels.bias_relu_pool_lrn(x, self.conv5_b, lrn=False)
         bg = self.background()
-        x, touched = kernels.encode_conv1(records, self.conv1_hwio, self.conv1_base, touched=True)
-        l2, l3, l4, l5, counts, rows2 = kernels.alexnet_active_sets(touched, totals=self.executed, rows=True)
+        x, touched = kernels.encode_conv1(records, self.conv1_hwio, self.conv1_base, touched=True, live=live)
+        l2, l3, l4, l5, counts, rows2 = kernels.alexnet_active_sets(touched, totals=self.executed, rows=True, live=live)
 
         def conv(name, x, pixels, k, bias, relu, groups):
             # active pixels computed, the others copied from the background by the workgroups behind the compute tiles
             return kernels.conv2d_same(x, getattr(self, name + "_w"), bias, groups=groups, relu=relu, pixels=pixels,
-                                       pixel_count=counts[k:k + 1], background=bg[name])
+                                       pixel_count=counts[k:k + 1], background=bg[name], live=live)
         # conv2 writes its active pixels only (61 % of its output would be copies of the background, and that copy is
         # not hidden behind the matrix work): the pool reads the background for the others itself
-        x = kernels.conv2d_same(x, self.conv2_w, None, groups=2, pixels=l2, pixel_count=counts[0:1],
+        x = kernels.conv2d_same(x, self.conv2_w, None, groups=2, pixels=l2, pixel_count=counts[0:1], live=live,
                                 out=torch.empty((records.shape[0], 32, 27, 27, 8), dtype=torch.float32, device=records.device))
-        x = kernels.bias_relu_pool_lrn(x, self.conv2_b, lrn=True, active_rows=rows2, background=bg["conv2"])
+        x = kernels.bias_relu_pool_lrn(x, self.conv2_b, lrn=True, active_rows=rows2, background=bg["conv2"], live=live)
         x = conv("conv3", x, l3, 1, self.conv3_b, True, 1)
         x = conv("conv4", x, l4, 2, self.conv4_b, True, 2)
         x = conv("conv5", x, l5, 3, None, False, 2)
-        return kernels.bias_relu_pool_lrn(x, self.conv5_b, lrn=False)
+        return kernels.bias_relu_pool_lrn(x, self.conv5_b, lrn=False, live=live)
 
     @torch.no_grad()
     def background(self):
@@ -185,15 +199,25 @@ class AlexNet(torch.nn.Module):
         return self._background
 
     @torch.no_grad()
-    def predict_records_packed(self, records, out=None):
+    def predict_records_packed(self, records, out=None, memo=None):
         """records int32 device tensor [B,12] (TSV columns 1..12) -> float32 [B,12] = softmax[5], class, logits[5], 0:
-        the three fetches of predict.py:209 in one packed row per image."""
+        the three fetches of predict.py:209 in one packed row per image.  ``memo`` (default: the model's): the network
+        runs once per distinct image of the launch (svx_image_dedup), the rows are gathered back per record."""
         from .. import kernels
-        x = self._convs(records)
+        memo = self.memo if memo is None else bool(memo)
+        live = inv = None
+        if memo and records.shape[0] > 0:
+            records, inv, live = kernels.image_dedup(records)
+        x = self._convs(records, live)
         x = x.reshape(x.shape[0], 9216)
-        x = kernels.fc_bias_act(x, self.fc6_w, self.fc6_b, relu=True)
-        x = kernels.fc_bias_act(x, self.fc7_w, self.fc7_b, relu=True)
-        return kernels.fc8_softmax(x, self.fc8_w, self.fc8_b, out=out)
+        # fc6 / fc7 keep the split-K grouping of the launch size B (a function of m): every row sums in the order it
+        # would without the memo
+        x = kernels.fc_bias_act(x, self.fc6_w, self.fc6_b, relu=True, live=live)
+        x = kernels.fc_bias_act(x, self.fc7_w, self.fc7_b, relu=True, live=live)
+        if live is None:
+            return kernels.fc8_softmax(x, self.fc8_w, self.fc8_b, out=out)
+        packed = kernels.fc8_softmax(x, self.fc8_w, self.fc8_b, live=live)
+        return kernels.gather_rows(packed, inv, out=out)
 
     @torch.no_grad()
     def predict_records(self, records):

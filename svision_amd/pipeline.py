@@ -175,10 +175,15 @@ class DeviceStage:
     ``launch_batches`` of them while that many are left, then half as many, ... down to single batches.  Every image is
     independent of its neighbours in every kernel (fixed k order per output element, tests/test_gpu_pipeline.py), so the
     grouping changes no result; it divides the fc6 / fc7 weight traffic per image (218 MB per launch whatever its size) and
-    the share of partly filled tile rounds of the convolutions."""
+    the share of partly filled tile rounds of the convolutions.
 
-    def __init__(self, net, batch, device, n_streams=2, use_graph=True, launch_batches=4, lazy=False):
+    ``memo`` (None: the model's setting, on unless SVX_IMAGE_MEMO=0): each launch runs the network once per distinct image
+    (svx_image_dedup inside the graph; the rows behind the distinct ones cost nothing) and gathers the packed rows back per
+    record -- the same rows, bit for bit, as without it."""
+
+    def __init__(self, net, batch, device, n_streams=2, use_graph=True, launch_batches=4, lazy=False, memo=None):
         self.net, self.batch, self.device = net, batch, torch.device(device)
+        self.memo = memo
         self.streams = [torch.cuda.Stream(device=self.device) for _ in range(n_streams)]
         self.use_graph = use_graph
         sizes, k = {batch}, max(1, int(launch_batches))
@@ -218,7 +223,7 @@ class DeviceStage:
         return slot
 
     def _body(self, rec, out):
-        self.net.predict_records_packed(rec, out=out)        # no image tensor: encoding is fused into the first layer
+        self.net.predict_records_packed(rec, out=out, memo=self.memo)     # no image tensor: encoding is fused into the first layer
 
     def run(self, d_rec, out, after=None, timing=None):
         """d_rec: int32 [n_padded,12] on the device (n_padded % batch == 0); out: float32 [n_padded,6].
