@@ -313,7 +313,7 @@ void bgzf_inflate_kernel(const uint8_t* __restrict__ comp, const uint64_t* __res
     int err = INF_OK;
     __attribute__((aligned(16))) uint8_t lens[LIT_SYMS + DIST_SYMS];
     bool last = false;
-    int state = w.hi == w.lo ? ST_DONE : ST_HEADER;             // an empty block (the EOF marker): nothing to decode
+    int state = ST_HEADER;                                      // (an empty block is decoded too: its stream must hold no byte)
     // One loop for the whole block, every lane in its own state: a lane that reaches the end of a DEFLATE block parses the
     // next header while the others go on decoding (an inner symbol loop per DEFLATE block made every lane wait, at every
     // block boundary, for the slowest of the wave).
@@ -598,7 +598,7 @@ void bgzf_inflate_wave_kernel(const uint8_t* __restrict__ comp, const uint64_t* 
     br.init(comp, src_off[b], src_len[b]);
     WaveWriter w{out, dst_off[b], dst_off[b], dst_off[b + 1], 0u};
     int err = INF_OK;
-    bool last = w.hi == w.lo;
+    bool last = false;                                          // (an empty block is decoded too: its stream must hold no byte)
     while (!last && err == INF_OK) {
         last = br.bits(1) != 0;
         const uint32_t type = br.bits(2);

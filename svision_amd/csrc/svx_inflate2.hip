@@ -333,7 +333,7 @@ void bgzf_tokens_kernel(const uint8_t* __restrict__ comp, const uint64_t* __rest
     uint32_t P = 0, W = 0, Q = pad;                  // (uniform) bit position, bytes decoded, stream bytes written
     uint32_t H = 0, Lc = 0;                          // (SPLIT, uniform) sequences and literal bytes written
     int err = INF_OK;
-    bool last = isize == 0;                          // an empty block (the EOF marker): nothing to decode
+    bool last = false;                               // (an empty block is decoded too: its stream must hold no byte -- the EOF marker's is 03 00)
     HeadReader hr;
     while (!last && err == INF_OK) {
         hr.seek(src, nbytes, P);

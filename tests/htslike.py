@@ -83,17 +83,21 @@ def encode_record(rec):
     return struct.pack("<i", len(body)) + body
 
 
-def _bgzf_block(data, level):
-    co = zlib.compressobj(level, zlib.DEFLATED, -15)
-    c = co.compress(data) + co.flush()
+def _bgzf_block(data, level, deflate=None):
+    if deflate is None:
+        co = zlib.compressobj(level, zlib.DEFLATED, -15)
+        c = co.compress(data) + co.flush()
+    else:
+        c = deflate(data)
     assert len(c) + 26 <= 65536
     return (b"\x1f\x8b\x08\x04\x00\x00\x00\x00\x00\xff\x06\x00BC\x02\x00" + struct.pack("<H", len(c) + 25) + c
             + struct.pack("<II", zlib.crc32(data) & 0xFFFFFFFF, len(data)))
 
 
-def write_bam(path, references, records, level=6, policy="htslib", header_text=None, index=True):
+def write_bam(path, references, records, level=6, policy="htslib", header_text=None, index=True, deflate=None):
     """references: [(name, length)]; records: coordinate-sorted dicts (encode_record), unmapped ones (tid -1) last.
-    Writes path (+ path.bai) and returns the virtual offset of every record."""
+    Writes path (+ path.bai) and returns the virtual offset of every record.  ``deflate``: raw DEFLATE of one block's bytes
+    (default: zlib at ``level``)."""
     if header_text is None:
         header_text = "@HD\tVN:1.6\tSO:coordinate\n" + "".join("@SQ\tSN:%s\tLN:%d\n" % r for r in references) + \
                       "@RG\tID:rg1\tSM:sampleA\n@RG\tID:rg2\tSM:sampleB\n@PG\tID:htslike\tPN:htslike\tVN:1\n"
@@ -130,7 +134,7 @@ def write_bam(path, references, records, level=6, policy="htslib", header_text=N
     coff, p, out = [], 0, []
     for b in blocks:
         coff.append(p)
-        z = _bgzf_block(b, level)
+        z = _bgzf_block(b, level, deflate)
         out.append(z)
         p += len(z)
     coff.append(p)                                              # where the EOF block starts

@@ -94,24 +94,59 @@ def _check(table, want, what):
     assert [table.names[i] for i in table.name_id] == want["qnames"], (what, "qname")
 
 
-CASES = [(1, "htslib"), (6, "htslib"), (9, "stream"), (6, "stream")]
+# (level, policy): zlib at that level; ("writer", policy): tests/deflate_writer.py's adversarial encoder (combined code-length
+# runs, single distance codes, stored blocks mixed in, DEFLATE blocks cut at odd token counts); ("libdeflate12", policy):
+# libdeflate at its highest level
+CASES = [(1, "htslib"), (6, "htslib"), (9, "stream"), (6, "stream"), ("writer", "stream"), ("libdeflate12", "htslib")]
+
+
+def _libdeflate12():
+    import ctypes
+    try:
+        ld = ctypes.CDLL("libdeflate.so.0")
+    except OSError:
+        return None
+    ld.libdeflate_alloc_compressor.restype = ctypes.c_void_p
+    ld.libdeflate_alloc_compressor.argtypes = [ctypes.c_int]
+    ld.libdeflate_deflate_compress.restype = ctypes.c_size_t
+    ld.libdeflate_deflate_compress.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t]
+    c = ld.libdeflate_alloc_compressor(12)
+
+    def deflate(data):
+        buf = ctypes.create_string_buffer(len(data) + 1024)
+        k = ld.libdeflate_deflate_compress(c, data, len(data), buf, len(buf))
+        assert k
+        return buf.raw[:k]
+    return deflate
 
 
 @pytest.fixture(scope="module")
 def files(tmp_path_factory):
+    from tests import deflate_writer
     d = tmp_path_factory.mktemp("htslike")
     recs = _records()
     out = {}
     for level, policy in CASES:
-        path = str(d / ("l%d_%s.bam" % (level, policy)))
-        out[(level, policy)] = (path, htslike.write_bam(path, REFS, recs, level=level, policy=policy))
+        path = str(d / ("l%s_%s.bam" % (level, policy)))
+        deflate = {"writer": deflate_writer.adversarial, "libdeflate12": _libdeflate12()}.get(level) if isinstance(level, str) else None
+        if isinstance(level, str) and deflate is None:
+            out[(level, policy)] = None                            # libdeflate.so.0 is not on the machine
+            continue
+        out[(level, policy)] = (path, htslike.write_bam(path, REFS, recs, level=6 if isinstance(level, str) else level, policy=policy,
+                                                        deflate=deflate))
     return recs, out
+
+
+def _case(out, case):
+    if out[case] is None:
+        pytest.skip("libdeflate.so.0 is not on this machine: the libdeflate level-12 file is not written")
+    return out[case]
 
 
 @pytest.mark.parametrize("case", CASES)
 def test_host_readers_on_a_foreign_bam(files, case):
     recs, out = files
-    path, voffs = out[case]
+    path, voffs = _case(out, case)
     head = bam.read_bam_header(path)
     assert head.references == [n for n, _l in REFS] and head.lengths == [l for _n, l in REFS]
     assert "SM:sampleB" in head.header_text and head.header_text.startswith("@HD")
@@ -143,7 +178,7 @@ def test_device_engine_on_a_foreign_bam(files, case):
     and the packed CIGARs it leaves in HBM are the same words."""
     import svision_amd.ingest_gpu as ig
     recs, out = files
-    path, _voffs = out[case]
+    path, _voffs = _case(out, case)
     head = bam.read_bam_header(path)
     saved = ig.FIRST_GROUP_BYTES, ig.PIPE_GROUP_BYTES
     try:
