@@ -293,7 +293,6 @@ class ChromosomeFeed:
                     sample.device_buffers = None
                 if dec is not None:
                     dec._mark("handed over %s [%s, %s) (scan + slot writes)" % (self.references[tid], lo, hi))
-                    dec.first_handover.set()                    # (the decoder holds its second launch back for this, ingest_gpu.py)
                 covered[tid] = hi
                 if last:
                     want.pop(0)

@@ -12,8 +12,25 @@ inflated data, a quarter of what the device pipeline consumes.  The same data in
 136 and 170 GB/s).
 Replaces pysam's AlignmentFile.fetch (run_collection.py:23-26) like the host reader (io.bam.BamStream), which stays the
 engine for files without a linear index, for --hash / --graph (read bases wanted) and for SVX_INGEST=cpu.
+
+Map of a run (DeviceDecoder.units_pipelined -> _Pipeline; the streams are those of svision_amd/streams.py):
+
+  planning   the caller's thread: plan_units / whole_units -> Units (file ranges), cut_groups -> the groups, one inflate
+             launch each.  No device work.
+  reader     thread "svx-read" (_Pipeline.reader, read_group): pread into the staging ring, BGZF block index, record starts
+             from the linear index; the compressed bytes go to the device on the "copy" stream.        -> Queue(maxsize=1)
+  driver     thread "svx-inflate-driver" (drive, pump, launch, finish_group): inflate, CRC32, walk-count, then per unit the
+             extraction and its read-back, on "ingest0" / "ingest1" in turn -- the tokens kernel of every group on "tokens"
+             --; the large buffers are allocated on the thread's default stream.  (Thread "svx-inflate-warm": the first two
+             groups' buffers, allocated and freed ahead of time.)                                      -> Queue(maxsize=8)
+  consumer   the caller's thread (_Pipeline.run): (unit, finish, device arrays); finish() is host work (QNAME ids, table); the
+             caller scans on a stream of its own, behind the unit's read-back event.
 """
+import collections
 import os
+import queue
+import threading
+import time
 
 import numpy as np
 import torch
@@ -22,39 +39,19 @@ from . import _lib, kernels, streams
 from .io.bam import AlignmentTable, read_bai_linear
 
 FIRST_GROUP_BYTES = 192 << 20            # the first launch is small (~7 k blocks: the wave-per-block kernel): the pipeline starts after ~0.1 s
-STAGE_BYTES = 64 << 20                   # a pinned staging slot of the pipelined reader (ring of eight)
+STAGE_BYTES = 64 << 20                   # a pinned staging slot of the reader (_StagingRing: eight of them)
 PIPE_GROUP_BYTES = 400 << 20             # the SECOND group: two slices (~14 k blocks) -- a ramp 192 / 400 / 600 MB.  Round 6, measured (profiles/r06_group_sweep.txt):
                                          # the five-window chr21 job (BASELINE configs[1]) is cut [1, 2, 2] instead of [1, 4] and takes 0.142 s instead of 0.172
                                          # (its second and third window no longer wait for the inflate of all four); 20 windows, cfg1, ONT: unchanged (+-1 %)
-                                         # parts_pipelined, the groups behind the first two: ~21 k blocks.  (Round 3 / early round 4: 768 MB, then 2.5 GB
+                                         # The groups behind the first two: ~21 k blocks.  (Round 3 / early round 4: 768 MB, then 2.5 GB
 LARGE_GROUP_BYTES = 600 << 20            # -- a launch of the lane-per-block kernel cost 60-90 ms whatever it held.  The two-kernel inflate is
 LARGE_GROUP_BLOCKS = 94_000              # proportional to the launch, and once the read-backs no longer blocked each other (launch(), streams.py)
                                          # a steady flow of small groups beat the large ones: the CNN behind never runs out of chromosomes.)
-GROUP_BYTES = 24 << 30                   # serial form (groups / decode_group): later groups as large as they come
+GROUP_BYTES = 24 << 30                   # read by no code of the package any more (the serial decoder it sized is gone): tests/test_gpu_inflate.py saves and restores it with the other sizes
 SLICE_BYTES = 256 << 20                  # a chromosome is handed over in slices of whole collection windows of about this many compressed bytes
 MIN_MARGIN = 128 << 10                   # reference bases a slice's records reach beyond its windows on either side, at least (plan_units)
 
-
-# The pinned staging slots outlive a decoder: a process that reads a second file (a service, a bench's warm-up pass) finds them
-# allocated -- hipHostMalloc costs ~0.1 s per GB and every other HIP call of the process waits for it.
-_STAGING = {"lock": None, "slots": [], "busy": False}
 _REACH_CACHE = {}                                             # (file identity) -> DeviceDecoder.estimate_reach: ~7 ms of zlib, once per file and process
-
-
-def _staging_ring():
-    """-> (slots, release): the process-wide ring of pinned slots if no other decoder holds it, else a private one."""
-    import threading
-    if _STAGING["lock"] is None:
-        _STAGING["lock"] = threading.Lock()
-    with _STAGING["lock"]:
-        if not _STAGING["busy"]:
-            _STAGING["busy"] = True
-
-            def release():
-                with _STAGING["lock"]:
-                    _STAGING["busy"] = False
-            return _STAGING["slots"], release
-    return [], (lambda: None)
 
 
 class DeviceIngestError(RuntimeError):
@@ -198,9 +195,62 @@ def cut_groups(tids, size_of, first_limits, limit, merge_last=True):
     return groups
 
 
+def _size_of(unit):
+    """Compressed bytes of a unit's file range, its last block included."""
+    return (unit.vhi >> 16) - (unit.vlo >> 16) + 65536
+
+
+_Blocks = collections.namedtuple("_Blocks", "k src_off src_len isize coff used")
+
+
+def _index_blocks(lib, ptr, nbytes, file_offset):
+    """svx_bgzf_index over the ``nbytes`` at host address ``ptr``, which lie at ``file_offset`` of the file -> _Blocks: ``k``
+    whole BGZF blocks (negative: no block starts at ``ptr``), per block its payload's offset from ``ptr``, the payload's
+    length, ISIZE and the block's file offset -- cut to ``k`` --, and ``used``: the bytes those blocks take."""
+    cap = nbytes // 28 + 16
+    src_off, coff = np.empty(cap, np.uint64), np.empty(cap, np.uint64)
+    src_len, isize = np.empty(cap, np.uint32), np.empty(cap, np.uint32)
+    used = np.zeros(1, np.uint64)
+    k = int(lib.svx_bgzf_index(ptr, nbytes, file_offset, cap, src_off.ctypes.data, src_len.ctypes.data, isize.ctypes.data, coff.ctypes.data,
+                               used.ctypes.data))
+    n = max(k, 0)
+    return _Blocks(k, src_off[:n], src_len[:n], isize[:n], coff[:n], int(used[0]))
+
+
+def _record_starts(coff, dst, lo, hi, linear):
+    """Where a walk of the records in the virtual-offset range [lo, hi) may start: ``lo``, the entries of the reference's
+    linear index inside the range and ``hi``, as ascending offsets into the inflated bytes of blocks that lie at the file
+    offsets ``coff`` and inflate to ``dst[i]`` .. ``dst[i + 1]`` (a virtual offset behind the last block: the end of the
+    data; two virtual offsets of one byte -- a block boundary -- are one start)."""
+    nb = int(coff.size)
+    seeds = linear[(linear >= np.uint64(lo)) & (linear < np.uint64(hi))]
+    voffs = np.unique(np.concatenate([np.asarray([lo], np.uint64), seeds, np.asarray([hi], np.uint64)]))
+    c = voffs >> np.uint64(16)
+    idx = np.searchsorted(coff, c)
+    at_end = idx >= nb
+    idx = np.minimum(idx, nb - 1)
+    if not (at_end | (coff[idx] == c)).all():
+        raise DeviceIngestError("the index points between two BGZF blocks")
+    return np.unique(np.where(at_end, dst[nb], dst[idx] + (voffs & np.uint64(0xFFFF))))
+
+
+def _pack_layout(n, name_bytes):
+    """-> (offs, size): the packed arrays of ``n`` records, everything the host wants of them, as sections of one buffer --
+    [cig_off n+1][name_off n+1][tid n][pos n][l_seq n][flag n][mapq n][names] (8, 8, 4, 4, 4, 2, 1, 1 bytes an element) --,
+    section k at ``offs[k]``, each padded to 16 bytes, 16 more at the end and ``size`` a multiple of 256."""
+    sect = [8 * (n + 1), 8 * (n + 1), 4 * n, 4 * n, 4 * n, 2 * n, n, name_bytes]
+    offs = np.zeros(len(sect) + 1, np.int64)
+    offs[1:] = np.cumsum([(v + 15) // 16 * 16 for v in sect])
+    return offs, (int(offs[-1]) + 16 + 255) // 256 * 256
+
+
+def _section(d_pack, offs, k, dtype, count):
+    """Section ``k`` of a device pack buffer (:func:`_pack_layout`) as ``count`` elements of the torch ``dtype``."""
+    return d_pack[int(offs[k]):int(offs[k]) + count * torch.empty(0, dtype=dtype).element_size()].view(dtype)
+
+
 class DeviceDecoder:
     def __init__(self, path, index, references, lengths, header_text, device, threads=8, alloc_for=None):
-        import time
         self._t0, self.trace = time.perf_counter(), []          # (seconds since construction, what) of the first events (SVX_TIMING)
         self.path, self.references, self.lengths, self.header_text = path, list(references), list(lengths), header_text
         self.device, self.threads = torch.device(device), max(1, int(threads))
@@ -208,40 +258,23 @@ class DeviceDecoder:
         self.lib = _lib.load()
         self.spans = read_bai_linear(index)
         self.size = os.path.getsize(path)
-        self.pinned = None
         self.stats = {"read_s": 0.0, "h2d_inflate_s": 0.0, "walk_s": 0.0, "d2h_s": 0.0, "names_s": 0.0, "blocks": 0, "bytes_in": 0, "bytes_inflated": 0}
         self._mark("index read")
-        import threading
-        self.first_handover = threading.Event()                 # set by the consumer once the first chromosome's scan is through
 
     def _mark(self, what):
-        import time
         if len(self.trace) < 400:
             self.trace.append((round(time.perf_counter() - self._t0, 4), what))
 
     def usable(self, tids):
         return all(t < len(self.spans) and (self.spans[t] is None or self.spans[t][2].size > 0) for t in tids)
 
-    def groups(self, tids):
-        """Chromosomes that have records, in file order, cut into runs of about FIRST_GROUP_BYTES / GROUP_BYTES compressed bytes."""
-        have = sorted((self.spans[t][0], t) for t in tids if t < len(self.spans) and self.spans[t] is not None)
-        out, cur, cur_bytes, limit = [], [], 0, FIRST_GROUP_BYTES
-        for _v, t in have:
-            lo, hi, _lin = self.spans[t]
-            nbytes = (hi >> 16) - (lo >> 16) + 65536
-            if cur and cur_bytes + nbytes > limit:
-                out.append(cur)
-                cur, cur_bytes, limit = [], 0, GROUP_BYTES
-            cur.append(t)
-            cur_bytes += nbytes
-        if cur:
-            out.append(cur)
-        return out
+    def _with_records(self, tids):
+        """The references of ``tids`` that have records, in file order."""
+        return [t for _v, t in sorted((self.spans[t][0], t) for t in tids if t < len(self.spans) and self.spans[t] is not None)]
 
     def whole_units(self, tids):
         """One unit per reference that has records, in file order: whole chromosomes."""
-        have = sorted((self.spans[t][0], t) for t in tids if t < len(self.spans) and self.spans[t] is not None)
-        return [Unit(t, 0, self.lengths[t] if t < len(self.lengths) else 1 << 62, self.spans[t][0], self.spans[t][1]) for _v, t in have]
+        return [Unit(t, 0, self.lengths[t] if t < len(self.lengths) else 1 << 62, self.spans[t][0], self.spans[t][1]) for t in self._with_records(tids)]
 
     def plan_units(self, tids, windows_of=None, margin=None, slice_bytes=None, resume=None, min_span_margins=None):
         """The references of ``tids`` that have records, in file order, each cut into slices of whole collection windows:
@@ -255,9 +288,8 @@ class DeviceDecoder:
         margin = int(margin if margin is not None else self.estimate_reach(tids))
         slice_bytes = int(slice_bytes or int(os.environ.get("SVX_SLICE_BYTES", "0")) or SLICE_BYTES)      # (the variable: experiments, tests)
         min_span = int(os.environ.get("SVX_SLICE_MIN_MARGINS", "13") if min_span_margins is None else min_span_margins) * margin
-        have = sorted((self.spans[t][0], t) for t in tids if t < len(self.spans) and self.spans[t] is not None)
         units, skipping = [], resume is not None
-        for _v, t in have:
+        for t in self._with_records(tids):
             span = self.spans[t]
             wins = windows_of(t) if windows_of is not None else None
             wins = sorted((int(a), int(b)) for a, b in wins) if wins else None        # (a reference the job names no window of: whole)
@@ -375,17 +407,8 @@ class DeviceDecoder:
         buf = np.empty(n, np.uint8)
         if self.lib.svx_read_range(self.path.encode(), start, n, buf.ctypes.data, 1) != 0:
             return 28_000.0
-        cap = n // 28 + 16
-        so, co = np.empty(cap, np.uint64), np.empty(cap, np.uint64)
-        sl, isz = np.empty(cap, np.uint32), np.empty(cap, np.uint32)
-        used = np.zeros(1, np.uint64)
-        k = int(self.lib.svx_bgzf_index(buf.ctypes.data, n, start, cap, so.ctypes.data, sl.ctypes.data, isz.ctypes.data, co.ctypes.data, used.ctypes.data))
-        return float(used[0]) / k if k > 0 else 28_000.0
-
-    def _pinned(self, n):
-        if self.pinned is None or self.pinned.numel() < n:
-            self.pinned = torch.empty(max(n, 64 << 20), dtype=torch.uint8, pin_memory=True)
-        return self.pinned
+        blocks = _index_blocks(self.lib, buf.ctypes.data, n, start)
+        return float(blocks.used) / blocks.k if blocks.k > 0 else 28_000.0
 
     # ---- pipelined form: a reader thread, up to `depth` groups in flight on streams of their own ------------------------
     def parts_pipelined(self, tids, depth=2):
@@ -397,437 +420,25 @@ class DeviceDecoder:
         """Generator over the units (:meth:`plan_units` / :meth:`whole_units`: whole chromosomes or slices of them, in file
         order): (unit, finish, (d_cigar int32, d_cig_off int64 [n+1], d_pos int32)) where ``finish()`` -> AlignmentTable on the
         host (the QNAME ids are computed there: host work the caller can overlap with the next unit's device work); (unit, None,
-        None) for a unit without a record.  The steps are overlapped: a reader thread fills the device buffers of the groups
-        ahead (through the staging ring); every group (cut_groups: ~600 MB of file) is inflated and counted without a host
-        synchronisation -- its tokens kernel on the process's "tokens" stream, one group after the other, the rest on one of
-        ``depth`` group streams (svision_amd/streams.py: hardware queues of their own) --; per group ONE read-back (block
-        status + walk counts: issued when the inflate is through, never queued behind it), per unit ONE (the packed arrays).
-        Consecutive slices of one chromosome overlap by their margins: inside a group the overlap is inflated once (the
-        group's bytes are one range of the file), across a group boundary twice (~2 % of a group)."""
-        import collections
-        import queue
-        import threading
-        import time
-        lib, dev = self.lib, self.device
-        units = list(units)
+        None) for a unit without a record.  The steps are overlapped (:class:`_Pipeline`): a reader thread fills the device
+        buffers of the groups ahead (through the staging ring); every group (cut_groups: ~600 MB of file) is inflated and
+        counted without a host synchronisation -- its tokens kernel on the process's "tokens" stream, one group after the
+        other, the rest on one of ``depth`` group streams (svision_amd/streams.py: hardware queues of their own) --; per group
+        ONE read-back (block status + walk counts: issued when the inflate is through, never queued behind it), per unit ONE
+        (the packed arrays).  Consecutive slices of one chromosome overlap by their margins: inside a group the overlap is
+        inflated once (the group's bytes are one range of the file), across a group boundary twice (~2 % of a group)."""
+        yield from _Pipeline(self, units, depth).run()
 
-        def size_of(u):
-            return (u.vhi >> 16) - (u.vlo >> 16) + 65536
-
-        def mb(name, default):                                 # (experiments: SVX_FIRST_GROUP_MB / SVX_PIPE_GROUP_MB / SVX_LARGE_GROUP_MB)
-            v = os.environ.get(name)
-            return int(v) << 20 if v else default
-        large = mb("SVX_LARGE_GROUP_MB", LARGE_GROUP_BYTES)
-        large = min(large, int(LARGE_GROUP_BLOCKS * self._block_bytes(units[0].tid))) if units else large
-        groups = cut_groups(units, size_of, [mb("SVX_FIRST_GROUP_MB", FIRST_GROUP_BYTES), mb("SVX_PIPE_GROUP_MB", PIPE_GROUP_BYTES)], large,
-                            merge_last=os.environ.get("SVX_MERGE_LAST", "1") != "0")
-        self._mark("groups cut: %s" % [len(g) for g in groups])
-        q = queue.Queue(maxsize=1)
-        stop = threading.Event()
-        # Staging: a ring of eight pinned 64 MB slots (four, until round 4: a slot's "copy done" event sits in a hardware queue its
-        # stream shares with long kernels and completes tens of ms after the copy itself -- with four slots the reader waited 0.15 s
-        # of a 0.5 s job for slots whose copies had long finished, with eight 0.02 s; a stream with a hardware queue of its own
-        # -- one of the low priority class, which nothing else of the process uses -- changed nothing).  A group's compressed bytes go to the device slot by slot -- read (8
-        # pread threads), index the BGZF blocks the slot holds, copy them to their place in the group's device buffer on a
-        # copy stream, reuse the slot once its copy is done.  (First version: one pinned buffer per group in flight --
-        # 3.7 GB of hipHostMalloc at 0.1 s per GB inside the run, during which every other HIP call of the process waited.)
-        ring, release_ring = _staging_ring()
-        ring[:] = [r for r in ring if r[0].numel() == STAGE_BYTES]
-        for r in ring:
-            r[1] = None
-        ring_at = [0]
-        # (low class: the copies run on the DMA engines, and nothing else of the process uses that class's hardware queues: streams.py)
-        copy_stream = streams.get("copy", dev)
-        n_slots = max(2, int(os.environ.get("SVX_STAGE_SLOTS", "8")))
-
-        def slot():
-            if ring_at[0] < n_slots and len(ring) < n_slots:
-                ring_at[0] += 1
-                ring.append([torch.empty(STAGE_BYTES, dtype=torch.uint8, pin_memory=True), None])
-                return ring[-1]
-            s_ = ring[ring_at[0] % len(ring)]
-            ring_at[0] += 1
-            if s_[1] is not None:
-                t_w = time.perf_counter()
-                s_[1].synchronize()
-                self.stats["slot_wait_s"] = self.stats.get("slot_wait_s", 0.0) + (time.perf_counter() - t_w)
-            return s_
-
-        def read_group(group):
-            spans = [(u.vlo, u.vhi, self.spans[u.tid][2]) for u in group]
-            tids_of = sorted({u.tid for u in group})
-            c0 = min(s[0] >> 16 for s in spans)
-            c1 = min(self.size, max(s[1] >> 16 for s in spans) + 65536 + 64)
-            nbytes = c1 - c0
-            t0 = time.perf_counter()
-            self._mark("read %s: start" % group[:2])
-            d_comp = torch.empty((nbytes + 31) // 16 * 16, dtype=torch.uint8, device=dev)
-            off, tables, copied = 0, [], None
-            while off < nbytes:
-                want = min(STAGE_BYTES, nbytes - off)
-                st_ = slot()
-                pin = st_[0]
-                t_p = time.perf_counter()
-                if lib.svx_read_range(self.path.encode(), c0 + off, want, pin.data_ptr(), self.threads) != 0:
-                    raise DeviceIngestError(lib.svx_bam_error().decode(), tids_of)
-                self.stats["pread_s"] = self.stats.get("pread_s", 0.0) + (time.perf_counter() - t_p)
-                cap = want // 28 + 16
-                so, co = np.empty(cap, np.uint64), np.empty(cap, np.uint64)
-                sl, isz = np.empty(cap, np.uint32), np.empty(cap, np.uint32)
-                used = np.zeros(1, np.uint64)
-                k = int(lib.svx_bgzf_index(pin.data_ptr(), want, c0 + off, cap, so.ctypes.data, sl.ctypes.data, isz.ctypes.data, co.ctypes.data,
-                                           used.ctypes.data))
-                if k < 0 or (k == 0 and off == 0):
-                    raise DeviceIngestError("no BGZF block at file offset %d" % (c0 + off), tids_of)
-                if k == 0:
-                    break                                      # what is left of the range is the head of a block that ends behind it
-                u = int(used[0])
-                with torch.cuda.stream(copy_stream):
-                    d_comp[off:off + u].copy_(pin[:u], non_blocking=True)
-                    copied = torch.cuda.Event()
-                    copied.record()
-                st_[1] = copied
-                tables.append((so[:k] + np.uint64(off), sl[:k], isz[:k], co[:k]))
-                off += u                                       # (a block cut by the end of the slot is read again, at the head of the next one)
-            d_comp.record_stream(copy_stream)
-            src_off, src_len, isize, coff = (np.concatenate([t[i] for t in tables]) for i in range(4))
-            nb = int(src_off.size)
-            dst = np.zeros(nb + 1, np.uint64)
-            dst[1:] = np.cumsum(isize.astype(np.uint64))
-
-            def inflated_offset(voffs):
-                c = voffs >> np.uint64(16)
-                idx = np.searchsorted(coff, c)
-                at_end = idx >= nb
-                idx = np.minimum(idx, nb - 1)
-                if not (at_end | (coff[idx] == c)).all():
-                    raise DeviceIngestError("the index points between two BGZF blocks")
-                return np.where(at_end, dst[nb], dst[idx] + (voffs & np.uint64(0xFFFF)))
-            starts = []
-            for u_, (lo, hi, linear) in zip(group, spans):
-                seeds = linear[(linear >= np.uint64(lo)) & (linear < np.uint64(hi))]
-                voffs = np.unique(np.concatenate([np.asarray([lo], np.uint64), seeds, np.asarray([hi], np.uint64)]))
-                try:
-                    starts.append(np.unique(inflated_offset(voffs)))
-                except DeviceIngestError as exc:
-                    raise DeviceIngestError(str(exc), [u_.tid]) from None
-            # one pinned block of small tables: payload offsets, payload sizes, inflated offsets, then every chromosome's starts
-            n_starts = [int(a.size) - 1 for a in starts]
-            words = 3 * nb + 1 + sum(a.size for a in starts) + 8
-            tab = torch.empty(words, dtype=torch.int64, pin_memory=True)
-            tv = tab.numpy()
-            tv[:nb] = src_off.view(np.int64)
-            tv[nb:2 * nb] = src_len.astype(np.int64)
-            tv[2 * nb:3 * nb + 1] = dst.view(np.int64)
-            at, start_at = 3 * nb + 1, []
-            for a in starts:
-                tv[at:at + a.size] = a.view(np.int64)
-                start_at.append(at)
-                at += a.size
-            self.stats["read_s"] += time.perf_counter() - t0
-            self.stats["blocks"] += nb
-            self.stats["bytes_in"] += int(nbytes)
-            self.stats["bytes_inflated"] += int(dst[nb])
-            self._mark("read: done, %d blocks" % nb)
-            return {"group": group, "d_comp": d_comp, "copied": copied, "nbytes": nbytes, "nb": nb, "total": int(dst[nb]), "tab": tab, "start_at": start_at,
-                    "n_starts": n_starts}
-
-        def reader():
-            def hand(item):                                     # stop-aware, the end marker and an exception included: an abandoned run
-                while not stop.is_set():                        # (a failed group, a plan that is cut again) leaves nobody to take them,
-                    try:                                        # and a reader blocked for ever keeps the process-wide staging ring busy
-                        q.put(item, timeout=0.2)
-                        return True
-                    except queue.Full:
-                        continue
-                return False
-            try:
-                for g in groups:
-                    if not hand(read_group(g)):
-                        return
-                hand(None)
-            except BaseException as exc:                         # noqa: BLE001
-                hand(exc)
-
-        def launch(item, stream):
-            nb = item["nb"]
-            self._mark("launch %s: start" % item["group"][:2])
-            # The group's large buffers -- the inflated bytes, the inflate's workspace -- are taken on THIS thread's (default)
-            # stream and handed to the group's stream with record_stream: the caching allocator keeps its free blocks per
-            # stream, so buffers allocated on the ingest streams (new ones every run) never met a cached block and were
-            # hipMalloc'ed fresh -- 0.2 ms per GB on most boxes, 15 ms per GB on some: a 0.24 s stall in front of the
-            # largest group's launch (two of nine bench runs).
-            variant = kernels.inflate_variant_for(nb)
-            d_raw = torch.empty(max(item["total"], 16), dtype=torch.uint8, device=dev)
-            d_ws = kernels.inflate_workspace(lib, variant, item["total"], nb, dev)
-            # (the allocator may hand out a block that default-stream work freed and is still using: the group's streams
-            # order themselves behind whatever the default stream holds at this point -- normally nothing)
-            allocated = torch.cuda.Event()
-            allocated.record(torch.cuda.default_stream(dev))
-            if tokens_stream is not None:
-                tokens_stream.wait_event(allocated)
-            with torch.cuda.stream(stream):
-                stream.wait_event(allocated)
-                stream.wait_event(item["copied"])              # the last slot of the group's compressed bytes is on the device
-                d_comp = item["d_comp"]
-                d_comp.record_stream(stream)
-                d_raw.record_stream(stream)
-                if d_ws is not None:
-                    d_ws.record_stream(stream)
-                d_tab = item["tab"].to(dev, non_blocking=True)
-                d_status = torch.zeros(nb, dtype=torch.int32, device=dev)
-                d_len = d_tab[nb:2 * nb].to(torch.int32)
-                st = kernels._stream_ptr(dev)
-                # every group's tokens kernel on ONE stream, in launch order (include/svx.h, svx_bgzf_inflate_fast_on): two of them
-                # side by side share the chip and finish together -- late; in a row, the first group's chromosomes are out a
-                # whole tokens launch earlier and its LZ copies (latency-bound) run next to the second group's tokens
-                if tokens_stream is not None and variant == "fast":
-                    for t_ in (d_comp, d_ws, d_tab, d_len, d_status):
-                        t_.record_stream(tokens_stream)
-                kernels.launch_inflate(lib, variant, d_comp.data_ptr(), d_tab.data_ptr(), d_len.data_ptr(), d_tab[2 * nb:].data_ptr(), nb,
-                                       d_raw.data_ptr(), d_status.data_ptr(), item["total"], dev, ws=d_ws,
-                                       tokens_stream=tokens_stream if variant == "fast" else None)
-                if kernels.bgzf_crc_wanted():                  # the footers' CRC32 (htslib checks it on every block): status 9 where one differs
-                    _lib.check(lib.svx_bgzf_crc32(d_raw.data_ptr(), d_tab[2 * nb:].data_ptr(), d_comp.data_ptr(), d_tab.data_ptr(), d_len.data_ptr(), nb,
-                                                  d_status.data_ptr(), st), "svx_bgzf_crc32")
-                total_starts = sum(item["n_starts"])
-                d_counts = torch.empty((total_starts + 1, 4), dtype=torch.int64, device=dev)
-                row = 0
-                for at, n in zip(item["start_at"], item["n_starts"]):
-                    _lib.check(lib.svx_bam_walk_count(d_raw.data_ptr(), d_tab[at:].data_ptr(), n, d_counts[row:].data_ptr(), st), "svx_bam_walk_count")
-                    row += n
-                d_counts[total_starts, 0] = d_status.max()
-                # NO read-back is enqueued here.  A device-to-host copy goes to a DMA engine's queue at once, with a wait for
-                # the kernels in front of it -- and the engine serves its queue in order: the counts' copy sat there for the
-                # whole inflate (40-120 ms) and every other read-back of the process (the previous group's packed arrays,
-                # the scans' results, the CNN's predictions) waited behind it.  finish_group() copies once the event is through.
-                ev = torch.cuda.Event()
-                ev.record()
-            item.update(d_raw=d_raw, d_tab=d_tab, d_counts=d_counts, event=ev, stream=stream)
-            self._mark("launched %s" % item["group"][:2])
-            return item
-
-        def finish_group(item):
-            t0 = time.perf_counter()
-            item["event"].synchronize()
-            self._mark("inflate + count done %s" % item["group"][:2])
-            item["d_comp"] = None
-            self.stats["h2d_inflate_s"] += time.perf_counter() - t0
-            d_counts = item.pop("d_counts")
-            h_counts = torch.empty(tuple(d_counts.shape), dtype=torch.int64, pin_memory=True)
-            with torch.cuda.stream(item["stream"]):
-                h_counts.copy_(d_counts, non_blocking=True)
-                ev_c = torch.cuda.Event()
-                ev_c.record()
-            ev_c.synchronize()
-            counts = h_counts.numpy()
-            if int(counts[-1, 0]) != 0:
-                raise DeviceIngestError("corrupt BGZF blocks in %s" % item["group"], sorted({u.tid for u in item["group"]}))
-            d_raw, d_tab, stream = item["d_raw"], item["d_tab"], item["stream"]
-            pending, row = [], 0
-            t0 = time.perf_counter()
-            # Sizes first, then ONE device buffer and ONE pinned buffer per group for the packed arrays of all its chromosomes
-            # (and one device buffer for their CIGAR words): every first-time hipMalloc / hipHostMalloc of a run costs
-            # milliseconds during which the other threads' HIP calls -- and their page faults -- wait; per chromosome that
-            # was six of them.
-            plan, pack_at, word_at = [], 0, 0
-            for unit_, at, n_starts in zip(item["group"], item["start_at"], item["n_starts"]):
-                c = counts[row:row + n_starts]
-                bad = c[:, 3] != 0
-                if bad.any():
-                    code = int(c[bad, 3][0])
-                    raise DeviceIngestError({1: "the linear index does not match the records", 2: "malformed BAM record"}.get(code, "walk error %d" % code), [unit_.tid])
-                n, words, name_bytes = (int(v) for v in c[:, :3].sum(axis=0)) if n_starts else (0, 0, 0)
-                # [cig_off n+1][name_off n+1][tid n][pos n][l_seq n][flag n][mapq n][names]: everything the host wants
-                sect = [8 * (n + 1), 8 * (n + 1), 4 * n, 4 * n, 4 * n, 2 * n, n, name_bytes]
-                offs = np.zeros(len(sect) + 1, np.int64)
-                offs[1:] = np.cumsum([(v + 15) // 16 * 16 for v in sect])
-                size = (int(offs[-1]) + 16 + 255) // 256 * 256
-                plan.append((at, n_starts, row, n, words, name_bytes, offs, pack_at, size, word_at, unit_))
-                pack_at += size
-                word_at += (max(words, 1) + 63) // 64 * 64       # (svx_cigar_scan reads 16-byte quads: every chromosome starts aligned)
-                row += n_starts
-            base_all = torch.zeros((max(row, 1), 3), dtype=torch.int64, pin_memory=True)
-            for at, n_starts, r0, *_rest in plan:
-                if n_starts > 1:
-                    base_all.numpy()[r0 + 1:r0 + n_starts] = np.cumsum(counts[r0:r0 + n_starts - 1, :3], axis=0)
-            d_pack_all = torch.empty(max(pack_at, 256), dtype=torch.uint8, device=dev)        # (default stream: see launch())
-            d_cigar_all = torch.empty(max(word_at, 64), dtype=torch.int32, device=dev)
-            allocated = torch.cuda.Event()
-            allocated.record(torch.cuda.default_stream(dev))
-            with torch.cuda.stream(stream):
-                stream.wait_event(allocated)
-                st = kernels._stream_ptr(dev)
-                d_pack_all.record_stream(stream)
-                d_cigar_all.record_stream(stream)
-                d_base_all = base_all.to(dev, non_blocking=True)
-                h_pack_all = torch.empty(max(pack_at, 256), dtype=torch.uint8, pin_memory=True)
-                for at, n_starts, r0, n, words, name_bytes, offs, p0, size, w0, unit_ in plan:
-                    if n == 0:                                   # a slice (or a reference) without a record: nothing to extract
-                        pending.append((None, None, offs, 0, 0, 0, None, None, None, base_all, None, unit_))
-                        continue
-                    d_pack = d_pack_all[p0:p0 + size]
-                    d_base = d_base_all[r0:r0 + n_starts]
-
-                    def view(k, dtype, count, d_pack=d_pack, offs=offs):
-                        return d_pack[int(offs[k]):int(offs[k]) + count * torch.empty(0, dtype=dtype).element_size()].view(dtype)
-                    d_cig_off, d_name_off = view(0, torch.int64, n + 1), view(1, torch.int64, n + 1)
-                    d_tid, d_pos, d_lseq = view(2, torch.int32, n), view(3, torch.int32, n), view(4, torch.int32, n)
-                    d_flag, d_mapq, d_names = view(5, torch.int16, n), view(6, torch.uint8, n), view(7, torch.uint8, max(name_bytes, 1))
-                    d_cigar = d_cigar_all[w0:w0 + max(words, 1)]
-                    _lib.check(lib.svx_bam_walk_extract(d_raw.data_ptr(), d_tab[at:].data_ptr(), n_starts, d_base.data_ptr(), d_tid.data_ptr(),
-                                                        d_pos.data_ptr(), d_flag.data_ptr(), d_mapq.data_ptr(), d_lseq.data_ptr(), d_cig_off.data_ptr(),
-                                                        d_cigar.data_ptr(), d_name_off.data_ptr(), d_names.data_ptr(), n, st), "svx_bam_walk_extract")
-                    h_pack = h_pack_all[p0:p0 + size]
-                    h_pack.copy_(d_pack, non_blocking=True)
-                    # svx_cigar_scan reads the offsets and positions where they are: views of the group's pack buffer, which
-                    # lives as long as one of them does (until round 4: two clones and two fills of the CSR arrays' closing
-                    # entries per chromosome -- four tiny launches, each a few hundred microseconds of waiting for room on a
-                    # chip that is full of inflate and CNN waves; the extract kernel writes the closing entries itself now).
-                    # The consumer scans on another stream and orders itself behind this one through the event only.
-                    ev = torch.cuda.Event()
-                    ev.record()
-                    pending.append((ev, h_pack, offs, n, words, name_bytes, d_cigar, d_cig_off, d_pos, base_all, d_pack, unit_))
-            self.stats["walk_s"] += time.perf_counter() - t0
-            yield None                                          # every chromosome's extraction is enqueued: the caller may launch the next group
-            for ev, h_pack, offs, n, words, name_bytes, d_cigar, d_cig_off, d_pos, _base, _d_pack, unit_ in pending:
-                if ev is None:
-                    yield unit_, None, None
-                    continue
-                t0 = time.perf_counter()
-                ev.synchronize()
-                self.stats["d2h_s"] += time.perf_counter() - t0
-                self._mark("packed read-back done")
-                yield unit_, self._make_finish(h_pack.numpy(), offs, n, words, name_bytes, d_cigar), (d_cigar, d_cig_off, d_pos)
-            item["d_raw"] = item["d_tab"] = None
-
-        th = threading.Thread(target=reader, name="svx-read", daemon=True)
-        th.start()
-        # high priority: the ingest kernels and the CNN share the device and do not overlap; whatever the order, the device
-        # does the same work, but chromosomes that arrive early give the pipeline behind a backlog (and the per-chromosome
-        # kernels here are small: behind queued graph replays they would wait for tens of ms)
-        depth = int(os.environ.get("SVX_INGEST_DEPTH", depth))          # (experiments)
-        depth = max(1, min(depth, 2))                              # (the high class has four hardware queues: tokens, two groups, scans)
-        tokens_stream = streams.get("tokens", dev) if os.environ.get("SVX_TOKENS_STREAM", "1") != "0" else None
-        group_streams = [streams.get("ingest%d" % i, dev) for i in range(depth)]
-        inflight = collections.deque()
-        state = {"done": False, "k": 0, "finished": 0, "hold_until": float("inf")}
-        # (SVX_FIRST_HOLD=1: the round-3 rule -- nothing is launched behind the first group until its chromosome is through.
-        # It protected that chromosome's small kernels from waiting behind the second group's inflate in a shared hardware
-        # queue; with queues of their own (streams.py) it only kept the second group's tokens kernel out of the start-up, when
-        # the device has nothing else to do: without it the second group's chromosomes arrive 20-30 ms earlier, 0.41 -> 0.40 s.)
-        hold_first = os.environ.get("SVX_FIRST_HOLD", "0") == "1"
-
-        def pump(block):
-            """Launch what the reader has ready, up to `depth` groups in flight; block only when nothing is in flight."""
-            while not state["done"] and len(inflight) < depth:
-                # Nothing is launched behind the very first group until its chromosome is through (extracted here, scanned by the
-                # consumer; at most 0.15 s): kernels do not pre-empt each other, these steps are a few small kernels, and behind the
-                # second group's inflate launch they would wait 60-90 ms -- while the pipeline waits for exactly that chromosome.
-                if hold_first and state["k"] == 1 and not (state["finished"] and self.first_handover.is_set()) and time.perf_counter() < state["hold_until"]:
-                    if inflight or not block:
-                        return                                  # (the caller goes on to finish the group in flight)
-                    time.sleep(0.0005)
-                    continue
-                try:
-                    item = q.get(block=block and not inflight, timeout=None)
-                except queue.Empty:
-                    return
-                if item is None:
-                    state["done"] = True
-                    return
-                if isinstance(item, BaseException):
-                    # a LATER group failed in the reader: the groups in flight in front of it are healthy -- they are finished and
-                    # their chromosomes yielded first (drive() raises this once nothing is in flight any more), so that the
-                    # consumer's count of finished chromosomes points at the failing group and nothing decoded is thrown away
-                    state["error"], state["done"] = item, True
-                    return
-                inflight.append(launch(item, group_streams[state["k"] % depth]))
-                state["k"] += 1
-                if state["k"] == 1:
-                    state["hold_until"] = time.perf_counter() + 0.15
-
-        # The launches are driven from a thread of their own: the consumer of this generator does host work per chromosome
-        # (QNAME ids, shared-memory copies, the upload for the scan: 3-80 ms) and a generator that launches only between two
-        # of its yields left the device without inflate work for as long.
-        out_q = queue.Queue(maxsize=8)
-
-        def put(x):
-            while not stop.is_set():
-                try:
-                    out_q.put(x, timeout=0.2)
-                    return True
-                except queue.Full:
-                    continue
-            return False
-
-        def drive():
-            try:
-                while not stop.is_set():
-                    pump(block=True)
-                    if not inflight:
-                        if state.get("error") is not None:
-                            raise state["error"]
-                        break
-                    head = inflight[0]
-                    while not head["event"].query():           # keep launching while the oldest group is still on the device ...
-                        pump(block=False)
-                        time.sleep(0.0005)
-                    inflight.popleft()
-                    for part in finish_group(head):
-                        if part is None:
-                            state["finished"] += 1              # (its extraction is enqueued: what is launched now runs behind it)
-                        elif not put(part):
-                            return
-                        pump(block=False)                       # (a group of a dozen chromosomes takes tens of ms to finish)
-                    self._mark("group %s finished" % head["group"][:2])
-                put(None)
-            except BaseException as exc:                         # noqa: BLE001 -- re-raised in the consumer's thread
-                put(exc)
-
-        def warm():
-            """The device buffers of the first two groups, allocated while the first read is still on its way (the caching allocator
-            hands them out again): their hipMalloc calls would sit on the path to the first chromosome.  Only those: on some
-            boxes a first hipMalloc costs 15 ms per GB instead of 0.2 -- 0.3 s for the 22 GB of all groups, during which no
-            other HIP call of the process returns -- and the large groups' buffers are better allocated when their turn comes,
-            next to device work that is already queued."""
-            for g in groups[:2]:                               # in the order they will be asked for: compressed bytes, inflated bytes
-                nbytes = sum(size_of(u) for u in g)
-                if stop.is_set():
-                    break
-                for n in (nbytes + (1 << 20), 3 * nbytes + (1 << 20)):
-                    torch.empty(n, dtype=torch.uint8, device=dev)      # allocated and released at once: the block stays in the allocator's cache
-            self._mark("warm: done")
-
-        threading.Thread(target=warm, name="svx-inflate-warm", daemon=True).start()
-        driver = threading.Thread(target=drive, name="svx-inflate-driver", daemon=True)
-        driver.start()
-        try:
-            while True:
-                part = out_q.get()
-                if part is None:
-                    break
-                if isinstance(part, BaseException):
-                    raise part
-                yield part
-        finally:
-            stop.set()
-            try:
-                th.join(timeout=10)                            # (an abandoned run: the reader may be in the middle of a group)
-                copy_stream.synchronize()                      # the slots go back to the process-wide ring: no copy may still read them
-            finally:
-                if not th.is_alive():
-                    release_ring()
-
-    def _make_finish(self, hp, offs, n, words, name_bytes, d_cigar):
-        """The host side of one device-decoded chromosome: packed read-back -> shared-memory arrays, QNAME ids, table."""
+    def _make_finish(self, hp, n, words, name_bytes, d_cigar):
+        """The host side of one device-decoded chromosome: packed read-back ``hp`` (:func:`_pack_layout`) -> shared-memory
+        arrays, QNAME ids, table."""
         lib = self.lib
+        offs, _size = _pack_layout(n, name_bytes)
 
         def sect(k, dtype, count):
             return hp[int(offs[k]):int(offs[k]) + count * np.dtype(dtype).itemsize].view(dtype)
 
         def finish():
-            import time
             t0 = time.perf_counter()
             alloc = self.alloc_for() if self.alloc_for is not None else (lambda _name, dtype, k: np.empty(k, dtype))
 
@@ -874,135 +485,457 @@ class DeviceDecoder:
             return table
         return finish
 
-    def decode_group(self, tids):
-        """Generator over the chromosomes of one group: (finish, (d_cigar int32, d_cig_off int64 [n+1], d_pos int32)) where
-        ``finish()`` -> AlignmentTable on the host (the QNAME ids are computed there: host work the caller can overlap
-        with the next chromosome's device work).  The group's blocks are inflated in ONE launch before the first yield."""
-        import time
-        lib, dev = self.lib, self.device
-        spans = [self.spans[t] for t in tids]
-        c0 = min(s[0] >> 16 for s in spans)
-        c1 = min(self.size, max(s[1] >> 16 for s in spans) + 65536 + 64)
+
+class _Group:
+    """One inflate launch: the units whose blocks it holds (one range of the file).  Filled by :meth:`_Pipeline.read_group`
+    (reader thread), completed by :meth:`_Pipeline.launch` (driver thread: ``d_raw`` and everything behind it); the device
+    buffers are dropped as soon as the last step that reads them is through."""
+    __slots__ = ("units", "d_comp", "copied", "nbytes", "n_blocks", "inflated_bytes", "tab", "start_at", "n_starts",
+                 "d_raw", "d_tab", "d_counts", "event", "stream")
+
+    def __init__(self, units, d_comp, copied, nbytes, n_blocks, inflated_bytes, tab, start_at, n_starts):
+        self.units, self.d_comp, self.copied, self.nbytes, self.n_blocks, self.inflated_bytes = units, d_comp, copied, nbytes, n_blocks, inflated_bytes
+        self.tab, self.start_at, self.n_starts = tab, start_at, n_starts      # pinned: block tables + every unit's record starts; where each unit's starts begin; how many
+        self.d_raw = self.d_tab = self.d_counts = self.event = self.stream = None
+
+
+class _Packed:
+    """One unit's share of its group's pack buffers (:meth:`_Pipeline.finish_group`): where its record starts and walk counts
+    are (``at`` in the group's table, ``n_starts`` rows from ``row``), what the walk counted (``n`` records, ``words`` CIGAR
+    words, ``name_bytes``), its place in the buffers (``pack_at`` + ``size`` bytes laid out by ``offs``, ``word_at``) and, once
+    its extraction is enqueued, what the consumer gets (``event``, ``h_pack``, ``d_cigar``, ``d_cig_off``, ``d_pos``)."""
+    __slots__ = ("unit", "at", "n_starts", "row", "n", "words", "name_bytes", "offs", "pack_at", "size", "word_at",
+                 "event", "h_pack", "d_cigar", "d_cig_off", "d_pos")
+
+    def __init__(self, unit, at, n_starts, row, n, words, name_bytes, pack_at, word_at):
+        self.unit, self.at, self.n_starts, self.row, self.n, self.words, self.name_bytes = unit, at, n_starts, row, n, words, name_bytes
+        self.offs, self.size = _pack_layout(n, name_bytes)
+        self.pack_at, self.word_at = pack_at, word_at
+        self.event = self.h_pack = self.d_cigar = self.d_cig_off = self.d_pos = None
+
+
+class _StagingRing:
+    """The ring of pinned 64 MB slots a group's compressed bytes go to the device through -- read (8 pread threads), index the
+    BGZF blocks the slot holds, copy them to their place in the group's device buffer on the copy stream, reuse the slot once
+    its copy is done.  Eight slots (four, until round 4: a slot's "copy done" event sits in a hardware queue its stream shares
+    with long kernels and completes tens of ms after the copy itself -- with four slots the reader waited 0.15 s of a 0.5 s job
+    for slots whose copies had long finished, with eight 0.02 s; a stream with a hardware queue of its own -- one of the low
+    priority class, which nothing else of the process uses -- changed nothing).  (First version: one pinned buffer per group in
+    flight -- 3.7 GB of hipHostMalloc at 0.1 s per GB inside the run, during which every other HIP call of the process waited.)
+
+    The slots outlive a decoder: a process that reads a second file (a service, a bench's warm-up pass) finds them allocated
+    -- hipHostMalloc costs ~0.1 s per GB and every other HIP call of the process waits for it.  One decoder at a time owns the
+    process-wide slots; another one running beside it gets a private ring."""
+    _lock, _shared, _busy = threading.Lock(), [], False
+
+    def __init__(self, stats):
+        cls = _StagingRing
+        with cls._lock:
+            self.shared = not cls._busy
+            if self.shared:
+                cls._busy = True
+        self.slots = cls._shared if self.shared else []        # [pinned tensor, "copy done" event of its last use or None]
+        self.slots[:] = [s for s in self.slots if s[0].numel() == STAGE_BYTES]
+        for s in self.slots:
+            s[1] = None
+        self.at, self.stats = 0, stats
+        self.n_slots = max(2, int(os.environ.get("SVX_STAGE_SLOTS", "8")))
+
+    def slot(self):
+        """Reader thread -> the next slot, its previous copy complete (the wait is counted in stats["slot_wait_s"])."""
+        if self.at < self.n_slots and len(self.slots) < self.n_slots:
+            self.at += 1
+            self.slots.append([torch.empty(STAGE_BYTES, dtype=torch.uint8, pin_memory=True), None])
+            return self.slots[-1]
+        s = self.slots[self.at % len(self.slots)]
+        self.at += 1
+        if s[1] is not None:
+            t_w = time.perf_counter()
+            s[1].synchronize()
+            self.stats["slot_wait_s"] = self.stats.get("slot_wait_s", 0.0) + (time.perf_counter() - t_w)
+        return s
+
+    def release(self):
+        """The process-wide slots are free for the next decoder (only once no thread of this one can touch them)."""
+        if self.shared:
+            with _StagingRing._lock:
+                _StagingRing._busy = False
+
+
+class _Pipeline:
+    """One run of :meth:`DeviceDecoder.units_pipelined`: four threads, each stage a method.
+
+        reader thread "svx-read"            reader -> read_group                 "copy" stream          -> Queue(maxsize=1)
+        driver thread "svx-inflate-driver"  drive -> pump -> launch,             "ingest0" / "ingest1"  -> Queue(maxsize=8)
+                                            drive -> finish_group                (+ "tokens", default)
+        warm thread "svx-inflate-warm"      warm                                 default stream
+        consumer (the caller's thread)      run
+
+    The groups (module constants and SVX_*_GROUP_MB are read here, at call time) are cut before anything starts."""
+
+    def __init__(self, dec, units, depth):
+        self.dec, self.lib, self.dev, self.stats, self.mark = dec, dec.lib, dec.device, dec.stats, dec._mark
+        units = list(units)
+
+        def mb(name, default):                                 # (experiments: SVX_FIRST_GROUP_MB / SVX_PIPE_GROUP_MB / SVX_LARGE_GROUP_MB)
+            v = os.environ.get(name)
+            return int(v) << 20 if v else default
+        large = mb("SVX_LARGE_GROUP_MB", LARGE_GROUP_BYTES)
+        large = min(large, int(LARGE_GROUP_BLOCKS * dec._block_bytes(units[0].tid))) if units else large
+        self.groups = cut_groups(units, _size_of, [mb("SVX_FIRST_GROUP_MB", FIRST_GROUP_BYTES), mb("SVX_PIPE_GROUP_MB", PIPE_GROUP_BYTES)], large,
+                                 merge_last=os.environ.get("SVX_MERGE_LAST", "1") != "0")
+        self.mark("groups cut: %s" % [len(g) for g in self.groups])
+        self.read_q = queue.Queue(maxsize=1)                   # reader -> driver: _Group | None (the end) | an exception
+        # The launches are driven from a thread of their own: the consumer of this generator does host work per chromosome
+        # (QNAME ids, shared-memory copies, the upload for the scan: 3-80 ms) and a generator that launches only between two
+        # of its yields left the device without inflate work for as long.
+        self.out_q = queue.Queue(maxsize=8)                    # driver -> consumer: what run() yields | None | an exception
+        self.stop = threading.Event()
+        # (low class: the copies run on the DMA engines, and nothing else of the process uses that class's hardware queues: streams.py)
+        self.copy_stream = streams.get("copy", self.dev)
+        # high priority: the ingest kernels and the CNN share the device and do not overlap; whatever the order, the device
+        # does the same work, but chromosomes that arrive early give the pipeline behind a backlog (and the per-chromosome
+        # kernels here are small: behind queued graph replays they would wait for tens of ms)
+        depth = int(os.environ.get("SVX_INGEST_DEPTH", depth))          # (experiments)
+        self.depth = max(1, min(depth, 2))                         # (the high class has four hardware queues: tokens, two groups, scans)
+        self.tokens_stream = streams.get("tokens", self.dev) if os.environ.get("SVX_TOKENS_STREAM", "1") != "0" else None
+        self.group_streams = [streams.get("ingest%d" % i, self.dev) for i in range(self.depth)]
+        self.inflight = collections.deque()                    # driver thread only: the groups launched and not yet finished
+        self.done, self.error, self.launched = False, None, 0  # driver thread only: the reader has ended / what it ended with / groups launched
+        self.ring = _StagingRing(self.stats)                   # (last: from here on run()'s finally gives the shared slots back)
+
+    # ---- reader thread ------------------------------------------------------------------------------------------------
+    def reader(self):
+        """Reader thread ("svx-read"): every group through :meth:`read_group`, then the end marker -- or the exception that
+        ended it -- into ``read_q``.  Device work: the staging copies of read_group, on the "copy" stream."""
+        def hand(item):                                         # stop-aware, the end marker and an exception included: an abandoned run
+            while not self.stop.is_set():                       # (a failed group, a plan that is cut again) leaves nobody to take them,
+                try:                                            # and a reader blocked for ever keeps the process-wide staging ring busy
+                    self.read_q.put(item, timeout=0.2)
+                    return True
+                except queue.Full:
+                    continue
+            return False
+        try:
+            for g in self.groups:
+                if not hand(self.read_group(g)):
+                    return
+            hand(None)
+        except BaseException as exc:                             # noqa: BLE001
+            hand(exc)
+
+    def read_group(self, units):
+        """Reader thread: the file range of ``units`` -> a :class:`_Group` whose compressed bytes are on their way to the
+        device.  Allocates ``d_comp`` on this thread's default stream; the copies out of the staging slots go to the "copy"
+        stream (``copied``: the event behind the last one).  The host work: pread, BGZF block index, record starts."""
+        dec, lib = self.dec, self.lib
+        tids_of = sorted({u.tid for u in units})
+        c0 = min(u.vlo >> 16 for u in units)
+        c1 = min(dec.size, max(u.vhi >> 16 for u in units) + 65536 + 64)
         nbytes = c1 - c0
         t0 = time.perf_counter()
-        pin = self._pinned(nbytes + 64)
-        if lib.svx_read_range(self.path.encode(), c0, nbytes, pin.data_ptr(), self.threads) != 0:
-            raise DeviceIngestError(lib.svx_bam_error().decode())
-        pin[nbytes:nbytes + 64].zero_()
-        cap = nbytes // 28 + 16
-        src_off, coff = np.empty(cap, np.uint64), np.empty(cap, np.uint64)
-        src_len, isize = np.empty(cap, np.uint32), np.empty(cap, np.uint32)
-        used = np.zeros(1, np.uint64)
-        nb = int(lib.svx_bgzf_index(pin.data_ptr(), nbytes, c0, cap, src_off.ctypes.data, src_len.ctypes.data, isize.ctypes.data,
-                                    coff.ctypes.data, used.ctypes.data))
-        if nb <= 0:
-            raise DeviceIngestError("no BGZF block at file offset %d" % c0)
-        src_off, src_len, isize, coff = src_off[:nb], src_len[:nb], isize[:nb], coff[:nb]
-        t1 = time.perf_counter()
-        self.stats["read_s"] += t1 - t0
-        padded = (nbytes + 31) // 16 * 16
-        d_comp = torch.empty(padded, dtype=torch.uint8, device=dev)
-        d_comp.copy_(pin[:padded], non_blocking=True)
-        d_raw, d_status = kernels.bgzf_inflate(d_comp, src_off, src_len, isize)
-        if int(d_status.max().item()) != 0:
-            raise DeviceIngestError("%d corrupt BGZF blocks" % int(d_status.ne(0).sum().item()))
-        del d_comp
-        t2 = time.perf_counter()
-        self.stats["h2d_inflate_s"] += t2 - t1
-        self.stats["blocks"] += nb
-        self.stats["bytes_in"] += int(nbytes)
-        self.stats["bytes_inflated"] += int(d_raw.numel())
+        self.mark("read %s: start" % units[:2])
+        d_comp = torch.empty((nbytes + 31) // 16 * 16, dtype=torch.uint8, device=self.dev)
+        off, tables, copied = 0, [], None
+        while off < nbytes:
+            want = min(STAGE_BYTES, nbytes - off)
+            slot = self.ring.slot()
+            pin = slot[0]
+            t_p = time.perf_counter()
+            if lib.svx_read_range(dec.path.encode(), c0 + off, want, pin.data_ptr(), dec.threads) != 0:
+                raise DeviceIngestError(lib.svx_bam_error().decode(), tids_of)
+            self.stats["pread_s"] = self.stats.get("pread_s", 0.0) + (time.perf_counter() - t_p)
+            blocks = _index_blocks(lib, pin.data_ptr(), want, c0 + off)
+            if blocks.k < 0 or (blocks.k == 0 and off == 0):
+                raise DeviceIngestError("no BGZF block at file offset %d" % (c0 + off), tids_of)
+            if blocks.k == 0:
+                break                                          # what is left of the range is the head of a block that ends behind it
+            with torch.cuda.stream(self.copy_stream):
+                d_comp[off:off + blocks.used].copy_(pin[:blocks.used], non_blocking=True)
+                copied = torch.cuda.Event()
+                copied.record()
+            slot[1] = copied
+            tables.append((blocks.src_off + np.uint64(off), blocks.src_len, blocks.isize, blocks.coff))
+            off += blocks.used                                 # (a block cut by the end of the slot is read again, at the head of the next one)
+        d_comp.record_stream(self.copy_stream)
+        src_off, src_len, isize, coff = (np.concatenate([t[i] for t in tables]) for i in range(4))
+        nb = int(src_off.size)
         dst = np.zeros(nb + 1, np.uint64)
         dst[1:] = np.cumsum(isize.astype(np.uint64))
+        starts = []
+        for u in units:
+            try:
+                starts.append(_record_starts(coff, dst, u.vlo, u.vhi, dec.spans[u.tid][2]))
+            except DeviceIngestError as exc:
+                raise DeviceIngestError(str(exc), [u.tid]) from None
+        # one pinned block of small tables: payload offsets, payload sizes, inflated offsets, then every chromosome's starts
+        n_starts = [int(a.size) - 1 for a in starts]
+        words = 3 * nb + 1 + sum(a.size for a in starts) + 8
+        tab = torch.empty(words, dtype=torch.int64, pin_memory=True)
+        tv = tab.numpy()
+        tv[:nb] = src_off.view(np.int64)
+        tv[nb:2 * nb] = src_len.astype(np.int64)
+        tv[2 * nb:3 * nb + 1] = dst.view(np.int64)
+        at, start_at = 3 * nb + 1, []
+        for a in starts:
+            tv[at:at + a.size] = a.view(np.int64)
+            start_at.append(at)
+            at += a.size
+        self.stats["read_s"] += time.perf_counter() - t0
+        self.stats["blocks"] += nb
+        self.stats["bytes_in"] += int(nbytes)
+        self.stats["bytes_inflated"] += int(dst[nb])
+        self.mark("read: done, %d blocks" % nb)
+        return _Group(units, d_comp, copied, nbytes, nb, int(dst[nb]), tab, start_at, n_starts)
 
-        def inflated_offset(voffs):
-            c = voffs >> np.uint64(16)
-            idx = np.searchsorted(coff, c)
-            at_end = idx >= nb                                   # the virtual offset of the end of the data: behind the last block
-            idx = np.minimum(idx, nb - 1)
-            ok = at_end | (coff[idx] == c)
-            if not ok.all():
-                raise DeviceIngestError("the index points between two BGZF blocks")
-            return np.where(at_end, dst[nb], dst[idx] + (voffs & np.uint64(0xFFFF)))
+    # ---- driver thread ------------------------------------------------------------------------------------------------
+    def launch(self, g, stream):
+        """Driver thread: inflate + CRC + walk-count of group ``g``, enqueued without a host synchronisation.  ``d_raw`` and the
+        inflate's workspace are allocated on this thread's DEFAULT stream and handed over with record_stream; the tokens
+        kernel of the "fast" variant goes to the "tokens" stream, everything else to ``stream`` ("ingest0" / "ingest1");
+        ``g.event`` is recorded behind the last kernel.  No device-to-host copy is enqueued here."""
+        lib, dev, nb, tokens_stream = self.lib, self.dev, g.n_blocks, self.tokens_stream
+        self.mark("launch %s: start" % g.units[:2])
+        # The group's large buffers -- the inflated bytes, the inflate's workspace -- are taken on THIS thread's (default)
+        # stream and handed to the group's stream with record_stream: the caching allocator keeps its free blocks per
+        # stream, so buffers allocated on the ingest streams (new ones every run) never met a cached block and were
+        # hipMalloc'ed fresh -- 0.2 ms per GB on most boxes, 15 ms per GB on some: a 0.24 s stall in front of the
+        # largest group's launch (two of nine bench runs).
+        variant = kernels.inflate_variant_for(nb)
+        d_raw = torch.empty(max(g.inflated_bytes, 16), dtype=torch.uint8, device=dev)
+        d_ws = kernels.inflate_workspace(lib, variant, g.inflated_bytes, nb, dev)
+        # (the allocator may hand out a block that default-stream work freed and is still using: the group's streams
+        # order themselves behind whatever the default stream holds at this point -- normally nothing)
+        allocated = torch.cuda.Event()
+        allocated.record(torch.cuda.default_stream(dev))
+        if tokens_stream is not None:
+            tokens_stream.wait_event(allocated)
+        with torch.cuda.stream(stream):
+            stream.wait_event(allocated)
+            stream.wait_event(g.copied)                        # the last slot of the group's compressed bytes is on the device
+            d_comp = g.d_comp
+            d_comp.record_stream(stream)
+            d_raw.record_stream(stream)
+            if d_ws is not None:
+                d_ws.record_stream(stream)
+            d_tab = g.tab.to(dev, non_blocking=True)
+            d_status = torch.zeros(nb, dtype=torch.int32, device=dev)
+            d_len = d_tab[nb:2 * nb].to(torch.int32)
+            st = kernels._stream_ptr(dev)
+            # every group's tokens kernel on ONE stream, in launch order (include/svx.h, svx_bgzf_inflate_fast_on): two of them
+            # side by side share the chip and finish together -- late; in a row, the first group's chromosomes are out a
+            # whole tokens launch earlier and its LZ copies (latency-bound) run next to the second group's tokens
+            if tokens_stream is not None and variant == "fast":
+                for t_ in (d_comp, d_ws, d_tab, d_len, d_status):
+                    t_.record_stream(tokens_stream)
+            kernels.launch_inflate(lib, variant, d_comp.data_ptr(), d_tab.data_ptr(), d_len.data_ptr(), d_tab[2 * nb:].data_ptr(), nb,
+                                   d_raw.data_ptr(), d_status.data_ptr(), g.inflated_bytes, dev, ws=d_ws,
+                                   tokens_stream=tokens_stream if variant == "fast" else None)
+            if kernels.bgzf_crc_wanted():                      # the footers' CRC32 (htslib checks it on every block): status 9 where one differs
+                _lib.check(lib.svx_bgzf_crc32(d_raw.data_ptr(), d_tab[2 * nb:].data_ptr(), d_comp.data_ptr(), d_tab.data_ptr(), d_len.data_ptr(), nb,
+                                              d_status.data_ptr(), st), "svx_bgzf_crc32")
+            total_starts = sum(g.n_starts)
+            d_counts = torch.empty((total_starts + 1, 4), dtype=torch.int64, device=dev)
+            row = 0
+            for at, n in zip(g.start_at, g.n_starts):
+                _lib.check(lib.svx_bam_walk_count(d_raw.data_ptr(), d_tab[at:].data_ptr(), n, d_counts[row:].data_ptr(), st), "svx_bam_walk_count")
+                row += n
+            d_counts[total_starts, 0] = d_status.max()
+            # NO read-back is enqueued here.  A device-to-host copy goes to a DMA engine's queue at once, with a wait for
+            # the kernels in front of it -- and the engine serves its queue in order: the counts' copy sat there for the
+            # whole inflate (40-120 ms) and every other read-back of the process (the previous group's packed arrays,
+            # the scans' results, the CNN's predictions) waited behind it.  finish_group() copies once the event is through.
+            ev = torch.cuda.Event()
+            ev.record()
+        g.d_raw, g.d_tab, g.d_counts, g.event, g.stream = d_raw, d_tab, d_counts, ev, stream
+        self.mark("launched %s" % g.units[:2])
+        return g
 
-        for t, (lo, hi, linear) in zip(tids, spans):
-            seeds = linear[(linear >= np.uint64(lo)) & (linear < np.uint64(hi))]
-            voffs = np.unique(np.concatenate([np.asarray([lo], np.uint64), seeds, np.asarray([hi], np.uint64)]))
-            starts = np.unique(inflated_offset(voffs))           # (two virtual offsets of one byte: a block boundary)
-            yield self._walk(t, d_raw, starts)
-
-    def _walk(self, tid, d_raw, starts):
-        import time
-        lib, dev = self.lib, self.device
-        st = kernels._stream_ptr(dev)
+    def finish_group(self, g):
+        """Driver thread, generator: waits for ``g.event``, reads the counts back (the group's ONE read-back: on the group's
+        stream, into pinned memory), enqueues every unit's extraction and packed read-back on the group's stream -- the two
+        buffers they share are allocated on this thread's DEFAULT stream -- and yields None (everything is enqueued: the
+        driver may launch the next group), then per unit what :meth:`run` yields, each after its own read-back event."""
+        lib, dev, stream = self.lib, self.dev, g.stream
         t0 = time.perf_counter()
-        n_starts = int(starts.size) - 1
-        d_starts = torch.from_numpy(starts.view(np.int64)).to(dev)
-        d_counts = torch.empty((n_starts, 4), dtype=torch.int64, device=dev)
-        _lib.check(lib.svx_bam_walk_count(d_raw.data_ptr(), d_starts.data_ptr(), n_starts, d_counts.data_ptr(), st), "svx_bam_walk_count")
-        counts = d_counts.cpu().numpy()
-        bad = counts[:, 3] != 0
-        if bad.any():
-            code = int(counts[bad, 3][0])
-            raise DeviceIngestError({1: "the linear index does not match the records", 2: "malformed BAM record"}.get(code, "walk error %d" % code))
-        base = np.zeros((n_starts, 3), np.uint64)
-        base[1:] = np.cumsum(counts[:-1, :3], axis=0).astype(np.uint64)
-        n, words, name_bytes = (int(v) for v in counts[:, :3].sum(axis=0))
-        d_base = torch.from_numpy(base.view(np.int64)).to(dev)
-        d_tid = torch.empty(n, dtype=torch.int32, device=dev)
-        d_pos = torch.empty(n, dtype=torch.int32, device=dev)
-        d_flag = torch.empty(n, dtype=torch.int16, device=dev)
-        d_mapq = torch.empty(n, dtype=torch.uint8, device=dev)
-        d_lseq = torch.empty(n, dtype=torch.int32, device=dev)
-        d_cig_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
-        d_cigar = torch.empty(max(words, 1), dtype=torch.int32, device=dev)
-        d_name_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
-        d_names = torch.empty(max(name_bytes, 1), dtype=torch.uint8, device=dev)
-        _lib.check(lib.svx_bam_walk_extract(d_raw.data_ptr(), d_starts.data_ptr(), n_starts, d_base.data_ptr(), d_tid.data_ptr(), d_pos.data_ptr(),
-                                            d_flag.data_ptr(), d_mapq.data_ptr(), d_lseq.data_ptr(), d_cig_off.data_ptr(), d_cigar.data_ptr(),
-                                            d_name_off.data_ptr(), d_names.data_ptr(), n, st), "svx_bam_walk_extract")
-        t1 = time.perf_counter()
-        alloc = self.alloc_for() if self.alloc_for is not None else (lambda _name, dtype, k: np.empty(k, dtype))
+        g.event.synchronize()
+        self.mark("inflate + count done %s" % g.units[:2])
+        g.d_comp = None
+        self.stats["h2d_inflate_s"] += time.perf_counter() - t0
+        d_counts, g.d_counts = g.d_counts, None
+        h_counts = torch.empty(tuple(d_counts.shape), dtype=torch.int64, pin_memory=True)
+        with torch.cuda.stream(stream):
+            h_counts.copy_(d_counts, non_blocking=True)
+            ev_c = torch.cuda.Event()
+            ev_c.record()
+        ev_c.synchronize()
+        counts = h_counts.numpy()
+        if int(counts[-1, 0]) != 0:
+            raise DeviceIngestError("corrupt BGZF blocks in %s" % g.units, sorted({u.tid for u in g.units}))
+        d_raw, d_tab = g.d_raw, g.d_tab
+        t0 = time.perf_counter()
+        # Sizes first, then ONE device buffer and ONE pinned buffer per group for the packed arrays of all its chromosomes
+        # (and one device buffer for their CIGAR words): every first-time hipMalloc / hipHostMalloc of a run costs
+        # milliseconds during which the other threads' HIP calls -- and their page faults -- wait; per chromosome that
+        # was six of them.
+        packed, row, pack_at, word_at = [], 0, 0, 0
+        for unit, at, n_starts in zip(g.units, g.start_at, g.n_starts):
+            c = counts[row:row + n_starts]
+            bad = c[:, 3] != 0
+            if bad.any():
+                code = int(c[bad, 3][0])
+                raise DeviceIngestError({1: "the linear index does not match the records", 2: "malformed BAM record"}.get(code, "walk error %d" % code), [unit.tid])
+            n, words, name_bytes = (int(v) for v in c[:, :3].sum(axis=0)) if n_starts else (0, 0, 0)
+            p = _Packed(unit, at, n_starts, row, n, words, name_bytes, pack_at, word_at)
+            packed.append(p)
+            pack_at += p.size
+            word_at += (max(words, 1) + 63) // 64 * 64           # (svx_cigar_scan reads 16-byte quads: every chromosome starts aligned)
+            row += n_starts
+        base_all = torch.zeros((max(row, 1), 3), dtype=torch.int64, pin_memory=True)
+        for p in packed:
+            if p.n_starts > 1:
+                base_all.numpy()[p.row + 1:p.row + p.n_starts] = np.cumsum(counts[p.row:p.row + p.n_starts - 1, :3], axis=0)
+        d_pack_all = torch.empty(max(pack_at, 256), dtype=torch.uint8, device=dev)        # (default stream: see launch())
+        d_cigar_all = torch.empty(max(word_at, 64), dtype=torch.int32, device=dev)
+        allocated = torch.cuda.Event()
+        allocated.record(torch.cuda.default_stream(dev))
+        with torch.cuda.stream(stream):
+            stream.wait_event(allocated)
+            st = kernels._stream_ptr(dev)
+            d_pack_all.record_stream(stream)
+            d_cigar_all.record_stream(stream)
+            d_base_all = base_all.to(dev, non_blocking=True)
+            h_pack_all = torch.empty(max(pack_at, 256), dtype=torch.uint8, pin_memory=True)
+            for p in packed:
+                if p.n == 0:                                     # a slice (or a reference) without a record: nothing to extract
+                    continue
+                n = p.n
+                d_pack = d_pack_all[p.pack_at:p.pack_at + p.size]
+                d_base = d_base_all[p.row:p.row + p.n_starts]
+                d_cig_off, d_name_off = _section(d_pack, p.offs, 0, torch.int64, n + 1), _section(d_pack, p.offs, 1, torch.int64, n + 1)
+                d_tid, d_pos, d_lseq = _section(d_pack, p.offs, 2, torch.int32, n), _section(d_pack, p.offs, 3, torch.int32, n), _section(d_pack, p.offs, 4, torch.int32, n)
+                d_flag, d_mapq = _section(d_pack, p.offs, 5, torch.int16, n), _section(d_pack, p.offs, 6, torch.uint8, n)
+                d_names = _section(d_pack, p.offs, 7, torch.uint8, max(p.name_bytes, 1))
+                d_cigar = d_cigar_all[p.word_at:p.word_at + max(p.words, 1)]
+                _lib.check(lib.svx_bam_walk_extract(d_raw.data_ptr(), d_tab[p.at:].data_ptr(), p.n_starts, d_base.data_ptr(), d_tid.data_ptr(),
+                                                    d_pos.data_ptr(), d_flag.data_ptr(), d_mapq.data_ptr(), d_lseq.data_ptr(), d_cig_off.data_ptr(),
+                                                    d_cigar.data_ptr(), d_name_off.data_ptr(), d_names.data_ptr(), n, st), "svx_bam_walk_extract")
+                p.h_pack = h_pack_all[p.pack_at:p.pack_at + p.size]
+                p.h_pack.copy_(d_pack, non_blocking=True)
+                # svx_cigar_scan reads the offsets and positions where they are: views of the group's pack buffer, which
+                # lives as long as one of them does (until round 4: two clones and two fills of the CSR arrays' closing
+                # entries per chromosome -- four tiny launches, each a few hundred microseconds of waiting for room on a
+                # chip that is full of inflate and CNN waves; the extract kernel writes the closing entries itself now).
+                # The consumer scans on another stream and orders itself behind this one through the event only.
+                p.event = torch.cuda.Event()
+                p.event.record()
+                p.d_cigar, p.d_cig_off, p.d_pos = d_cigar, d_cig_off, d_pos
+        self.stats["walk_s"] += time.perf_counter() - t0
+        yield None                                              # every chromosome's extraction is enqueued: the caller may launch the next group
+        for p in packed:
+            if p.event is None:
+                yield p.unit, None, None
+                continue
+            t0 = time.perf_counter()
+            p.event.synchronize()
+            self.stats["d2h_s"] += time.perf_counter() - t0
+            self.mark("packed read-back done")
+            yield p.unit, self.dec._make_finish(p.h_pack.numpy(), p.n, p.words, p.name_bytes, p.d_cigar), (p.d_cigar, p.d_cig_off, p.d_pos)
+        g.d_raw = g.d_tab = None
 
-        def to_host(name, d, dtype):
-            host = alloc(name, dtype, d.numel())
-            if d.numel():
-                torch.from_numpy(host).copy_(d)                  # (staged through the runtime's pinned bounce buffer)
-            return host
-        tid_h = to_host("tid", d_tid, np.int32)
-        pos_h = to_host("pos", d_pos, np.int32)
-        l_seq_h = to_host("l_seq", d_lseq, np.int32)
-        flag_h = alloc("flag", np.uint16, n)
-        if n:
-            torch.from_numpy(flag_h.view(np.int16)).copy_(d_flag)
-        mapq_h = to_host("mapq", d_mapq, np.uint8)
-        cig_off_h = to_host("cig_off", d_cig_off, np.int64)
-        # the CIGAR words stay in HBM (svx_cigar_scan reads them there).  The host has one rare use for them -- comparing
-        # duplicated records by value (collection.classes.Seg.same_value) -- and gets its copy off the critical path:
-        # spill_cigar() below, called by the feed after the chromosome has been handed to the pipeline
-        cigar_h = LazyCigar(words)
-        name_off_h = d_name_off.cpu().numpy()
-        names_h = d_names[:name_bytes].cpu().numpy()
-        t2 = time.perf_counter()
-        self.stats["walk_s"] += t1 - t0
-        self.stats["d2h_s"] += t2 - t1
+    def pump(self, block):
+        """Driver thread: launch what the reader has ready, up to ``depth`` groups in flight, each on the next of the group
+        streams; block only when nothing is in flight."""
+        while not self.done and len(self.inflight) < self.depth:
+            try:
+                item = self.read_q.get(block=block and not self.inflight, timeout=None)
+            except queue.Empty:
+                return
+            if item is None:
+                self.done = True
+                return
+            if isinstance(item, BaseException):
+                # a LATER group failed in the reader: the groups in flight in front of it are healthy -- they are finished and
+                # their chromosomes yielded first (drive() raises this once nothing is in flight any more), so that the
+                # consumer's count of finished chromosomes points at the failing group and nothing decoded is thrown away
+                self.error, self.done = item, True
+                return
+            self.inflight.append(self.launch(item, self.group_streams[self.launched % self.depth]))
+            self.launched += 1
 
-        def finish():
-            t2 = time.perf_counter()
-            name_id = alloc("name_id", np.int32, n)
-            uniq = np.empty(max(name_bytes, 1), np.uint8)
-            ub = np.zeros(1, np.uint64)
-            n_unique = int(lib.svx_name_ids(names_h.ctypes.data, name_off_h.ctypes.data, n, name_id.ctypes.data, uniq.ctypes.data, ub.ctypes.data))
-            blob = alloc("names", np.uint8, int(ub[0]))
-            blob[:] = uniq[:int(ub[0])]
-            name_list = blob.tobytes().decode().split("\n")[:-1] if n_unique else []
-            self.stats["names_s"] += time.perf_counter() - t2
-            table = AlignmentTable(self.references, self.lengths, tid_h, pos_h, flag_h, mapq_h, l_seq_h, name_id, name_list, np.empty(0, np.uint32),
-                                   cig_off_h, self.header_text)
-            table.cigar = cigar_h                                # (the constructor wants an array)
-            table._names_blob = blob
-            table._alloc = alloc
-            table._shm_dir = getattr(alloc, "dir", None)
-            table._d_cigar = d_cigar
-            return table
-        return finish, (d_cigar[:max(words, 1)], d_cig_off, d_pos)
+    def put(self, x):
+        """Driver thread: ``x`` into ``out_q`` unless the consumer has gone (-> False)."""
+        while not self.stop.is_set():
+            try:
+                self.out_q.put(x, timeout=0.2)
+                return True
+            except queue.Full:
+                continue
+        return False
+
+    def drive(self):
+        """Driver thread ("svx-inflate-driver"): pump, wait for the oldest group in flight, finish it unit by unit into
+        ``out_q`` -- pumping all the while --, then the end marker or the exception (the reader's, once nothing is in flight
+        in front of it).  Issues no device work of its own: that is launch() and finish_group()."""
+        try:
+            while not self.stop.is_set():
+                self.pump(block=True)
+                if not self.inflight:
+                    if self.error is not None:
+                        raise self.error
+                    break
+                head = self.inflight[0]
+                while not head.event.query():                  # keep launching while the oldest group is still on the device ...
+                    self.pump(block=False)
+                    time.sleep(0.0005)
+                self.inflight.popleft()
+                for part in self.finish_group(head):
+                    # (None: the group's extraction is enqueued -- what is launched now runs behind it)
+                    if part is not None and not self.put(part):
+                        return
+                    self.pump(block=False)                      # (a group of a dozen chromosomes takes tens of ms to finish)
+                self.mark("group %s finished" % head.units[:2])
+            self.put(None)
+        except BaseException as exc:                             # noqa: BLE001 -- re-raised in the consumer's thread
+            self.put(exc)
+
+    # ---- warm thread --------------------------------------------------------------------------------------------------
+    def warm(self):
+        """Warm thread ("svx-inflate-warm"), default stream: the device buffers of the first two groups, allocated while the
+        first read is still on its way (the caching allocator hands them out again): their hipMalloc calls would sit on the
+        path to the first chromosome.  Only those: on some boxes a first hipMalloc costs 15 ms per GB instead of 0.2 -- 0.3 s
+        for the 22 GB of all groups, during which no other HIP call of the process returns -- and the large groups' buffers
+        are better allocated when their turn comes, next to device work that is already queued."""
+        for g in self.groups[:2]:                              # in the order they will be asked for: compressed bytes, inflated bytes
+            nbytes = sum(_size_of(u) for u in g)
+            if self.stop.is_set():
+                break
+            for n in (nbytes + (1 << 20), 3 * nbytes + (1 << 20)):
+                torch.empty(n, dtype=torch.uint8, device=self.dev)      # allocated and released at once: the block stays in the allocator's cache
+        self.mark("warm: done")
+
+    # ---- consumer -----------------------------------------------------------------------------------------------------
+    def run(self):
+        """The caller's thread, generator: starts the three threads and yields what the driver puts out; an exception of the
+        reader or the driver is raised here.  No device work; on exit (exhausted, failed or abandoned) the threads are told
+        to stop, the reader is joined and the "copy" stream synchronised before the staging slots go back."""
+        reader = threading.Thread(target=self.reader, name="svx-read", daemon=True)
+        reader.start()
+        threading.Thread(target=self.warm, name="svx-inflate-warm", daemon=True).start()
+        threading.Thread(target=self.drive, name="svx-inflate-driver", daemon=True).start()
+        try:
+            while True:
+                part = self.out_q.get()
+                if part is None:
+                    break
+                if isinstance(part, BaseException):
+                    raise part
+                yield part
+        finally:
+            self.stop.set()
+            try:
+                reader.join(timeout=10)                        # (an abandoned run: the reader may be in the middle of a group)
+                self.copy_stream.synchronize()                 # the slots go back to the process-wide ring: no copy may still read them
+            finally:
+                if not reader.is_alive():
+                    self.ring.release()

@@ -176,6 +176,7 @@ def test_device_decoder_equals_the_host_decoder(tmp_path):
     """ingest_gpu.DeviceDecoder (read -> upload -> svx_bgzf_inflate -> svx_bam_walk_* through the .bai linear index) gives,
     chromosome by chromosome, the tables of the host decoder, and the packed CIGARs it leaves in HBM are the same words."""
     from svision_amd import synth
+    import svision_amd.ingest_gpu as ig
     from svision_amd.ingest_gpu import DeviceDecoder, DeviceIngestError
     cfg = synth.SimConfig(contigs=[("c1", 900_000), ("c2", 50_000), ("c3", 600_000), ("c4", 300_000)], coverage=12, read_len_mean=9000,
                           read_len_sd=1500, sv_spacing=20_000, sv_min_gap=9_000, sv_max=3000, seed=9)
@@ -185,41 +186,44 @@ def test_device_decoder_equals_the_host_decoder(tmp_path):
     path = str(tmp_path / "dev.bam")
     bam.write_bam_segments(path, table.references, table.lengths, segs)
     head = bam.read_bam_header(path)
-    for first_group in (1 << 10, 1 << 40):                               # every chromosome its own launch / all in one
-        import svision_amd.ingest_gpu as ig
-        ig.FIRST_GROUP_BYTES = ig.GROUP_BYTES = first_group
-        dec = DeviceDecoder(path, path + ".bai", head.references, head.lengths, head.header_text, "cuda:0", threads=3)
-        assert dec.usable([0, 1, 2, 3])
-        groups = dec.groups([0, 1, 2, 3])
-        assert sorted(t for g in groups for t in g) == [0, 2, 3]
-        got = {}
-        for g in groups:
-            for finish, (d_cigar, d_off, d_pos) in dec.decode_group(g):
+    saved = ig.FIRST_GROUP_BYTES, ig.PIPE_GROUP_BYTES
+    try:
+        for group_bytes in (1 << 10, 1 << 40):                           # every chromosome its own launch / all in one
+            ig.FIRST_GROUP_BYTES = ig.PIPE_GROUP_BYTES = group_bytes
+            dec = DeviceDecoder(path, path + ".bai", head.references, head.lengths, head.header_text, "cuda:0", threads=3)
+            assert dec.usable([0, 1, 2, 3])
+            got = {}
+            for finish, (d_cigar, d_off, d_pos) in dec.parts_pipelined([0, 1, 2, 3]):
                 tb = finish()
                 assert tb.cigar.size == int(d_off[-1].item())
                 with pytest.raises(RuntimeError):
                     tb.cigar[0]                                # the words are on the device only ...
                 ig.spill_cigar(tb)                             # ... until the feed spills them to the table's slot
                 t = int(tb.tid[0])
+                assert t not in got
                 got[t] = tb
                 assert np.array_equal(d_cigar.cpu().numpy().view(np.uint32)[:tb.cigar.size], tb.cigar)
                 assert np.array_equal(d_off.cpu().numpy(), tb.cig_off) and np.array_equal(d_pos.cpu().numpy(), tb.pos)
-        for t in (0, 2, 3):
-            _same_table(got[t], bam.read_bam(path, tids=[t]))
+            assert sorted(got) == [0, 2, 3]
+            for t in (0, 2, 3):
+                _same_table(got[t], bam.read_bam(path, tids=[t]))
+    finally:
+        ig.FIRST_GROUP_BYTES, ig.PIPE_GROUP_BYTES = saved
     # the golden BAM written by the plain writer (own .bai), and an index that does not fit the file
     plain = str(tmp_path / "plain.bam")
     bam.write_bam(plain, bam.read_bam(os.path.join(helpers.GOLDEN, "collect_small.bam")), index=True)
     head = bam.read_bam_header(plain)
     dec = DeviceDecoder(plain, plain + ".bai", head.references, head.lengths, head.header_text, "cuda:0")
-    for g in dec.groups([0, 1]):
-        for finish, _arrays in dec.decode_group(g):
-            tb = finish()
-            ig.spill_cigar(tb)
-            _same_table(tb, bam.read_bam(plain, tids=[int(tb.tid[0])]))
+    n_tables = 0
+    for finish, _arrays in dec.parts_pipelined([0, 1]):
+        tb = finish()
+        ig.spill_cigar(tb)
+        _same_table(tb, bam.read_bam(plain, tids=[int(tb.tid[0])]))
+        n_tables += 1
+    assert n_tables == len(dec.whole_units([0, 1])) > 0
     wrong = DeviceDecoder(path, plain + ".bai", head.references, head.lengths, head.header_text, "cuda:0")
     with pytest.raises(DeviceIngestError):
-        for g in wrong.groups([0, 1]):
-            list(wrong.decode_group(g))
+        list(wrong.parts_pipelined([0, 1]))
 
 
 def test_command_line_with_device_ingest_equals_host_ingest(tmp_path):

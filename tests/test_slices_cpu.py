@@ -232,3 +232,51 @@ def test_lazy_cigar_in_the_owner_process_waits_for_the_spill():
     failed.event.set()                                        # a spill that failed sets the event without attaching anything
     with pytest.raises(RuntimeError):
         failed[0]
+
+
+def test_record_starts_lie_on_record_boundaries(sliced):
+    """ingest_gpu._index_blocks + _record_starts (the reader's host work): the starts a reference's linear index gives, as
+    offsets into the inflated file, are record boundaries -- a walk from the first (4 + block_size per record) hits every one
+    of them and ends on the last, through records of that reference only."""
+    import struct
+    from svision_amd import ingest_gpu as ig
+    path, table, _fasta, dec = sliced
+    raw = np.fromfile(path, np.uint8)
+    blocks = ig._index_blocks(dec.lib, raw.ctypes.data, raw.size, 0)
+    assert blocks.k == blocks.coff.size > 100 and blocks.coff[0] == 0 and blocks.used <= raw.size
+    data = bam.bgzf_decompress(raw.tobytes())
+    dst = np.zeros(blocks.k + 1, np.uint64)
+    dst[1:] = np.cumsum(blocks.isize.astype(np.uint64))
+    assert int(dst[-1]) == len(data)
+    for tid in (0, 1):
+        lo, hi, linear = dec.spans[tid]
+        starts = ig._record_starts(blocks.coff, dst, lo, hi, linear).tolist()
+        assert len(starts) > 10 and starts == sorted(set(starts))
+        at, hit, records = starts[0], set(), 0
+        while at < starts[-1]:
+            hit.add(at)
+            block_size, ref_id = struct.unpack_from("<ii", data, at)
+            assert block_size >= 32 and ref_id == tid
+            at += 4 + block_size
+            records += 1
+        assert at == starts[-1] and hit.issuperset(starts[:-1])
+        assert records == int((table.tid == tid).sum())
+    lo, hi, linear = dec.spans[0]
+    between = (int(blocks.coff[1]) + 1) << 16                                  # no block of the file starts at this file offset
+    with pytest.raises(ig.DeviceIngestError):
+        ig._record_starts(blocks.coff, dst, lo, hi, np.append(linear, np.uint64(between)))
+    with pytest.raises(ig.DeviceIngestError):
+        ig._record_starts(blocks.coff, dst, between, hi, linear)
+
+
+@pytest.mark.parametrize("n, name_bytes", [(0, 0), (1, 7), (4321, 98_765)])
+def test_pack_layout_sections_are_aligned_and_disjoint(n, name_bytes):
+    """ingest_gpu._pack_layout: [cig_off n+1][name_off n+1][tid][pos][l_seq][flag][mapq][names] in one buffer."""
+    from svision_amd.ingest_gpu import _pack_layout
+    offs, size = _pack_layout(n, name_bytes)
+    nbytes = [8 * (n + 1), 8 * (n + 1), 4 * n, 4 * n, 4 * n, 2 * n, n, name_bytes]      # element count x element size
+    assert len(offs) == len(nbytes) + 1 and int(offs[0]) == 0
+    for k, want in enumerate(nbytes):
+        assert int(offs[k]) % 16 == 0
+        assert int(offs[k]) + want <= int(offs[k + 1])                          # the section holds its elements and ends in front of the next
+    assert size % 256 == 0 and size >= int(offs[-1]) + 16
