@@ -378,6 +378,22 @@ int            svx_bam_walk_extract(const uint8_t* d_raw, const uint64_t* d_star
                                     int32_t* d_tid, int32_t* d_pos, uint16_t* d_flag, uint8_t* d_mapq, int32_t* d_l_seq,
                                     int64_t* d_cig_off, uint32_t* d_cigar, int64_t* d_name_off, uint8_t* d_names, uint32_t n_records,
                                     void* stream);
+/* The same walk WITH the read bases (--hash / --graph on the device engine); the two exports above are untouched by it.
+ *   svx_bam_walk_count_seq    as svx_bam_walk_count, and d_seq_bytes [n_starts] = the SEQ bytes -- (l_seq + 1) / 2 a record --
+ *                             between start i and start i + 1
+ *   svx_bam_walk_extract_seq  as svx_bam_walk_extract, and d_seq_base [n_starts] = exclusive prefix sum of d_seq_bytes;
+ *                             fills d_seq_off [records + 1] (dense, as the host decoder builds it; the closing entry = the
+ *                             total) and d_seq [total]: every record's 4-bit SEQ as stored in the file, the spare nibble of
+ *                             an odd length included.  A wave per record, 16-byte stores aligned on d_seq, whole chunks only
+ *                             where they hold no neighbour's byte.  d_raw must be 16-byte aligned and readable up to the
+ *                             next multiple of 16 behind its last byte (aligned 16-byte loads) */
+int            svx_bam_walk_count_seq(const uint8_t* d_raw, const uint64_t* d_starts, uint32_t n_starts, uint64_t* d_counts,
+                                      uint64_t* d_seq_bytes, void* stream);
+int            svx_bam_walk_extract_seq(const uint8_t* d_raw, const uint64_t* d_starts, uint32_t n_starts, const uint64_t* d_base,
+                                        int32_t* d_tid, int32_t* d_pos, uint16_t* d_flag, uint8_t* d_mapq, int32_t* d_l_seq,
+                                        int64_t* d_cig_off, uint32_t* d_cigar, int64_t* d_name_off, uint8_t* d_names,
+                                        const uint64_t* d_seq_base, int64_t* d_seq_off, uint8_t* d_seq, uint32_t n_records,
+                                        void* stream);
 /* host helpers of the device-side ingestion: parallel positional read into caller memory; the whole BGZF blocks of a
  * buffer (payload offset / size, ISIZE, file offset; -> their number or -1, *used = bytes they cover); QNAME ids by
  * first occurrence (-> number of distinct names, written '\n'-separated to uniq) */

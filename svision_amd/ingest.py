@@ -27,6 +27,11 @@ from .io.bam import AlignmentTable, BamStream
 from . import streams
 from .sample import Sample
 
+# What "auto" means for a run that wants the read bases (--hash / --graph), decided by measurement (profiles/ingest_seq_ab.txt,
+# DESIGN.md section 6): the device engine only if its median is below the host engine's fastest run.  An explicit
+# engine="gpu" / SVX_INGEST=gpu is honoured either way.
+AUTO_WITH_SEQ = "cpu"
+
 _KEYS = itertools.count()                                    # keys of the parts announced to the helper processes (pipeline.PooledHotPath)
 
 
@@ -110,10 +115,11 @@ class ChromosomeFeed:
         self.header_text = header_text
         # where the BGZF blocks are inflated: "gpu" = on the device (ingest_gpu.DeviceDecoder), "cpu" = libdeflate on host
         # threads (io.bam.BamStream), "auto" (the default; SVX_INGEST overrides) = the device whenever it can: the file has a
-        # .bai with its linear index and the run needs no read bases (--hash / --graph).  On a 16-CPU GPU box the device engine
-        # takes 0.6 s for the 3.9 GB of the bench's 20-window file, the host engine 1.15 s (DESIGN.md section 5 "Device-side
-        # ingestion"); a reference the device engine cannot take (a linear index that does not match, a corrupt block) falls back to the
-        # host engine chromosome by chromosome.
+        # .bai with its linear index.  On a 16-CPU GPU box the device engine takes 0.6 s for the 3.9 GB of the bench's 20-window
+        # file, the host engine 1.15 s (DESIGN.md section 5 "Device-side ingestion"); a reference the device engine cannot take (a
+        # linear index that does not match, a corrupt block) falls back to the host engine chromosome by chromosome.  Runs that
+        # want the read bases (--hash / --graph) are served by the device engine too (svx_bam_walk_*_seq; the bases follow the
+        # hand-over through the spill thread); which engine "auto" picks for them: AUTO_WITH_SEQ below.
         self.engine = engine or os.environ.get("SVX_INGEST", "auto")
         self.references, self.lengths = list(references), list(lengths)
         self.chroms = list(chroms)
@@ -147,9 +153,9 @@ class ChromosomeFeed:
                 d = os.path.join(self.root, "s%d" % self._n_slots)
                 self._n_slots += 1
                 os.makedirs(d)
-        flag = os.path.join(d, "cigar.ready")
-        if os.path.exists(flag):
-            os.remove(flag)
+        for flag in (os.path.join(d, "cigar.ready"), os.path.join(d, "seq.ready")):
+            if os.path.exists(flag):
+                os.remove(flag)
         arrays = {}
 
         def alloc(name, dtype, n):
@@ -200,8 +206,8 @@ class ChromosomeFeed:
                 raise RuntimeError("ChromosomeFeed needs the GPU (svx_cigar_scan); there is no CPU fallback")
             engine = self.engine
             if engine == "auto":
-                engine = "gpu"
-            if engine == "gpu" and (self.index is None or self.with_seq or not str(self.device).startswith("cuda")):
+                engine = AUTO_WITH_SEQ if self.with_seq else "gpu"
+            if engine == "gpu" and (self.index is None or not str(self.device).startswith("cuda")):
                 engine = "cpu"
             self.stats["engine"] = engine
             stage_a = threading.Thread(target=self._decode, args=(engine, tids, decoded), name="svx-decode", daemon=True)
@@ -285,6 +291,9 @@ class ChromosomeFeed:
                     meta["spilled"] = threading.Event()
                     if hasattr(table.cigar, "attach"):            # (LazyCigar: a reader in THIS process waits for the spill)
                         table.cigar.event = meta["spilled"]
+                    if hasattr(table.seq_packed, "attach"):       # (LazySeq: the bases follow the same way, behind the words)
+                        meta["lazy_seq"] = int(table.seq_packed.size)
+                        table.seq_packed.event = meta["spilled"]
                     spill.put((table, meta["spilled"], sample))
                 else:
                     # host engine: the upload served the scan and nothing else (windows of a file-driven run are never scanned
@@ -364,9 +373,10 @@ class ChromosomeFeed:
         return need + 1000
 
     def _spill(self, jobs):
-        """Stage C: host copies of the device-decoded CIGAR words (ingest_gpu.spill_cigar), after the hand-over."""
+        """Stage C: host copies of the device-decoded CIGAR words (ingest_gpu.spill_cigar) and, with_seq, of the bases
+        (ingest_gpu.spill_seq), after the hand-over."""
         import torch
-        from .ingest_gpu import spill_cigar
+        from .ingest_gpu import spill_cigar, spill_seq
         stream = streams.get("spill", self.device)
         while True:
             job = jobs.get()
@@ -376,10 +386,13 @@ class ChromosomeFeed:
             try:
                 with torch.cuda.stream(stream):
                     spill_cigar(table)
+                    if getattr(table, "_d_seq", None) is not None:
+                        table._d_seq.record_stream(stream)
+                        spill_seq(table)
                     if sample.device_buffers is not None:      # (the arrays were last used on this stream: the spill's copy)
                         for t in sample.device_buffers[:3]:
                             t.record_stream(stream)
-                table._d_cigar = None
+                table._d_cigar = table._d_seq = None
                 sample.device_buffers = None                   # the device arrays of the slice: scanned, spilled, never read again
             except BaseException as exc:                       # noqa: BLE001 -- a helper that needs the words would wait for ever
                 self.error = self.error or exc
@@ -439,7 +452,7 @@ class ChromosomeFeed:
                 # pread threads of the device engine: copies out of the page cache, ~2 GB/s each (SVX_READ_THREADS overrides)
                 n_read = int(os.environ.get("SVX_READ_THREADS", "0")) or min(8, max(1, self.threads))
                 dec = self.decoder = DeviceDecoder(self.bam_path, self.index, self.references, self.lengths, self.header_text, self.device,
-                                                   threads=n_read, alloc_for=self._slot_alloc)
+                                                   threads=n_read, alloc_for=self._slot_alloc, with_seq=self.with_seq)
                 if not dec.usable(tids):
                     host_parts(tids)
                 else:
@@ -617,6 +630,9 @@ def load_shared_sample(meta, fasta):
     if meta.get("lazy_cigar") is not None:                     # device engine: the words arrive in the slot a little later
         from .ingest_gpu import LazyCigar
         table.cigar = LazyCigar(meta["lazy_cigar"], os.path.join(d, "cigar.bin"), os.path.join(d, "cigar.ready"))
+    if meta.get("lazy_seq") is not None:                       # ... and, with_seq, the bases behind them
+        from .ingest_gpu import LazySeq
+        table.seq_packed = LazySeq(meta["lazy_seq"], os.path.join(d, "seq_packed.bin"), os.path.join(d, "seq.ready"))
     from . import kernels
     gaps = arr("gaps", kernels.GAP_DTYPE)
     stats = np.asarray(arr("stats", np.int32)).reshape(meta["stats_shape"])

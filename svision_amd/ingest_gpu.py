@@ -11,7 +11,9 @@ GPU boxes this was built on give a container the CPU time of 16 cores (svision_a
 inflated data, a quarter of what the device pipeline consumes.  The same data inflates at 75 GB/s on the MI355X (two kernels,
 136 and 170 GB/s).
 Replaces pysam's AlignmentFile.fetch (run_collection.py:23-26) like the host reader (io.bam.BamStream), which stays the
-engine for files without a linear index, for --hash / --graph (read bases wanted) and for SVX_INGEST=cpu.
+engine for files without a linear index and for SVX_INGEST=cpu.  --hash / --graph want the read bases too: with
+``with_seq`` the walk also packs every record's 4-bit SEQ (svx_bam_walk_*_seq); like the CIGAR words the bases stay in HBM until
+the hand-over is through and follow through the spill thread (LazySeq, spill_seq).
 
 Map of a run (DeviceDecoder.units_pipelined -> _Pipeline; the streams are those of svision_amd/streams.py):
 
@@ -63,12 +65,14 @@ class DeviceIngestError(RuntimeError):
         self.tids = list(tids) if tids is not None else None
 
 
-class LazyCigar:
-    """Stand-in for ``AlignmentTable.cigar`` while the words exist on the device only.  ``attach(array)`` (owner process,
-    after the spill) or ``path`` + ``ready`` (helper processes: the file the owner spills to and its completion flag)."""
+class _LazyArray:
+    """An array of a device-decoded table that exists on the device only at the hand-over and reaches the host a little
+    later, through the spill thread.  ``attach(array)`` (owner process, after the spill) or ``path`` + ``ready`` (helper
+    processes: the file the owner spills to and its completion flag)."""
+    dtype, what = None, "array"
 
-    def __init__(self, n_words, path=None, ready=None):
-        self.size, self.nbytes, self.path, self.ready, self._arr = int(n_words), 4 * int(n_words), path, ready, None
+    def __init__(self, n, path=None, ready=None):
+        self.size, self.nbytes, self.path, self.ready, self._arr = int(n), np.dtype(self.dtype).itemsize * int(n), path, ready, None
         self.event = None                    # owner process: set when the spill of this table is through (ingest.ChromosomeFeed)
 
     def attach(self, arr):
@@ -78,20 +82,21 @@ class LazyCigar:
         if self._arr is None:
             import time
             if self.path is None:
-                # the owner process itself reads the words (-t 1: the by-value comparison of duplicated records): the spill runs
-                # right behind the hand-over on a thread of its own -- wait for it (round 6: with the hand-over 10 ms earlier the
-                # first window's collection could get here first, and the window was skipped as "failed")
+                # the owner process itself reads the array (-t 1: the by-value comparison of duplicated records, the k-mer
+                # re-aligner's bases): the spill runs right behind the hand-over on a thread of its own -- wait for it (round 6:
+                # with the hand-over 10 ms earlier the first window's collection could get here first, and the window was skipped
+                # as "failed")
                 if self.event is not None:
                     self.event.wait(timeout=120)
                 if self._arr is not None:
                     return self._arr
-                raise RuntimeError("the CIGAR words of this table are on the device only")
+                raise RuntimeError("the %s of this table are on the device only" % self.what)
             t0 = time.time()
             while not os.path.exists(self.ready):              # the owner spills them right after the hand-over
                 if time.time() - t0 > 120:
-                    raise RuntimeError("the CIGAR spill %s never completed" % self.path)
+                    raise RuntimeError("the spill %s never completed" % self.path)
                 time.sleep(0.001)
-            self._arr = np.memmap(self.path, dtype=np.uint32, mode="r", shape=(self.size,)) if self.size else np.empty(0, np.uint32)
+            self._arr = np.memmap(self.path, dtype=self.dtype, mode="r", shape=(self.size,)) if self.size else np.empty(0, self.dtype)
         return self._arr
 
     def __getitem__(self, key):
@@ -103,6 +108,17 @@ class LazyCigar:
     def __array__(self, dtype=None, copy=None):
         a = self._get()
         return np.asarray(a, dtype) if dtype is not None else np.asarray(a)
+
+
+class LazyCigar(_LazyArray):
+    """Stand-in for ``AlignmentTable.cigar`` while the words exist on the device only."""
+    dtype, what = np.uint32, "CIGAR words"
+
+
+class LazySeq(_LazyArray):
+    """Stand-in for ``AlignmentTable.seq_packed`` (``with_seq``) while the bases exist on the device only: the 4-bit SEQ bytes
+    of every record, record i at byte ``seq_off[i]`` (AlignmentTable.query_sequence and subset take it as it is)."""
+    dtype, what = np.uint8, "read bases"
 
 
 def spill_cigar(table):
@@ -122,6 +138,55 @@ def spill_cigar(table):
     lazy.attach(host)
     if getattr(alloc, "dir", None) is not None:                # the flag the helper processes wait for (LazyCigar._get)
         with open(os.path.join(alloc.dir, "cigar.ready"), "w"):
+            pass
+
+
+SPILL_STAGE_BYTES = 8 << 20              # spill_seq: two pinned buffers of this size, whatever a group's bases come to (a third of its inflated bytes)
+_SPILL_STAGE = []                        # (pinned tensor, event of its last copy) x 2, per process: the spill thread is the only user
+
+
+def spill_seq(table):
+    """Owner process, off the critical path, behind :func:`spill_cigar`: the device bases of a table decoded ``with_seq`` ->
+    this process's memory (LazySeq.attach) and, with a shared-memory slot, ``seq_packed.bin`` + the flag ``seq.ready``.  The
+    copy goes through two pinned staging buffers of SPILL_STAGE_BYTES in turn -- the device-to-host copy of one chunk runs
+    while the chunk before is written -- on the current stream."""
+    d_seq, alloc, lazy = table._d_seq, table._alloc, table.seq_packed
+    n, slot = lazy.size, getattr(alloc, "dir", None)
+    host = np.empty(n, np.uint8) if hasattr(alloc, "put") else alloc("seq_packed", np.uint8, n)
+    f = None
+    if slot is not None and n:
+        path = os.path.join(slot, "seq_packed.bin")
+        f = open(path, "r+b" if os.path.exists(path) and os.path.getsize(path) >= n else "wb")
+    try:
+        while len(_SPILL_STAGE) < 2:
+            _SPILL_STAGE.append(torch.empty(SPILL_STAGE_BYTES, dtype=torch.uint8, pin_memory=True))
+        step = SPILL_STAGE_BYTES
+        chunks = [(at, min(step, n - at)) for at in range(0, n, step)]
+        events = [None, None]
+
+        def issue(i):
+            at, m = chunks[i]
+            _SPILL_STAGE[i % 2][:m].copy_(d_seq[at:at + m], non_blocking=True)
+            events[i % 2] = torch.cuda.Event()
+            events[i % 2].record()
+        if chunks:
+            issue(0)
+        for i, (at, m) in enumerate(chunks):
+            if i + 1 < len(chunks):
+                issue(i + 1)
+            events[i % 2].synchronize()
+            part = _SPILL_STAGE[i % 2].numpy()[:m]
+            host[at:at + m] = part
+            if f is not None:
+                f.write(part)
+    finally:
+        if f is not None:
+            f.close()
+    if hasattr(host, "flush"):
+        host.flush()
+    lazy.attach(host)
+    if slot is not None:                                        # the flag the helper processes wait for (LazySeq._get)
+        with open(os.path.join(slot, "seq.ready"), "w"):
             pass
 
 
@@ -234,11 +299,12 @@ def _record_starts(coff, dst, lo, hi, linear):
     return np.unique(np.where(at_end, dst[nb], dst[idx] + (voffs & np.uint64(0xFFFF))))
 
 
-def _pack_layout(n, name_bytes):
+def _pack_layout(n, name_bytes, with_seq=False):
     """-> (offs, size): the packed arrays of ``n`` records, everything the host wants of them, as sections of one buffer --
-    [cig_off n+1][name_off n+1][tid n][pos n][l_seq n][flag n][mapq n][names] (8, 8, 4, 4, 4, 2, 1, 1 bytes an element) --,
+    [cig_off n+1][name_off n+1][tid n][pos n][l_seq n][flag n][mapq n][names] (8, 8, 4, 4, 4, 2, 1, 1 bytes an element) and,
+    ``with_seq``, [seq_off n+1] (8) behind them (small: it goes with the hand-over; the bases themselves do not) --,
     section k at ``offs[k]``, each padded to 16 bytes, 16 more at the end and ``size`` a multiple of 256."""
-    sect = [8 * (n + 1), 8 * (n + 1), 4 * n, 4 * n, 4 * n, 2 * n, n, name_bytes]
+    sect = [8 * (n + 1), 8 * (n + 1), 4 * n, 4 * n, 4 * n, 2 * n, n, name_bytes] + ([8 * (n + 1)] if with_seq else [])
     offs = np.zeros(len(sect) + 1, np.int64)
     offs[1:] = np.cumsum([(v + 15) // 16 * 16 for v in sect])
     return offs, (int(offs[-1]) + 16 + 255) // 256 * 256
@@ -250,11 +316,12 @@ def _section(d_pack, offs, k, dtype, count):
 
 
 class DeviceDecoder:
-    def __init__(self, path, index, references, lengths, header_text, device, threads=8, alloc_for=None):
+    def __init__(self, path, index, references, lengths, header_text, device, threads=8, alloc_for=None, with_seq=False):
         self._t0, self.trace = time.perf_counter(), []          # (seconds since construction, what) of the first events (SVX_TIMING)
         self.path, self.references, self.lengths, self.header_text = path, list(references), list(lengths), header_text
         self.device, self.threads = torch.device(device), max(1, int(threads))
         self.alloc_for = alloc_for                               # callable() -> alloc(name, dtype, n) of the next part (shared memory)
+        self.with_seq = bool(with_seq)                           # the walk also packs the read bases (svx_bam_walk_*_seq): tables with seq_off + a LazySeq
         self.lib = _lib.load()
         self.spans = read_bai_linear(index)
         self.size = os.path.getsize(path)
@@ -429,11 +496,12 @@ class DeviceDecoder:
         inflated once (the group's bytes are one range of the file), across a group boundary twice (~2 % of a group)."""
         yield from _Pipeline(self, units, depth).run()
 
-    def _make_finish(self, hp, n, words, name_bytes, d_cigar):
+    def _make_finish(self, hp, n, words, name_bytes, d_cigar, seq_bytes=None, d_seq=None):
         """The host side of one device-decoded chromosome: packed read-back ``hp`` (:func:`_pack_layout`) -> shared-memory
-        arrays, QNAME ids, table."""
+        arrays, QNAME ids, table.  ``seq_bytes`` / ``d_seq`` (``with_seq``): the table gets its ``seq_off`` and a LazySeq over
+        the bases, which are still on the device (``table._d_seq``: :func:`spill_seq`)."""
         lib = self.lib
-        offs, _size = _pack_layout(n, name_bytes)
+        offs, _size = _pack_layout(n, name_bytes, seq_bytes is not None)
 
         def sect(k, dtype, count):
             return hp[int(offs[k]):int(offs[k]) + count * np.dtype(dtype).itemsize].view(dtype)
@@ -456,6 +524,7 @@ class DeviceDecoder:
             tid_h, pos_h, l_seq_h = keep("tid", np.int32, sect(2, np.int32, n)), keep("pos", np.int32, sect(3, np.int32, n)), keep("l_seq", np.int32, sect(4, np.int32, n))
             flag_h, mapq_h = keep("flag", np.uint16, sect(5, np.uint16, n)), keep("mapq", np.uint8, sect(6, np.uint8, n))
             names_h = np.ascontiguousarray(sect(7, np.uint8, name_bytes))
+            seq_off_h = keep("seq_off", np.int64, sect(8, np.int64, n + 1)[:n]) if seq_bytes is not None else None      # (n entries, as the host decoder's)
             name_id = np.empty(n, np.int32) if put is not None else alloc("name_id", np.int32, n)
             uniq = np.empty(max(name_bytes, 1), np.uint8)
             ub = np.zeros(1, np.uint64)
@@ -482,6 +551,8 @@ class DeviceDecoder:
             table._alloc = alloc
             table._shm_dir = getattr(alloc, "dir", None)
             table._d_cigar = d_cigar
+            if seq_bytes is not None:
+                table.seq_packed, table.seq_off, table._d_seq = LazySeq(seq_bytes), seq_off_h, d_seq
             return table
         return finish
 
@@ -491,7 +562,7 @@ class _Group:
     (reader thread), completed by :meth:`_Pipeline.launch` (driver thread: ``d_raw`` and everything behind it); the device
     buffers are dropped as soon as the last step that reads them is through."""
     __slots__ = ("units", "d_comp", "copied", "nbytes", "n_blocks", "inflated_bytes", "tab", "start_at", "n_starts",
-                 "d_raw", "d_tab", "d_counts", "event", "stream")
+                 "d_raw", "d_tab", "d_counts", "event", "stream")      # (d_counts, with_seq: the counts and, behind them, the SEQ bytes per start)
 
     def __init__(self, units, d_comp, copied, nbytes, n_blocks, inflated_bytes, tab, start_at, n_starts):
         self.units, self.d_comp, self.copied, self.nbytes, self.n_blocks, self.inflated_bytes = units, d_comp, copied, nbytes, n_blocks, inflated_bytes
@@ -505,13 +576,14 @@ class _Packed:
     words, ``name_bytes``), its place in the buffers (``pack_at`` + ``size`` bytes laid out by ``offs``, ``word_at``) and, once
     its extraction is enqueued, what the consumer gets (``event``, ``h_pack``, ``d_cigar``, ``d_cig_off``, ``d_pos``)."""
     __slots__ = ("unit", "at", "n_starts", "row", "n", "words", "name_bytes", "offs", "pack_at", "size", "word_at",
-                 "event", "h_pack", "d_cigar", "d_cig_off", "d_pos")
+                 "event", "h_pack", "d_cigar", "d_cig_off", "d_pos", "seq_bytes", "seq_at", "d_seq")
 
-    def __init__(self, unit, at, n_starts, row, n, words, name_bytes, pack_at, word_at):
+    def __init__(self, unit, at, n_starts, row, n, words, name_bytes, pack_at, word_at, seq_bytes=None, seq_at=0):
         self.unit, self.at, self.n_starts, self.row, self.n, self.words, self.name_bytes = unit, at, n_starts, row, n, words, name_bytes
-        self.offs, self.size = _pack_layout(n, name_bytes)
+        self.seq_bytes, self.seq_at = seq_bytes, seq_at          # with_seq: the SEQ bytes of the unit's records, their place in the group's buffer of bases
+        self.offs, self.size = _pack_layout(n, name_bytes, seq_bytes is not None)
         self.pack_at, self.word_at = pack_at, word_at
-        self.event = self.h_pack = self.d_cigar = self.d_cig_off = self.d_pos = None
+        self.event = self.h_pack = self.d_cigar = self.d_cig_off = self.d_pos = self.d_seq = None
 
 
 class _StagingRing:
@@ -702,7 +774,8 @@ class _Pipeline:
         # hipMalloc'ed fresh -- 0.2 ms per GB on most boxes, 15 ms per GB on some: a 0.24 s stall in front of the
         # largest group's launch (two of nine bench runs).
         variant = kernels.inflate_variant_for(nb)
-        d_raw = torch.empty(max(g.inflated_bytes, 16), dtype=torch.uint8, device=dev)
+        # (readable up to the next multiple of 16 behind its last byte: the walk's aligned loads, include/svx.h)
+        d_raw = torch.empty((max(g.inflated_bytes, 1) + 15) // 16 * 16, dtype=torch.uint8, device=dev)
         d_ws = kernels.inflate_workspace(lib, variant, g.inflated_bytes, nb, dev)
         # (the allocator may hand out a block that default-stream work freed and is still using: the group's streams
         # order themselves behind whatever the default stream holds at this point -- normally nothing)
@@ -735,12 +808,20 @@ class _Pipeline:
                 _lib.check(lib.svx_bgzf_crc32(d_raw.data_ptr(), d_tab[2 * nb:].data_ptr(), d_comp.data_ptr(), d_tab.data_ptr(), d_len.data_ptr(), nb,
                                               d_status.data_ptr(), st), "svx_bgzf_crc32")
             total_starts = sum(g.n_starts)
-            d_counts = torch.empty((total_starts + 1, 4), dtype=torch.int64, device=dev)
+            with_seq = self.dec.with_seq
+            # (with_seq: the SEQ bytes per start lie behind the counts, in the same buffer -- the group's ONE read-back stays one)
+            d_flat = torch.empty(4 * (total_starts + 1) + (total_starts if with_seq else 0), dtype=torch.int64, device=dev)
+            d_counts = d_flat[:4 * (total_starts + 1)].view(total_starts + 1, 4)
             row = 0
             for at, n in zip(g.start_at, g.n_starts):
-                _lib.check(lib.svx_bam_walk_count(d_raw.data_ptr(), d_tab[at:].data_ptr(), n, d_counts[row:].data_ptr(), st), "svx_bam_walk_count")
+                if with_seq:
+                    _lib.check(lib.svx_bam_walk_count_seq(d_raw.data_ptr(), d_tab[at:].data_ptr(), n, d_counts[row:].data_ptr(),
+                                                          d_flat[4 * (total_starts + 1) + row:].data_ptr(), st), "svx_bam_walk_count_seq")
+                else:
+                    _lib.check(lib.svx_bam_walk_count(d_raw.data_ptr(), d_tab[at:].data_ptr(), n, d_counts[row:].data_ptr(), st), "svx_bam_walk_count")
                 row += n
             d_counts[total_starts, 0] = d_status.max()
+            d_counts = d_flat
             # NO read-back is enqueued here.  A device-to-host copy goes to a DMA engine's queue at once, with a wait for
             # the kernels in front of it -- and the engine serves its queue in order: the counts' copy sat there for the
             # whole inflate (40-120 ms) and every other read-back of the process (the previous group's packed arrays,
@@ -763,13 +844,15 @@ class _Pipeline:
         g.d_comp = None
         self.stats["h2d_inflate_s"] += time.perf_counter() - t0
         d_counts, g.d_counts = g.d_counts, None
+        with_seq, total_starts = self.dec.with_seq, sum(g.n_starts)
         h_counts = torch.empty(tuple(d_counts.shape), dtype=torch.int64, pin_memory=True)
         with torch.cuda.stream(stream):
             h_counts.copy_(d_counts, non_blocking=True)
             ev_c = torch.cuda.Event()
             ev_c.record()
         ev_c.synchronize()
-        counts = h_counts.numpy()
+        counts = h_counts.numpy()[:4 * (total_starts + 1)].reshape(total_starts + 1, 4)
+        seq_counts = h_counts.numpy()[4 * (total_starts + 1):]      # (with_seq: SEQ bytes per start)
         if int(counts[-1, 0]) != 0:
             raise DeviceIngestError("corrupt BGZF blocks in %s" % g.units, sorted({u.tid for u in g.units}))
         d_raw, d_tab = g.d_raw, g.d_tab
@@ -778,7 +861,7 @@ class _Pipeline:
         # (and one device buffer for their CIGAR words): every first-time hipMalloc / hipHostMalloc of a run costs
         # milliseconds during which the other threads' HIP calls -- and their page faults -- wait; per chromosome that
         # was six of them.
-        packed, row, pack_at, word_at = [], 0, 0, 0
+        packed, row, pack_at, word_at, seq_at = [], 0, 0, 0, 0
         for unit, at, n_starts in zip(g.units, g.start_at, g.n_starts):
             c = counts[row:row + n_starts]
             bad = c[:, 3] != 0
@@ -786,17 +869,26 @@ class _Pipeline:
                 code = int(c[bad, 3][0])
                 raise DeviceIngestError({1: "the linear index does not match the records", 2: "malformed BAM record"}.get(code, "walk error %d" % code), [unit.tid])
             n, words, name_bytes = (int(v) for v in c[:, :3].sum(axis=0)) if n_starts else (0, 0, 0)
-            p = _Packed(unit, at, n_starts, row, n, words, name_bytes, pack_at, word_at)
+            seq_bytes = int(seq_counts[row:row + n_starts].sum()) if with_seq else None
+            p = _Packed(unit, at, n_starts, row, n, words, name_bytes, pack_at, word_at, seq_bytes, seq_at)
             packed.append(p)
             pack_at += p.size
+            if with_seq:
+                seq_at += (max(seq_bytes, 1) + 255) // 256 * 256
             word_at += (max(words, 1) + 63) // 64 * 64           # (svx_cigar_scan reads 16-byte quads: every chromosome starts aligned)
             row += n_starts
-        base_all = torch.zeros((max(row, 1), 3), dtype=torch.int64, pin_memory=True)
+        rows = max(row, 1)
+        base_flat = torch.zeros(3 * rows + (rows if with_seq else 0), dtype=torch.int64, pin_memory=True)      # (with_seq: the fourth base, behind the three)
+        base_all, seq_base_all = base_flat.numpy()[:3 * rows].reshape(rows, 3), base_flat.numpy()[3 * rows:]
         for p in packed:
             if p.n_starts > 1:
-                base_all.numpy()[p.row + 1:p.row + p.n_starts] = np.cumsum(counts[p.row:p.row + p.n_starts - 1, :3], axis=0)
+                base_all[p.row + 1:p.row + p.n_starts] = np.cumsum(counts[p.row:p.row + p.n_starts - 1, :3], axis=0)
+                if with_seq:
+                    seq_base_all[p.row + 1:p.row + p.n_starts] = np.cumsum(seq_counts[p.row:p.row + p.n_starts - 1])
         d_pack_all = torch.empty(max(pack_at, 256), dtype=torch.uint8, device=dev)        # (default stream: see launch())
         d_cigar_all = torch.empty(max(word_at, 64), dtype=torch.int32, device=dev)
+        # the group's bases: they stay here until the spill thread has copied them out (table._d_seq), never in the read-back below
+        d_seq_all = torch.empty(max(seq_at, 256), dtype=torch.uint8, device=dev) if with_seq else None
         allocated = torch.cuda.Event()
         allocated.record(torch.cuda.default_stream(dev))
         with torch.cuda.stream(stream):
@@ -804,7 +896,10 @@ class _Pipeline:
             st = kernels._stream_ptr(dev)
             d_pack_all.record_stream(stream)
             d_cigar_all.record_stream(stream)
-            d_base_all = base_all.to(dev, non_blocking=True)
+            if with_seq:
+                d_seq_all.record_stream(stream)
+            d_base_flat = base_flat.to(dev, non_blocking=True)
+            d_base_all = d_base_flat[:3 * rows].view(rows, 3)
             h_pack_all = torch.empty(max(pack_at, 256), dtype=torch.uint8, pin_memory=True)
             for p in packed:
                 if p.n == 0:                                     # a slice (or a reference) without a record: nothing to extract
@@ -817,9 +912,17 @@ class _Pipeline:
                 d_flag, d_mapq = _section(d_pack, p.offs, 5, torch.int16, n), _section(d_pack, p.offs, 6, torch.uint8, n)
                 d_names = _section(d_pack, p.offs, 7, torch.uint8, max(p.name_bytes, 1))
                 d_cigar = d_cigar_all[p.word_at:p.word_at + max(p.words, 1)]
-                _lib.check(lib.svx_bam_walk_extract(d_raw.data_ptr(), d_tab[p.at:].data_ptr(), p.n_starts, d_base.data_ptr(), d_tid.data_ptr(),
-                                                    d_pos.data_ptr(), d_flag.data_ptr(), d_mapq.data_ptr(), d_lseq.data_ptr(), d_cig_off.data_ptr(),
-                                                    d_cigar.data_ptr(), d_name_off.data_ptr(), d_names.data_ptr(), n, st), "svx_bam_walk_extract")
+                if with_seq:
+                    p.d_seq = d_seq_all[p.seq_at:p.seq_at + max(p.seq_bytes, 1)]
+                    _lib.check(lib.svx_bam_walk_extract_seq(d_raw.data_ptr(), d_tab[p.at:].data_ptr(), p.n_starts, d_base.data_ptr(), d_tid.data_ptr(),
+                                                            d_pos.data_ptr(), d_flag.data_ptr(), d_mapq.data_ptr(), d_lseq.data_ptr(), d_cig_off.data_ptr(),
+                                                            d_cigar.data_ptr(), d_name_off.data_ptr(), d_names.data_ptr(),
+                                                            d_base_flat[3 * rows + p.row:].data_ptr(), _section(d_pack, p.offs, 8, torch.int64, n + 1).data_ptr(),
+                                                            p.d_seq.data_ptr(), n, st), "svx_bam_walk_extract_seq")
+                else:
+                    _lib.check(lib.svx_bam_walk_extract(d_raw.data_ptr(), d_tab[p.at:].data_ptr(), p.n_starts, d_base.data_ptr(), d_tid.data_ptr(),
+                                                        d_pos.data_ptr(), d_flag.data_ptr(), d_mapq.data_ptr(), d_lseq.data_ptr(), d_cig_off.data_ptr(),
+                                                        d_cigar.data_ptr(), d_name_off.data_ptr(), d_names.data_ptr(), n, st), "svx_bam_walk_extract")
                 p.h_pack = h_pack_all[p.pack_at:p.pack_at + p.size]
                 p.h_pack.copy_(d_pack, non_blocking=True)
                 # svx_cigar_scan reads the offsets and positions where they are: views of the group's pack buffer, which
@@ -840,7 +943,7 @@ class _Pipeline:
             p.event.synchronize()
             self.stats["d2h_s"] += time.perf_counter() - t0
             self.mark("packed read-back done")
-            yield p.unit, self.dec._make_finish(p.h_pack.numpy(), p.n, p.words, p.name_bytes, p.d_cigar), (p.d_cigar, p.d_cig_off, p.d_pos)
+            yield p.unit, self.dec._make_finish(p.h_pack.numpy(), p.n, p.words, p.name_bytes, p.d_cigar, p.seq_bytes, p.d_seq), (p.d_cigar, p.d_cig_off, p.d_pos)
         g.d_raw = g.d_tab = None
 
     def pump(self, block):

@@ -131,7 +131,10 @@ class AlignmentTable:
         if n == 0 or self.seq_packed is None:
             return None
         o = int(self.seq_off[i])
-        raw = np.frombuffer(self.seq_packed, np.uint8, (n + 1) // 2, o)
+        packed = self.seq_packed
+        if hasattr(packed, "_get"):                        # ingest_gpu.LazySeq: the bases follow the hand-over (waits for the spill)
+            packed = packed._get()
+        raw = np.frombuffer(packed, np.uint8, (n + 1) // 2, o)
         codes = np.empty(2 * raw.size, np.uint8)
         codes[0::2] = raw >> 4
         codes[1::2] = raw & 15
