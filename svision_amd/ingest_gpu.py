@@ -80,7 +80,6 @@ class _LazyArray:
 
     def _get(self):
         if self._arr is None:
-            import time
             if self.path is None:
                 # the owner process itself reads the array (-t 1: the by-value comparison of duplicated records, the k-mer
                 # re-aligner's bases): the spill runs right behind the hand-over on a thread of its own -- wait for it (round 6:
@@ -121,24 +120,30 @@ class LazySeq(_LazyArray):
     dtype, what = np.uint8, "read bases"
 
 
+class _PrivateSlot:
+    """The private-memory twin of a shared-memory slot (ingest._Slot) for a decoder that serves no helper processes
+    (``DeviceDecoder(take_slot=None)``): ``put`` keeps the array, nothing is written and no flag is set."""
+    dir = None
+
+    def put(self, _name, src):
+        return np.ascontiguousarray(src).reshape(-1)
+
+    def open_for(self, _name, _nbytes):
+        return open(os.devnull, "wb")
+
+    def mark(self, _flag):
+        pass
+
+
 def spill_cigar(table):
-    """Owner process, off the critical path: the device CIGAR words of a device-decoded table -> its shared-memory slot."""
-    d_cigar, alloc, lazy = table._d_cigar, table._alloc, table.cigar
-    if hasattr(alloc, "put"):                                   # a shared-memory slot: read back into private memory, then written to the file
-        host = np.empty(lazy.size, np.uint32)
-        if lazy.size:
-            torch.from_numpy(host.view(np.int32)).copy_(d_cigar[:lazy.size])
-        alloc.put("cigar", host)
-    else:
-        host = alloc("cigar", np.uint32, lazy.size)
-        if lazy.size:
-            torch.from_numpy(host.view(np.int32)).copy_(d_cigar[:lazy.size])
-            if hasattr(host, "flush"):
-                host.flush()
-    lazy.attach(host)
-    if getattr(alloc, "dir", None) is not None:                # the flag the helper processes wait for (LazyCigar._get)
-        with open(os.path.join(alloc.dir, "cigar.ready"), "w"):
-            pass
+    """Owner process, off the critical path: the device CIGAR words of a device-decoded table -> this process's memory
+    (LazyCigar.attach) and the table's slot; the file first, the flag the helper processes wait for (LazyCigar._get) behind it."""
+    d_cigar, slot, lazy = table._d_cigar, table._slot, table.cigar
+    host = np.empty(lazy.size, np.uint32)
+    if lazy.size:
+        torch.from_numpy(host.view(np.int32)).copy_(d_cigar[:lazy.size])
+    lazy.attach(slot.put("cigar", host))
+    slot.mark("cigar.ready")
 
 
 SPILL_STAGE_BYTES = 8 << 20              # spill_seq: two pinned buffers of this size, whatever a group's bases come to (a third of its inflated bytes)
@@ -147,47 +152,34 @@ _SPILL_STAGE = []                        # (pinned tensor, event of its last cop
 
 def spill_seq(table):
     """Owner process, off the critical path, behind :func:`spill_cigar`: the device bases of a table decoded ``with_seq`` ->
-    this process's memory (LazySeq.attach) and, with a shared-memory slot, ``seq_packed.bin`` + the flag ``seq.ready``.  The
-    copy goes through two pinned staging buffers of SPILL_STAGE_BYTES in turn -- the device-to-host copy of one chunk runs
-    while the chunk before is written -- on the current stream."""
-    d_seq, alloc, lazy = table._d_seq, table._alloc, table.seq_packed
-    n, slot = lazy.size, getattr(alloc, "dir", None)
-    host = np.empty(n, np.uint8) if hasattr(alloc, "put") else alloc("seq_packed", np.uint8, n)
-    f = None
-    if slot is not None and n:
-        path = os.path.join(slot, "seq_packed.bin")
-        f = open(path, "r+b" if os.path.exists(path) and os.path.getsize(path) >= n else "wb")
-    try:
-        while len(_SPILL_STAGE) < 2:
-            _SPILL_STAGE.append(torch.empty(SPILL_STAGE_BYTES, dtype=torch.uint8, pin_memory=True))
-        step = SPILL_STAGE_BYTES
-        chunks = [(at, min(step, n - at)) for at in range(0, n, step)]
-        events = [None, None]
+    this process's memory (LazySeq.attach) and the slot's ``seq_packed.bin`` + the flag ``seq.ready``.  The copy goes
+    through two pinned staging buffers of SPILL_STAGE_BYTES in turn -- the device-to-host copy of one chunk runs while the
+    chunk before is written -- on the current stream."""
+    d_seq, slot, lazy = table._d_seq, table._slot, table.seq_packed
+    n = lazy.size
+    host = np.empty(n, np.uint8)
+    while len(_SPILL_STAGE) < 2:
+        _SPILL_STAGE.append(torch.empty(SPILL_STAGE_BYTES, dtype=torch.uint8, pin_memory=True))
+    chunks = [(at, min(SPILL_STAGE_BYTES, n - at)) for at in range(0, n, SPILL_STAGE_BYTES)]
+    events = [None, None]
 
-        def issue(i):
-            at, m = chunks[i]
-            _SPILL_STAGE[i % 2][:m].copy_(d_seq[at:at + m], non_blocking=True)
-            events[i % 2] = torch.cuda.Event()
-            events[i % 2].record()
-        if chunks:
-            issue(0)
-        for i, (at, m) in enumerate(chunks):
-            if i + 1 < len(chunks):
-                issue(i + 1)
-            events[i % 2].synchronize()
-            part = _SPILL_STAGE[i % 2].numpy()[:m]
-            host[at:at + m] = part
-            if f is not None:
+    def issue(i):
+        at, m = chunks[i]
+        _SPILL_STAGE[i % 2][:m].copy_(d_seq[at:at + m], non_blocking=True)
+        events[i % 2] = torch.cuda.Event()
+        events[i % 2].record()
+    if chunks:
+        issue(0)
+        with slot.open_for("seq_packed", n) as f:
+            for i, (at, m) in enumerate(chunks):
+                if i + 1 < len(chunks):
+                    issue(i + 1)
+                events[i % 2].synchronize()
+                part = _SPILL_STAGE[i % 2].numpy()[:m]
+                host[at:at + m] = part
                 f.write(part)
-    finally:
-        if f is not None:
-            f.close()
-    if hasattr(host, "flush"):
-        host.flush()
     lazy.attach(host)
-    if slot is not None:                                        # the flag the helper processes wait for (LazySeq._get)
-        with open(os.path.join(slot, "seq.ready"), "w"):
-            pass
+    slot.mark("seq.ready")                                      # the flag the helper processes wait for (LazySeq._get)
 
 
 class Unit:
@@ -207,14 +199,6 @@ class Unit:
     def __repr__(self):
         return "Unit(tid %d, [%d, %d)%s%s)" % (self.tid, self.lo, self.hi, "" if self.left_edge is None else ", records from %d" % self.left_edge,
                                                  "" if self.to_end else ", cut")
-
-
-class MarginError(RuntimeError):
-    """A slice turned out not to hold every record its windows can touch: ``needed`` = the reach its own records have."""
-
-    def __init__(self, unit, needed):
-        super().__init__("%r: its records reach %d bases, more than the margin it was cut with" % (unit, needed))
-        self.unit, self.needed = unit, int(needed)
 
 
 def voff_at(span, coord):
@@ -316,11 +300,11 @@ def _section(d_pack, offs, k, dtype, count):
 
 
 class DeviceDecoder:
-    def __init__(self, path, index, references, lengths, header_text, device, threads=8, alloc_for=None, with_seq=False):
+    def __init__(self, path, index, references, lengths, header_text, device, threads=8, take_slot=None, with_seq=False):
         self._t0, self.trace = time.perf_counter(), []          # (seconds since construction, what) of the first events (SVX_TIMING)
         self.path, self.references, self.lengths, self.header_text = path, list(references), list(lengths), header_text
         self.device, self.threads = torch.device(device), max(1, int(threads))
-        self.alloc_for = alloc_for                               # callable() -> alloc(name, dtype, n) of the next part (shared memory)
+        self.take_slot = take_slot or _PrivateSlot               # callable() -> the slot of the next part (ingest._SlotPool.take: shared memory)
         self.with_seq = bool(with_seq)                           # the walk also packs the read bases (svx_bam_walk_*_seq): tables with seq_off + a LazySeq
         self.lib = _lib.load()
         self.spans = read_bai_linear(index)
@@ -350,7 +334,7 @@ class DeviceDecoder:
         records from the linear-index entry of ``start - margin`` to that of ``end + margin``: a real 30x chromosome is 3 GB
         of file, and its first window should not wait for all of it (the reference fetches window by window,
         run_collection.py:23-26).  ``margin`` is a guess (:meth:`estimate_reach`); the consumer checks every slice against the
-        reach of its own records (ingest.ChromosomeFeed: MarginError -> planned again with a larger one).  ``resume`` = (tid,
+        reach of its own records (ingest.ChromosomeFeed._reject -> planned again with a larger one).  ``resume`` = (tid,
         coordinate): leave out that reference's windows in front of the coordinate and every reference in front of it."""
         margin = int(margin if margin is not None else self.estimate_reach(tids))
         slice_bytes = int(slice_bytes or int(os.environ.get("SVX_SLICE_BYTES", "0")) or SLICE_BYTES)      # (the variable: experiments, tests)
@@ -508,24 +492,16 @@ class DeviceDecoder:
 
         def finish():
             t0 = time.perf_counter()
-            alloc = self.alloc_for() if self.alloc_for is not None else (lambda _name, dtype, k: np.empty(k, dtype))
+            slot = self.take_slot()
 
-            put = getattr(alloc, "put", None)                   # a shared-memory slot (ingest._slot_alloc): arrays are written to its files
-
-            def keep(name, dtype, src):
-                if put is not None:
-                    return put(name, np.asarray(src, dtype))        # (a view of the group's pinned read-back buffer, which lives as long as its views)
-                out = alloc(name, dtype, src.size)
-                if src.size:
-                    out[:] = src
-                return out
-            cig_off_h = keep("cig_off", np.int64, sect(0, np.int64, n + 1))
+            # (what goes into the slot: views of the group's pinned read-back buffer, which lives as long as its views)
+            cig_off_h = slot.put("cig_off", sect(0, np.int64, n + 1))
             name_off_h = sect(1, np.int64, n + 1)
-            tid_h, pos_h, l_seq_h = keep("tid", np.int32, sect(2, np.int32, n)), keep("pos", np.int32, sect(3, np.int32, n)), keep("l_seq", np.int32, sect(4, np.int32, n))
-            flag_h, mapq_h = keep("flag", np.uint16, sect(5, np.uint16, n)), keep("mapq", np.uint8, sect(6, np.uint8, n))
+            tid_h, pos_h, l_seq_h = slot.put("tid", sect(2, np.int32, n)), slot.put("pos", sect(3, np.int32, n)), slot.put("l_seq", sect(4, np.int32, n))
+            flag_h, mapq_h = slot.put("flag", sect(5, np.uint16, n)), slot.put("mapq", sect(6, np.uint8, n))
             names_h = np.ascontiguousarray(sect(7, np.uint8, name_bytes))
-            seq_off_h = keep("seq_off", np.int64, sect(8, np.int64, n + 1)[:n]) if seq_bytes is not None else None      # (n entries, as the host decoder's)
-            name_id = np.empty(n, np.int32) if put is not None else alloc("name_id", np.int32, n)
+            seq_off_h = slot.put("seq_off", sect(8, np.int64, n + 1)[:n]) if seq_bytes is not None else None      # (n entries, as the host decoder's)
+            name_id = np.empty(n, np.int32)
             uniq = np.empty(max(name_bytes, 1), np.uint8)
             ub = np.zeros(1, np.uint64)
             name_off_c = np.ascontiguousarray(name_off_h)
@@ -534,12 +510,8 @@ class DeviceDecoder:
             n_unique = int(lib.svx_name_ids(names_h.ctypes.data, name_off_c.ctypes.data, n, name_id.ctypes.data, uniq.ctypes.data, ub.ctypes.data))
             t2 = time.perf_counter()
             self.stats["finish_ids_s"] = self.stats.get("finish_ids_s", 0.0) + (t2 - t1)
-            if put is not None:
-                put("name_id", name_id)
-                blob = put("names", uniq[:int(ub[0])].copy())
-            else:
-                blob = alloc("names", np.uint8, int(ub[0]))
-                blob[:] = uniq[:int(ub[0])]
+            slot.put("name_id", name_id)
+            blob = slot.put("names", uniq[:int(ub[0])].copy())
             name_list = blob.tobytes().decode().split("\n")[:-1] if n_unique else []
             self.stats["finish_list_s"] = self.stats.get("finish_list_s", 0.0) + (time.perf_counter() - t2)
             self.stats["names_s"] += time.perf_counter() - t0
@@ -547,9 +519,7 @@ class DeviceDecoder:
             table = AlignmentTable(self.references, self.lengths, tid_h, pos_h, flag_h, mapq_h, l_seq_h, name_id, name_list, np.empty(0, np.uint32),
                                    cig_off_h, self.header_text)
             table.cigar = LazyCigar(words)
-            table._names_blob = blob
-            table._alloc = alloc
-            table._shm_dir = getattr(alloc, "dir", None)
+            table._slot = slot                                  # travels with the table: spill_cigar / spill_seq write to it
             table._d_cigar = d_cigar
             if seq_bytes is not None:
                 table.seq_packed, table.seq_off, table._d_seq = LazySeq(seq_bytes), seq_off_h, d_seq

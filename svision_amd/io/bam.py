@@ -286,30 +286,26 @@ def read_bai(path):
     return out
 
 
-def _table_from_handle(lib, h, with_seq, threads=0, alloc=None):
-    """A decoded handle (svx_bam_open / svx_bam_stream_next) -> AlignmentTable; the handle is closed.
-    ``alloc(name, dtype, n)``: where the big arrays are created (a shared-memory file for the host helpers)."""
+def _table_from_handle(lib, h, with_seq, threads=0):
+    """A decoded handle (svx_bam_open / svx_bam_stream_next) -> AlignmentTable; the handle is closed."""
     import ctypes
-    if alloc is None:
-        def alloc(_name, dtype, n):
-            return np.empty(n, dtype)
     try:
         sizes = np.zeros(8, np.uint64)
         lib.svx_bam_sizes(h, sizes.ctypes.data)
         n, nc, nref, _nn, nb, hb, rb, rawb = (int(v) for v in sizes)
-        tid, pos, l_seq, name_id = (alloc(k, np.int32, n) for k in ("tid", "pos", "l_seq", "name_id"))
-        flag, mapq = alloc("flag", np.uint16, n), alloc("mapq", np.uint8, n)
-        cig_off, cigar = alloc("cig_off", np.int64, n + 1), alloc("cigar", np.uint32, nc)
-        names, header, ref_names = alloc("names", np.uint8, nb), np.empty(hb, np.uint8), np.empty(rb, np.uint8)
+        tid, pos, l_seq, name_id = (np.empty(n, np.int32) for _ in range(4))
+        flag, mapq = np.empty(n, np.uint16), np.empty(n, np.uint8)
+        cig_off, cigar = np.empty(n + 1, np.int64), np.empty(nc, np.uint32)
+        names, header, ref_names = np.empty(nb, np.uint8), np.empty(hb, np.uint8), np.empty(rb, np.uint8)
         ref_lens = np.empty(nref, np.int32)
-        seq_off = alloc("seq_off", np.int64, n) if with_seq else None
+        seq_off = np.empty(n, np.int64) if with_seq else None
         lib.svx_bam_export(h, int(threads), tid.ctypes.data, pos.ctypes.data, flag.ctypes.data, mapq.ctypes.data,
                            l_seq.ctypes.data, name_id.ctypes.data, cig_off.ctypes.data, cigar.ctypes.data, names.ctypes.data,
                            header.ctypes.data, ref_names.ctypes.data, ref_lens.ctypes.data,
                            seq_off.ctypes.data if with_seq else None)
         seq_packed = None
         if with_seq:
-            seq_packed = alloc("seq_packed", np.uint8, rawb)
+            seq_packed = np.empty(rawb, np.uint8)
             if rawb:
                 ctypes.memmove(seq_packed.ctypes.data, lib.svx_bam_seq(h), rawb)
     finally:
@@ -318,7 +314,7 @@ def _table_from_handle(lib, h, with_seq, threads=0, alloc=None):
     refs = ref_names.tobytes().decode().split("\n")[:-1] if rb else []
     table = AlignmentTable(refs, [int(v) for v in ref_lens], tid, pos, flag, mapq, l_seq, name_id, name_list, cigar, cig_off,
                            header.tobytes().decode(), seq_packed, seq_off)
-    table._names_blob = names                                  # the '\n'-joined QNAMEs as they were exported (shared with the helpers)
+    table._names_blob = names                                  # the '\n'-joined QNAMEs as they were exported (ingest.put_table: shared with the helpers)
     return table
 
 
@@ -409,10 +405,10 @@ class BamStream:
 
     What the reference does window by window through pysam's ``fetch`` (run_collection.py:23-26)."""
 
-    def __init__(self, path, with_seq=False, threads=0, tids=None, index=None, alloc=None):
+    def __init__(self, path, with_seq=False, threads=0, tids=None, index=None):
         from .. import _lib
         self.lib = _lib.load()
-        self.path, self.with_seq, self.alloc = path, with_seq, alloc
+        self.path, self.with_seq = path, with_seq
         self.keep = None if tids is None else set(int(t) for t in tids)
         voffs = np.zeros(0, np.uint64)
         if tids is not None and index is None:
@@ -444,7 +440,7 @@ class BamStream:
                 if err is not None:
                     raise ValueError("%s: %s" % (self.path, err))
                 raise StopIteration
-            table = _table_from_handle(self.lib, part, self.with_seq, alloc=self.alloc)
+            table = _table_from_handle(self.lib, part, self.with_seq)
             if len(table) and (self.keep is None or int(table.tid[0]) in self.keep):
                 return table
 

@@ -69,34 +69,34 @@ def test_effective_cpus_reads_the_cgroup_quota(tmp_path, monkeypatch):
 
 
 def test_shared_memory_slots_are_recycled_in_place(tmp_path):
-    """ChromosomeFeed's slot allocator: a released slot's files are overwritten in place (no new pages) when they are large
-    enough, re-created when they are not, and what a helper maps is what was written."""
+    """ChromosomeFeed's slots (ingest._SlotPool, _Slot.put): a released slot's files are overwritten in place (no new pages)
+    when they are large enough, re-created when they are not, and what a helper maps is what was written."""
     from svision_amd import ingest
-    feed = ingest.ChromosomeFeed.__new__(ingest.ChromosomeFeed)
-    import threading
-    feed.root, feed._slot_lock, feed._free_slots, feed._n_slots = str(tmp_path), threading.Lock(), [], 0
-    a = feed._slot_alloc()
-    x = a("pos", np.int32, 1000)
-    x[:] = np.arange(1000)
-    x.flush()
+    pool = ingest._SlotPool(str(tmp_path))
+    a = pool.take()
+    x = a.put("pos", np.arange(1000, dtype=np.int32))
+    assert x.tolist() == list(range(1000))
     ino = os.stat(os.path.join(a.dir, "pos.bin")).st_ino
     assert a.arrays == {"pos": ("<i4", 1000)}
-    feed._slot_free(a.dir)
-    b = feed._slot_alloc()
-    assert b.dir == a.dir
-    y = b("pos", np.int32, 400)                                      # fits: same file, same pages
+    a.mark("cigar.ready")
+    a.mark("seq.ready")
+    assert os.path.exists(os.path.join(a.dir, "cigar.ready")) and os.path.exists(os.path.join(a.dir, "seq.ready"))
+    pool.give(a.dir)
+    b = pool.take()
+    assert b.dir == a.dir and b.arrays == {}
+    assert not os.path.exists(os.path.join(b.dir, "cigar.ready")) and not os.path.exists(os.path.join(b.dir, "seq.ready"))   # stale flags are gone
+    y = b.put("pos", np.full(400, 7, np.int32))                      # fits: same file, same pages
     assert os.stat(os.path.join(b.dir, "pos.bin")).st_ino == ino and y.shape == (400,)
-    y[:] = 7
-    y.flush()
-    z = b("cigar", np.uint32, 0)
-    assert z.size == 0 and b.arrays["cigar"] == ("<u4", 0)
+    z = b.put("cigar", np.empty(0, np.uint32))
+    assert z.size == 0 and b.arrays["cigar"] == ("<u4", 0) and not os.path.exists(os.path.join(b.dir, "cigar.bin"))
     back = np.memmap(os.path.join(b.dir, "pos.bin"), dtype=np.int32, mode="c", shape=(400,))
     assert (back == 7).all()
-    feed._slot_free(b.dir)
-    c = feed._slot_alloc()
-    big = c("pos", np.int32, 5000)                                   # does not fit: a new file
+    pool.give(b.dir)
+    c = pool.take()
+    big = c.put("pos", np.arange(5000, dtype=np.int32))              # does not fit: a new file
     assert big.shape == (5000,) and os.path.getsize(os.path.join(c.dir, "pos.bin")) == 20000
-    other = feed._slot_alloc()
+    assert np.array_equal(np.fromfile(os.path.join(c.dir, "pos.bin"), np.int32), np.arange(5000))
+    other = pool.take()
     assert other.dir != c.dir                                        # no free slot: a fresh one
 
 

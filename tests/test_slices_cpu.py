@@ -15,7 +15,7 @@ import pytest
 from svision_amd import _lib, synth
 from svision_amd.collection.output_clusters import collect_pair_lines
 from svision_amd.collection.run_collection import detect_window
-from svision_amd.ingest import ChromosomeFeed
+from svision_amd.ingest import ChromosomeFeed, grow_margin
 from svision_amd.ingest_gpu import DeviceDecoder, Unit, voff_at
 from svision_amd.io import bam
 from svision_amd.pipeline import WindowResult, _vote, stitch_windows
@@ -181,7 +181,7 @@ def test_a_record_spanning_a_whole_slice_is_not_an_empty_slice(tmp_path):
     spanned = sum(1 for u in units if voff_at(span, u.lo - margin) == voff_at(span, u.hi + 2 * margin) < span[1]
                   and np.any((table.pos < u.hi) & (ref_end > u.lo)))
     assert spanned >= 1                                       # the case really occurs in this file with this margin
-    # the feed's loop (ingest.ChromosomeFeed._run / _decode): a rejected slice -> everything from it on is cut again with twice
+    # the feed's loop (ingest.ChromosomeFeed._run / _decode_device): a rejected slice -> everything from it on is cut again with twice
     # what it needed; an accepted slice must hold every record the whole file has for its windows
     served, replans = [], 0
     while units:
@@ -197,7 +197,7 @@ def test_a_record_spanning_a_whole_slice_is_not_an_empty_slice(tmp_path):
         if not ChromosomeFeed._slice_complete(u, smp):
             replans += 1
             assert replans < 12
-            margin = (max(2 * ChromosomeFeed._slice_needs(u, smp), 2 * margin) + 16383) >> 14 << 14
+            margin = grow_margin(ChromosomeFeed._slice_needs(u, smp), margin)
             units = dec.plan_units([0], lambda t: windows, margin=margin, slice_bytes=1, min_span_margins=0, resume=(0, u.lo))
             continue
         for a, b in u.windows:
