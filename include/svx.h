@@ -394,6 +394,29 @@ int            svx_bam_walk_extract_seq(const uint8_t* d_raw, const uint64_t* d_
                                         int64_t* d_cig_off, uint32_t* d_cigar, int64_t* d_name_off, uint8_t* d_names,
                                         const uint64_t* d_seq_base, int64_t* d_seq_off, uint8_t* d_seq, uint32_t n_records,
                                         void* stream);
+/* Record starts WITHOUT an index (svx_bamindex.hip): a BAM that has no .bai names one record start -- the end of its header --
+ * and chains the others through their block_size fields.  For a range of whole BGZF blocks inflated to d_raw (d_dst_off [n_blocks + 1]:
+ * where every block's bytes lie, as svx_bgzf_inflate_fast took them) and `entry`, the byte offset in d_raw of one known record start
+ * (d_dst_off[0] <= entry <= d_dst_off[n_blocks]: the header's end in a file's first range, d_exit[0] of the range in front in a later one):
+ *   d_first [n_blocks]  the offset in d_raw of the first record of the chain from `entry` that STARTS in block b, UINT64_MAX
+ *                       where none does (a block inside one long record, a block in front of `entry`, a block of no bytes)
+ *   d_exit [2]          [0] the start of the chain's last record where the range's end cuts it, the range's end where the
+ *                       chain ends exactly there; [1] status: 0 ok, 1 the chain ran into a malformed record, at offset [0]
+ *   n_ref, d_ref_len    the reference dictionary (int32 lengths): what a plausible record may name
+ *   d_ws                scratch of ws_bytes >= svx_bam_find_starts_ws_bytes(n_blocks) bytes, 16-byte aligned, contents ignored
+ * A wave per block guesses the block's first start (64 offsets a step, the lowest that looks like a record) and walks from it
+ * to the block's end; a guess counts only if the chain from `entry` arrives exactly on it -- pointer doubling over the blocks'
+ * successor links marks that path in log2(n_blocks) launches, and one lane re-walks the block behind every link that does not
+ * hold: serial work per broken link, not per block or record.  No atomics; the result does not depend on the guesses.
+ * The compacted d_first + d_exit[0] is the d_starts array of svx_bam_walk_count / svx_bam_walk_extract (2 + 2 log2(n_blocks) launches).
+ *   svx_bam_walk_offsets  d_rec_off [records] = the byte offset in d_raw of every record between the starts, in the order and
+ *                       with the d_base of svx_bam_walk_extract (a lane per start; after a count pass with status 0) */
+size_t         svx_bam_find_starts_ws_bytes(uint32_t n_blocks);
+int            svx_bam_find_starts(const uint8_t* d_raw, const uint64_t* d_dst_off, uint32_t n_blocks, uint64_t entry, uint32_t n_ref,
+                                   const int32_t* d_ref_len, uint64_t* d_first, uint64_t* d_exit, void* d_ws, uint64_t ws_bytes,
+                                   void* stream);
+int            svx_bam_walk_offsets(const uint8_t* d_raw, const uint64_t* d_starts, uint32_t n_starts, const uint64_t* d_base,
+                                    uint64_t* d_rec_off, void* stream);
 /* host helpers of the device-side ingestion: parallel positional read into caller memory; the whole BGZF blocks of a
  * buffer (payload offset / size, ISIZE, file offset; -> their number or -1, *used = bytes they cover); QNAME ids by
  * first occurrence (-> number of distinct names, written '\n'-separated to uniq) */

@@ -66,6 +66,9 @@ SYMBOLS = {
     "svx_bam_walk_extract": (ctypes.c_int, [_vp, _vp, _u32, _vp] + [_vp] * 9 + [_u32, _vp]),
     "svx_bam_walk_count_seq": (ctypes.c_int, [_vp, _vp, _u32, _vp, _vp, _vp]),
     "svx_bam_walk_extract_seq": (ctypes.c_int, [_vp, _vp, _u32, _vp] + [_vp] * 12 + [_u32, _vp]),
+    "svx_bam_find_starts_ws_bytes": (_sz, [_u32]),
+    "svx_bam_find_starts": (ctypes.c_int, [_vp, _vp, _u32, _u64, _u32, _vp, _vp, _vp, _vp, _u64, _vp]),
+    "svx_bam_walk_offsets": (ctypes.c_int, [_vp, _vp, _u32, _vp, _vp, _vp]),
     "svx_read_range": (ctypes.c_int, [ctypes.c_char_p, _u64, _u64, _vp, ctypes.c_int]),
     "svx_bgzf_index": (ctypes.c_int64, [_vp, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _vp]),
     "svx_name_ids": (ctypes.c_int64, [_vp, _vp, _u64, _vp, _vp, _vp]),

@@ -172,6 +172,13 @@ def run(options, sample=None, classifier=None):
             raise SystemExit(1)
         fasta = Fasta(options.genome)
         references, lengths = head.references, head.lengths
+        index = find_index(options.bam_path)
+        build_index = index is None and os.environ.get("SVX_BUILD_INDEX") == "1"
+        if build_index and ws > 1:
+            # (every rank would build the same file; one build in front of the launch serves them all)
+            logging.error("SVX_BUILD_INDEX=1 builds the index in a single-rank run only: build it first with "
+                          "`python -m svision_amd.index %s` and start the %d ranks again", options.bam_path, ws)
+            raise SystemExit(1)
     else:
         fasta = sample.fasta
         references, lengths = sample.table.references, sample.table.lengths
@@ -207,8 +214,16 @@ def run(options, sample=None, classifier=None):
         if sample is None:
             from .ingest import decode_threads
             threads = decode_threads(int(os.environ.get("LOCAL_WORLD_SIZE", ws)), options.thread_num)      # inflate threads of this rank
+            if build_index:
+                # SVX_BUILD_INDEX=1 and no .bai next to the BAM: built on the device (svision_amd/index.py) into the output directory --
+                # the BAM's own may be read-only --, and the device engine serves the run
+                from .index import build_index as _build_index
+                index = _build_index(options.bam_path, os.path.join(work_dir, os.path.basename(options.bam_path) + ".bai"),
+                                     device=torch.device("cuda", torch.cuda.current_device()))
+                logging.info("no index next to %s: built %s on the device", options.bam_path, index)
+                _tick("index built on the device")
             feed = ChromosomeFeed(options.bam_path, fasta, options, [c for c in mine if c in references], references, lengths,
-                                  device=torch.device("cuda", torch.cuda.current_device()), index=find_index(options.bam_path), threads=threads,
+                                  device=torch.device("cuda", torch.cuda.current_device()), index=index, threads=threads,
                                   tasks={c: tasks[c] for c in mine if c in tasks})
             logging.info("rank %d/%d: %s streamed from %s with %d decode threads", rank, ws, ",".join(mine) or "-", options.bam_path, threads)
         else:

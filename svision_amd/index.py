@@ -1,0 +1,320 @@
+"""Build the ``.bai`` of a BAM that has none, on the device: ``python -m svision_amd.index sample.bam [-o sample.bam.bai]``.
+
+The device ingest engine (svision_amd/ingest_gpu.py) starts every parallel step of its record walk at an entry of the .bai
+linear index; a file without one was left to the host engine.  Indexing it with the usual tools is a single-threaded pass over
+the whole file.  Everything such a pass needs is on the device already -- inflate, CRC32, the record walk, the CIGAR scan that
+yields every record's reference span -- except knowing where records start when nothing says so: svx_bam_find_starts
+(csrc/svx_bamindex.hip) finds, per BGZF block, the first record that starts in it.  The pass:
+
+  header     host: read_bam_header (references) + the first blocks through zlib -> where the first record starts
+  per range  whole BGZF blocks, the decoder's group size of file a range (svx_read_range, svx_bgzf_index), then on the device
+             svx_bgzf_inflate_fast -> svx_bgzf_crc32 -> svx_bam_find_starts -> svx_bam_walk_count / _extract ->
+             svx_bam_walk_offsets -> svx_cigar_scan (its per-record reference span) -> tid, pos, flag, span, byte offset back
+  carry      a record the range's end cuts is not lost: the next range begins with the block it starts in, and its start is
+             that range's known record start -- at most one record's blocks are inflated twice.  A range in which no record
+             completes is read again, twice as large
+  assembly   host: svision_amd.io.bai.bai_bytes, written under a temporary name in the target's directory and renamed
+
+A corrupt block, a CRC mismatch, a malformed or cut record chain or a file that is not coordinate-sorted raises IndexBuildError
+(a ValueError); no file is left behind.  A plain loop: nothing here overlaps reading, inflating and walking.
+"""
+import os
+import struct
+import sys
+import tempfile
+import time
+import zlib
+
+import numpy as np
+
+from . import _lib
+from .io import bai
+
+NO_START = np.uint64(0xFFFFFFFFFFFFFFFF)                        # UINT64_MAX in d_first: no record of the chain starts in the block
+STAGES = ("read", "upload", "inflate", "crc", "find_starts", "walk", "scan", "read_back", "assembly")
+
+
+class IndexBuildError(ValueError):
+    pass
+
+
+def first_record(path, limit=1 << 30):
+    """Host: the BAM header through zlib, block by block -> (file offset of the BGZF block the first record starts in, the
+    record's offset in that block's inflated bytes, number of references)."""
+    need, have, n_ref, step, at = 8, 0, None, 0, 0
+    head = bytearray()
+    with open(path, "rb") as f:
+        while True:
+            f.seek(at)
+            fixed = f.read(18)
+            if len(fixed) < 18 or fixed[:4] != b"\x1f\x8b\x08\x04":
+                raise IndexBuildError("%s: no BGZF block at file offset %d (the BAM header is cut)" % (path, at))
+            xlen = struct.unpack_from("<H", fixed, 10)[0]
+            f.seek(at + 12)
+            extra = f.read(xlen)
+            bsize, q = None, 0
+            while q + 4 <= len(extra):
+                slen = struct.unpack_from("<H", extra, q + 2)[0]
+                if extra[q:q + 2] == b"BC" and slen == 2:
+                    bsize = struct.unpack_from("<H", extra, q + 4)[0] + 1
+                q += 4 + slen
+            if bsize is None:
+                raise IndexBuildError("%s: the gzip member at file offset %d is no BGZF block" % (path, at))
+            payload = f.read(bsize - 12 - xlen - 8)
+            try:
+                data = zlib.decompress(payload, -15)
+            except zlib.error as exc:
+                raise IndexBuildError("%s: the block at file offset %d does not inflate (%s)" % (path, at, exc)) from None
+            block_at, block_base = at, have
+            head += data
+            have += len(data)
+            at += bsize
+            # the header's fields, as far as they are in hand: magic, l_text, text, n_ref, then per reference l_name, name, l_ref
+            while have >= need:
+                if step == 0:
+                    if bytes(head[:4]) != b"BAM\x01":
+                        raise IndexBuildError("%s is not a BAM file" % path)
+                    l_text = struct.unpack_from("<i", head, 4)[0]
+                    need, step = 8 + l_text + 4, 1
+                elif step == 1:
+                    n_ref = struct.unpack_from("<i", head, need - 4)[0]
+                    left, step = n_ref, 2
+                    if left:
+                        need += 4
+                    else:
+                        step = 3
+                        break
+                elif step == 2:
+                    l_name = struct.unpack_from("<i", head, need - 4)[0]
+                    need, step = need + l_name + 4, 4
+                elif step == 4:
+                    left -= 1
+                    if left:
+                        need, step = need + 4, 2
+                    else:
+                        step = 3
+                        break
+            if step == 3:
+                break
+            if have > limit:
+                raise IndexBuildError("%s: a BAM header of more than %d bytes" % (path, limit))
+    if need == have:                                            # the header fills its block: the first record opens the next one
+        return at, 0, n_ref
+    return block_at, need - block_base, n_ref
+
+
+class _Clock:
+    """Wall time per stage, the device drained at every boundary (what a stage enqueued is counted as that stage's)."""
+
+    def __init__(self, torch, device):
+        self.torch, self.device, self.t, self.times = torch, device, time.perf_counter(), dict.fromkeys(STAGES, 0.0)
+
+    def lap(self, stage, device_work=True):
+        if device_work:
+            self.torch.cuda.synchronize(self.device)
+        now = time.perf_counter()
+        self.times[stage] += now - self.t
+        self.t = now
+
+
+def _as_i64(t_np):
+    return np.ascontiguousarray(t_np, np.uint64).view(np.int64)
+
+
+def _index_range(lib, torch, kernels, dev, pinned, blocks, entry, d_ref_len, n_ref, clock):
+    """One range on the device -> (exit offset, dst_off, per-record arrays tid, pos, flag, span, byte offset), or raises."""
+    n, used = blocks.k, blocks.used
+    st = kernels._stream_ptr(dev)
+    dst = np.zeros(n + 1, np.uint64)
+    dst[1:] = np.cumsum(blocks.isize.astype(np.uint64))
+    total = int(dst[n])
+    d_comp = torch.empty((used + 31) // 16 * 16, dtype=torch.uint8, device=dev)
+    d_comp[:used].copy_(pinned[:used], non_blocking=True)
+    d_src = torch.from_numpy(_as_i64(blocks.src_off)).to(dev)
+    d_len = torch.from_numpy(np.ascontiguousarray(blocks.src_len, np.uint32).view(np.int32)).to(dev)
+    d_dst = torch.from_numpy(dst.view(np.int64)).to(dev)
+    clock.lap("upload")
+    # (readable up to the next multiple of 16 behind its last byte: the walk's aligned loads, include/svx.h)
+    d_raw = torch.empty((max(total, 1) + 15) // 16 * 16 + 16, dtype=torch.uint8, device=dev)
+    d_status = torch.zeros(n, dtype=torch.int32, device=dev)
+    d_ws = torch.empty(int(lib.svx_bgzf_inflate_fast_ws_bytes(total, n)), dtype=torch.uint8, device=dev)
+    _lib.check(lib.svx_bgzf_inflate_fast(d_comp.data_ptr(), d_src.data_ptr(), d_len.data_ptr(), d_dst.data_ptr(), n, total, d_raw.data_ptr(),
+                                         d_status.data_ptr(), d_ws.data_ptr(), int(d_ws.numel()), st), "svx_bgzf_inflate_fast")
+    clock.lap("inflate")
+    _lib.check(lib.svx_bgzf_crc32(d_raw.data_ptr(), d_dst.data_ptr(), d_comp.data_ptr(), d_src.data_ptr(), d_len.data_ptr(), n,
+                                  d_status.data_ptr(), st), "svx_bgzf_crc32")
+    status = d_status.cpu().numpy()
+    clock.lap("crc")
+    del d_ws
+    if status.any():
+        b = int(np.flatnonzero(status)[0])
+        raise IndexBuildError("the BGZF block at file offset %d %s" % (int(blocks.coff[b]), "fails its CRC32" if status[b] == kernels.INFLATE_BAD_CRC
+                                                                         else "is corrupt (inflate status %d)" % status[b]))
+    # where records start: per block the first start of the chain from `entry`
+    d_first = torch.empty(n, dtype=torch.int64, device=dev)
+    d_exit = torch.zeros(2, dtype=torch.int64, device=dev)
+    d_fws = torch.empty(int(lib.svx_bam_find_starts_ws_bytes(n)), dtype=torch.uint8, device=dev)
+    _lib.check(lib.svx_bam_find_starts(d_raw.data_ptr(), d_dst.data_ptr(), n, int(entry), n_ref, d_ref_len.data_ptr(), d_first.data_ptr(),
+                                       d_exit.data_ptr(), d_fws.data_ptr(), int(d_fws.numel()), st), "svx_bam_find_starts")
+    first = d_first.cpu().numpy().view(np.uint64)
+    exit_off, chain_status = (int(v) for v in d_exit.cpu().numpy().view(np.uint64))
+    clock.lap("find_starts")
+    if chain_status:
+        at = min(max(int(np.searchsorted(dst[:n], np.uint64(exit_off), "right")) - 1, 0), n - 1)
+        raise IndexBuildError("a malformed record %d bytes into the BGZF block at file offset %d" % (exit_off - int(dst[at]), int(blocks.coff[at])))
+    starts = np.unique(np.append(first[first != NO_START], np.uint64(exit_off)))
+    n_starts = int(starts.size) - 1
+    empty = (np.empty(0, np.int32), np.empty(0, np.int32), np.empty(0, np.uint16), np.empty(0, np.int32), np.empty(0, np.uint64))
+    if n_starts <= 0:
+        return exit_off, dst, empty
+    # the existing walk over those starts: counts -> prefix sums -> the records' fields, CIGAR words and byte offsets
+    d_starts = torch.from_numpy(starts.view(np.int64)).to(dev)
+    d_counts = torch.empty((n_starts, 4), dtype=torch.int64, device=dev)
+    _lib.check(lib.svx_bam_walk_count(d_raw.data_ptr(), d_starts.data_ptr(), n_starts, d_counts.data_ptr(), st), "svx_bam_walk_count")
+    counts = d_counts.cpu().numpy()
+    if counts[:, 3].any():
+        i = int(np.flatnonzero(counts[:, 3])[0])
+        raise IndexBuildError("the record walk from byte %d of the range's inflated stream ended with status %d" % (int(starts[i]), int(counts[i, 3])))
+    base = np.zeros((n_starts, 3), np.int64)
+    base[1:] = np.cumsum(counts[:-1, :3], axis=0)
+    n_rec, words, name_bytes = (int(v) for v in counts[:, :3].sum(axis=0))
+    if n_rec == 0:
+        clock.lap("walk")
+        return exit_off, dst, empty
+    d_base = torch.from_numpy(base).to(dev)
+    d_tid, d_pos, d_l_seq = (torch.empty(n_rec, dtype=torch.int32, device=dev) for _ in range(3))
+    d_flag, d_mapq = torch.empty(n_rec, dtype=torch.int16, device=dev), torch.empty(n_rec, dtype=torch.uint8, device=dev)
+    d_cig_off, d_name_off = (torch.empty(n_rec + 1, dtype=torch.int64, device=dev) for _ in range(2))
+    d_cigar = torch.empty(max(words, 1) + 4, dtype=torch.int32, device=dev)
+    d_names = torch.empty(max(name_bytes, 1), dtype=torch.uint8, device=dev)
+    d_rec_off = torch.empty(n_rec, dtype=torch.int64, device=dev)
+    _lib.check(lib.svx_bam_walk_extract(d_raw.data_ptr(), d_starts.data_ptr(), n_starts, d_base.data_ptr(), d_tid.data_ptr(), d_pos.data_ptr(),
+                                        d_flag.data_ptr(), d_mapq.data_ptr(), d_l_seq.data_ptr(), d_cig_off.data_ptr(), d_cigar.data_ptr(),
+                                        d_name_off.data_ptr(), d_names.data_ptr(), n_rec, st), "svx_bam_walk_extract")
+    _lib.check(lib.svx_bam_walk_offsets(d_raw.data_ptr(), d_starts.data_ptr(), n_starts, d_base.data_ptr(), d_rec_off.data_ptr(), st),
+               "svx_bam_walk_offsets")
+    clock.lap("walk")
+    # the reference span of every record: the scan's statistics (a CG-tag record: of its real CIGAR); no gap is long enough to be listed
+    scan = kernels.cigar_scan(d_cigar, d_cig_off, d_pos, 0x7FFFFFFF, n_words=words)
+    clock.lap("scan")
+    out = (d_tid.cpu().numpy(), d_pos.cpu().numpy(), d_flag.cpu().numpy().view(np.uint16), scan.stats[:, 0].contiguous().cpu().numpy(),
+           d_rec_off.cpu().numpy().view(np.uint64))
+    clock.lap("read_back")
+    return exit_off, dst, out
+
+
+def build_index(bam_path, out_path=None, device="cuda", range_bytes=None, stats=None):
+    """Write the ``.bai`` of ``bam_path`` to ``out_path`` (default ``bam_path + ".bai"``) and return that path.  ``range_bytes``:
+    compressed bytes a range (default: the device decoder's group size; tests).  ``stats``: a dict that receives the number of
+    ranges, blocks and records and the seconds per stage -- in total ("seconds") and per range ("per_range")."""
+    import torch
+    from . import ingest, ingest_gpu, kernels
+    from .io.bam import read_bam_header
+    if not torch.cuda.is_available():
+        raise _lib.SvxError("build_index needs the GPU (svx_bam_find_starts); there is no CPU fallback")
+    lib = _lib.load()
+    dev = torch.device(device)
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    out_path = out_path or bam_path + ".bai"
+    base_bytes = int(range_bytes or ingest_gpu.LARGE_GROUP_BYTES)
+    clock = _Clock(torch, dev)
+    head = read_bam_header(bam_path)
+    file_at, entry, n_ref = first_record(bam_path)
+    if n_ref != len(head.references):
+        raise IndexBuildError("%s: the header names %d references, its dictionary %d" % (bam_path, len(head.references), n_ref))
+    size = os.path.getsize(bam_path)
+    d_ref_len = torch.from_numpy(np.asarray(list(head.lengths) + [0], np.int32)).to(dev)
+    parts, per_range, n_blocks, want_bytes, end_voff = [], [], 0, base_bytes, None
+    pinned = None                                               # a range's file bytes: read into pinned memory, reused from range to range
+    threads = ingest.decode_threads()
+    clock.lap("read", False)
+    while True:
+        want = int(min(want_bytes, size - file_at))
+        if want <= 0:
+            raise IndexBuildError("%s ends without a whole BGZF block behind file offset %d" % (bam_path, file_at))
+        if pinned is None or pinned.numel() < want:
+            pinned = torch.empty(want, dtype=torch.uint8, pin_memory=True)
+        before = dict(clock.times)
+        if lib.svx_read_range(bam_path.encode(), file_at, want, pinned.data_ptr(), threads) != 0:
+            raise IndexBuildError(lib.svx_bam_error().decode())
+        blocks = ingest_gpu._index_blocks(lib, pinned.data_ptr(), want, file_at)
+        at_end = file_at + want == size
+        if blocks.k < 0 or (blocks.k == 0 and at_end) or (at_end and blocks.used != want):
+            raise IndexBuildError("%s: no whole BGZF block at file offset %d" % (bam_path, file_at + max(blocks.used, 0)))
+        clock.lap("read", False)
+        if blocks.k == 0:
+            want_bytes *= 2
+            continue
+        exit_off, dst, (tid, pos, flag, span, rec_off) = _index_range(lib, torch, kernels, dev, pinned, blocks, entry, d_ref_len, n_ref, clock)
+        total = int(dst[blocks.k])
+        if exit_off == entry and not at_end and exit_off < total:
+            want_bytes *= 2                                     # no record completes in the range: the same place again, twice as large
+            continue
+        n_blocks += blocks.k
+        parts.append((tid, pos, flag, span, bai.virtual_offsets(dst, blocks.coff, rec_off)))
+        clock.lap("assembly", False)
+        per_range.append(dict({k: round(clock.times[k] - before[k], 6) for k in STAGES}, blocks=int(blocks.k), records=int(tid.size),
+                              compressed_bytes=int(blocks.used), inflated_bytes=total))
+        if at_end:
+            if exit_off != total:
+                raise IndexBuildError("%s is cut inside a record: its last record starts %d bytes before the end of the data and does not fit"
+                                      % (bam_path, total - exit_off))
+            end_voff = bai.virtual_offsets(dst, blocks.coff, [total])
+            break
+        want_bytes = base_bytes
+        if exit_off >= total:
+            file_at, entry = file_at + blocks.used, 0
+        else:                                                   # the block the cut record starts in opens the next range
+            b = int(np.searchsorted(dst[:blocks.k], np.uint64(exit_off), "right")) - 1
+            file_at, entry = int(blocks.coff[b]), exit_off - int(dst[b])
+    tid, pos, flag, span, voff = (np.concatenate([p[i] for p in parts]) for i in range(5))
+    voff_end = np.append(voff[1:], end_voff).astype(np.uint64)
+    pos64 = pos.astype(np.int64)
+    try:
+        data = bai.bai_bytes(n_ref, tid, pos64, pos64 + np.maximum(span.astype(np.int64), 1), flag, voff, voff_end)
+    except ValueError as exc:
+        raise IndexBuildError("%s: %s" % (bam_path, exc)) from None
+    fd, tmp = tempfile.mkstemp(prefix=os.path.basename(out_path) + ".", suffix=".tmp", dir=os.path.dirname(os.path.abspath(out_path)))
+    try:
+        with os.fdopen(fd, "wb") as f:
+            f.write(data)
+        os.chmod(tmp, 0o666 & ~_umask())
+        os.replace(tmp, out_path)
+    except BaseException:
+        if os.path.exists(tmp):
+            os.unlink(tmp)
+        raise
+    clock.lap("assembly", False)
+    if stats is not None:
+        stats.update(ranges=len(per_range), blocks=n_blocks, records=int(tid.size), seconds={k: round(v, 6) for k, v in clock.times.items()},
+                     per_range=per_range)
+    return out_path
+
+
+def _umask():
+    mask = os.umask(0)
+    os.umask(mask)
+    return mask
+
+
+def main(argv=None):
+    import argparse
+    ap = argparse.ArgumentParser(prog="python -m svision_amd.index", description="Build the .bai of a coordinate-sorted BAM on the GPU.")
+    ap.add_argument("bam")
+    ap.add_argument("-o", "--output", default=None, help="the index to write (default: BAM + .bai)")
+    ap.add_argument("--device", default="cuda")
+    args = ap.parse_args(argv)
+    stats = {}
+    try:
+        path = build_index(args.bam, args.output, device=args.device, stats=stats)
+    except (IndexBuildError, OSError) as exc:
+        print("svision_amd.index: %s" % exc, file=sys.stderr)
+        return 1
+    print("%s: %d records in %d BGZF blocks, %d range(s), %.2f s" % (path, stats["records"], stats["blocks"], stats["ranges"],
+                                                                   sum(stats["seconds"].values())))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
