@@ -52,7 +52,7 @@ def test_device_seed_and_extend_matches_reference_cases():
     and its raw hit lists == the host aligner's, in order."""
     from svision_amd import kernels
     from svision_amd.segmentplot import run_hash_lineplot as rh
-    from svision_amd.segmentplot.hash_aligner import HashAligner
+    from tests import hashcases
     with open(os.path.join(helpers.GOLDEN, "hash_small.expected.json")) as f:
         cases = json.load(f)
     got = rh.hashplot_unmapped_batch([(c["ref"], c["seq"]) for c in cases], 10, 50, "cuda:0")
@@ -66,15 +66,8 @@ def test_device_seed_and_extend_matches_reference_cases():
     for c in cases[:40]:
         x, y = kernels.pack_bases(c["seq"]), kernels.pack_bases(c["ref"])
         hits_a, hits_b = kernels.hash_seeds([(x, y)], 10, 50, "cuda:0")[0]
-        a = HashAligner(10, 50, 0, 2)
-        a.run(c["ref"], c["ref"])
-        want_a = [[s.yStart(), s.xStart() if s.forward() else (len(y) - 1) - s.xStart(), s._length, int(bool(s.forward()))] for s in a.getSegments()]
+        want_a, want_b = hashcases.raw_hit_lists(c["ref"], c["seq"], 10, 50)
         assert hits_a.tolist() == want_a
-        b = HashAligner(10, 50, 0, 2)
-        b.compareDiffSegs = []                                   # keep every hit
-        b.y_hashvalues = a.getHashValues()
-        b._align(c["seq"], c["ref"], a.getAvoidKmer())
-        want_b = [[s.yStart(), s.xStart() if s.forward() else (len(x) - 1) - s.xStart(), s._length, int(bool(s.forward()))] for s in b.getSegments()]
         assert hits_b.tolist() == want_b
     # sequences outside ACGTN are refused by the packer (host path)
     assert kernels.pack_bases("ACGTnACGT") is not None and kernels.pack_bases("ACGTBDACGT") is None
