@@ -300,6 +300,15 @@ typedef struct SvxHashJob {
 } SvxHashJob;
 int svx_hash_seeds(const uint8_t* d_bases, const SvxHashJob* d_jobs, uint32_t n_jobs, uint64_t* d_table,
                    int32_t* d_hits, uint32_t* d_counts, uint32_t k, uint32_t window, uint32_t max_x_len, void* stream);
+/* (ABI 420, additive) The hit lists of a batch, compacted for the read-back: enqueued behind svx_hash_seeds on the same
+ * stream, with the same d_jobs / d_hits / d_counts.  The 2 n_jobs lists are numbered A0 B0 A1 B1 ...; a list whose count
+ * exceeds its hit_cap holds no row here (d_counts still tells: the caller redoes that job on the host).
+ *   d_row_off   [2 n_jobs + 1]  rows in front of every list; the last entry is the total
+ *   d_packed    [packed_cap][4] every list's rows, in list order and in their own order; 16-byte aligned, like d_hits
+ * Rows behind packed_cap are not written: a caller that reads d_row_off[2 n_jobs] > packed_cap calls again with a larger
+ * array (d_hits is untouched, the seeds are not repeated). */
+int svx_hash_pack_hits(const SvxHashJob* d_jobs, uint32_t n_jobs, const int32_t* d_hits, const uint32_t* d_counts,
+                       uint32_t* d_row_off, int32_t* d_packed, uint64_t packed_cap, void* stream);
 
 /* ---- host side: native BGZF/BAM ingestion (no device work) -------------------------------------------
  * Replaces the per-record pysam iteration of the reference (aln_file.fetch at

@@ -29,9 +29,9 @@ cpdef analyze_gap(Seg cur, Seg nxt, chrom_of, fetch_ref, options, qname, help_se
 cpdef _piece(list out, Seg seg, long q0, long q1, long r0, long r1)
 
 @cython.locals(vrp=long, first_ref=long, m=long, ref_pos=long, length=long, kind=long, rows=list, out=list)
-cpdef tuple analyze_inside_align(Seg seg, gaps, options=*, sample=*)
+cpdef tuple analyze_inside_align(Seg seg, gaps, options=*, sample=*, deferred=*)
 
 @cython.locals(p_rev=bint, a_rev=bint, qlen=long, lead=long, trail=long, r0=long, span=long, tid=long, mapq=long, flag=long,
                q_start=long, q_end=long, seg=Seg, base=Seg, target=Seg, left_most=long, right_most=long, last=long, i=long,
                majors=list, minors=list, same_strand=list, ordered=list)
-cpdef tuple analyze_between_aligns(primary, supplementary, table, options, sample=*, cols=*)
+cpdef tuple analyze_between_aligns(primary, supplementary, table, options, sample=*, cols=*, deferred=*)

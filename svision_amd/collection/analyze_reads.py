@@ -247,18 +247,34 @@ def _hash_hits_to_segs(hits, read_offset, ref_offset, like, read_seq):
     return out
 
 
+class HashJob:
+    """A re-alignment that the two-phase collection of a window (collect_signatures.analyze_alignments) has put off: it
+    stands in its read's segment list exactly where the helper segments of the ``hashplot_unmapped`` call would have
+    been appended, until all jobs of the window have been resolved in one batch."""
+    __slots__ = ("ref_seq", "piece", "read_offset", "ref_offset", "like", "read_seq")
+
+    def __init__(self, ref_seq, piece, read_offset, ref_offset, like, read_seq):
+        self.ref_seq, self.piece, self.read_offset, self.ref_offset = ref_seq, piece, read_offset, ref_offset
+        self.like, self.read_seq = like, read_seq
+
+    def segs(self, hits):
+        """The helper segments the put-off call would have appended, from its hits."""
+        return _hash_hits_to_segs(hits, self.read_offset, self.ref_offset, self.like, self.read_seq)
+
+
 def _fields(table, a):
     """(flag, leading clip, trailing clip, pos, reference span, tid, mapq, l_seq) of record ``a`` as Python ints."""
     return (int(table.flag[a]), int(table.lead_clip[a]), int(table.trail_clip[a]), int(table.pos[a]), int(table.ref_span[a]),
             int(table.tid[a]), int(table.mapq[a]), int(table.l_seq[a]))
 
 
-def analyze_between_aligns(primary, supplementary, table, options, sample=None, cols=None):
+def analyze_between_aligns(primary, supplementary, table, options, sample=None, cols=None, deferred=None):
     """Primary + supplementary alignments of one read -> (major, minor) segments (:619-801).
 
     ``primary``/``supplementary`` are record indices into ``table`` (an AlignmentTable with the
     device scan attached).  Query coordinates are expressed on the primary's strand.  ``cols``: {record index:
-    :func:`_fields` tuple} prepared by the caller for the records of a whole window."""
+    :func:`_fields` tuple} prepared by the caller for the records of a whole window.  ``deferred``: a list -> the --hash
+    re-alignments are not run but appended to it (and to the minor segments) as :class:`HashJob` placeholders."""
     if not options.contig and len(supplementary) > 4:
         return [], []
     _TABLE[0] = table
@@ -308,11 +324,11 @@ def analyze_between_aligns(primary, supplementary, table, options, sample=None, 
             base.type = "main"
             majors.append(base)
     if options.hash:
-        _hash_between(majors, minors, options, sample)
+        _hash_between(majors, minors, options, sample, deferred)
     return majors, minors
 
 
-def _hash_between(majors, minors, options, sample):
+def _hash_between(majors, minors, options, sample, deferred=None):
     """--hash: re-align the unmapped read piece between two adjacent main segments (:731-790).
     Upstream indexes the sorted segment list with the loop counter rather than with the main
     segment's own position (:744-745) and slices the segment's own bases with whole-read
@@ -335,6 +351,11 @@ def _hash_between(majors, minors, options, sample):
         ref_end = max(cur.ref_end, nxt.ref_end)
         ref_seq = sample.fetch_ref_str(sample.chrom_of(cur.ref_id), ref_start, ref_end)
         if len(piece) < options.max_hash_len:
+            if deferred is not None:
+                job = HashJob(ref_seq, piece, read_start, ref_start, cur, piece)
+                deferred.append(job)
+                minors.append(job)
+                continue
             _m, hits = hashplot_unmapped(ref_seq, piece, options.k_size, options.min_accept)
             minors.extend(_hash_hits_to_segs(hits, read_start, ref_start, cur, piece))
 
@@ -347,11 +368,11 @@ def _piece(out, seg, q0, q1, r0, r1):
     out.append(new)
 
 
-def analyze_inside_align(seg, gaps, options=None, sample=None):
+def analyze_inside_align(seg, gaps, options=None, sample=None, deferred=None):
     """Split one major segment at its long CIGAR gaps (:857-948).  ``gaps`` are this
     alignment's SvxGap records (kind, read_pos, ref_pos, len in op order) from the device scan;
     returns (new major segments, helper segments from --hash) or (None, None) when the alignment
-    holds no long gap."""
+    holds no long gap.  ``deferred``: as in :func:`analyze_between_aligns`, the placeholders stand among the helpers."""
     if len(gaps) == 0:
         return None, None
     out = []
@@ -385,6 +406,11 @@ def analyze_inside_align(seg, gaps, options=None, sample=None):
             if ref_seq is None or True:                        # upstream re-fetches per insertion (same span)
                 ref_seq = sample.fetch_ref_str(sample.chrom_of(seg.ref_id), seg.ref_start, seg.ref_end)
             if len(ins) < options.max_hash_len:
+                if deferred is not None:
+                    job = HashJob(ref_seq, ins, read_pos, seg.ref_start, seg, "")
+                    deferred.append(job)
+                    helpers.append(job)
+                    continue
                 _m, hits = hashplot_unmapped(ref_seq, ins, options.k_size, options.min_accept)
                 hs = _hash_hits_to_segs(hits, read_pos, seg.ref_start, seg, "")
                 helpers.extend(hs)

@@ -11,7 +11,8 @@ with vectorised masks.
 """
 import numpy as np
 
-from .analyze_reads import analyze_between_aligns, analyze_gap, analyze_inside_align
+from ..segmentplot import run_hash_lineplot
+from .analyze_reads import HashJob, analyze_between_aligns, analyze_gap, analyze_inside_align
 from .classes import by_read_pos
 from .graph import build_graph
 
@@ -27,6 +28,31 @@ def _emit(ctx, cur, nxt, helpers, next_is_last):
     if sig is not None:
         sig.set_graph(graph)
         signatures.append(sig)
+
+
+def _finish_read(env, primary, qname, segs):
+    """The segments of one read, complete -> its Signatures (:218-308), for the second phase of a --hash window: the tail of
+    the loop in :func:`analyze_alignments`, which stays inline there (the single-pass path is the hot one)."""
+    signatures, want_graph, chrom_of, fetch_ref, sample, options, table = env
+    segs.sort(key=by_read_pos)
+    n = len(segs)
+    if n < 2:
+        return
+
+    whole_seq = table.query_sequence(primary) if want_graph else None
+    ctx = (signatures, want_graph, whole_seq, chrom_of, fetch_ref, sample, options, qname)
+    if n == 2:
+        _emit(ctx, segs[0], segs[1], (), True)
+        return
+    if segs[0].is_reverse:                                # :250-261
+        _emit(ctx, segs[0], segs[1], (), True)
+    if segs[-1].is_reverse:                               # :263-274
+        _emit(ctx, segs[-2], segs[-1], (), True)
+    main_idx = [i for i, s in enumerate(segs) if s.type == "main"]
+    for p in range(len(main_idx) - 1):                    # :287-308
+        i, j = main_idx[p], main_idx[p + 1]
+        if segs[j].q_start - segs[i].q_end >= -25:
+            _emit(ctx, segs[i], segs[j], segs[i + 1:j], p == len(main_idx) - 2)
 
 
 def analyze_alignments(rows, sample, options, part_num=0):
@@ -72,6 +98,11 @@ def analyze_alignments(rows, sample, options, part_num=0):
                                   table.mapq[sel_rows].tolist(), table.l_seq[sel_rows].tolist())))
     names = table.names
     want_graph = getattr(options, "graph", False)
+    # --hash: two phases -- the reads' segment lists are built with a HashJob placeholder for every re-alignment, the
+    # window's jobs are resolved together (one device launch), then every read is finished.  Job enumeration does not
+    # depend on job results, and nothing in front of _finish_read reads the lists.
+    deferred = [] if options.hash and run_hash_lineplot.batch_enabled() else None
+    reads = [] if deferred is not None else None
     for rid, lo, hi in zip(uniq[cand_ids].tolist(), bounds[0].tolist(), bounds[1].tolist()):
         primary = -1
         supp = []
@@ -86,15 +117,18 @@ def analyze_alignments(rows, sample, options, part_num=0):
             # SEQ '*' on the primary: the reference slices None (analyze_reads.py:667) and the window fails
             raise TypeError("'NoneType' object is not subscriptable")
         qname = names[rid]
-        majors, minors = analyze_between_aligns(primary, supp, table, options, sample, cols)
+        majors, minors = analyze_between_aligns(primary, supp, table, options, sample, cols, deferred)
         segs = list(minors)
         for seg in majors:                                    # :201-216
-            pieces, helpers = analyze_inside_align(seg, sample.gaps_of(seg.aln), options, sample)
+            pieces, helpers = analyze_inside_align(seg, sample.gaps_of(seg.aln), options, sample, deferred)
             if pieces is None:
                 segs.append(seg)
             else:
                 segs.extend(pieces)
                 segs.extend(helpers)
+        if deferred is not None:
+            reads.append((primary, qname, segs))
+            continue
         segs.sort(key=by_read_pos)
         n = len(segs)
         if n < 2:
@@ -114,4 +148,19 @@ def analyze_alignments(rows, sample, options, part_num=0):
             i, j = main_idx[p], main_idx[p + 1]
             if segs[j].q_start - segs[i].q_end >= -25:
                 _emit(ctx, segs[i], segs[j], segs[i + 1:j], p == len(main_idx) - 2)
+    if deferred is not None:
+        env = (signatures, want_graph, chrom_of, fetch_ref, sample, options, table)
+        # second phase: every put-off re-alignment of the window in ONE batch, its helper segments spliced in where the
+        # sequential code appends them (the sort below is stable and ties exist), then the reads in their order
+        hits = run_hash_lineplot.hashplot_unmapped_many([(job.ref_seq, job.piece) for job in deferred], options.k_size,
+                                                        options.min_accept) if deferred else []
+        found = dict(zip(map(id, deferred), hits))
+        for primary, qname, segs in reads:
+            full = []
+            for item in segs:
+                if type(item) is HashJob:
+                    full.extend(item.segs(found[id(item)]))
+                else:
+                    full.append(item)
+            _finish_read(env, primary, qname, full)
     return signatures

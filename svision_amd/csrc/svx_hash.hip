@@ -225,7 +225,64 @@ void hash_seeds_kernel(const uint8_t* __restrict__ bases, const Job* __restrict_
     if (tid == 0) { counts[2 * blockIdx.x] = total_a; counts[2 * blockIdx.x + 1] = total_b; }
 }
 
+// ---- compacted read-back: the rows the two lists of every job really hold, densely, with where each list starts ----
+// A list that overflowed (count > hit_cap) contributes no row: its job is redone on the host, which sees it in `counts`.
+__device__ inline uint32_t list_rows(const Job* jobs, const uint32_t* counts, uint32_t l)
+{
+    const uint32_t c = counts[l];
+    return c > jobs[l >> 1].hit_cap ? 0u : c;
+}
+
+// one workgroup walks the 2 * n_jobs lists in chunks of BLOCK with a running carry: row_off[l] = rows in front of list l
+__global__ __launch_bounds__(BLOCK)
+void hash_row_offsets_kernel(const Job* __restrict__ jobs, const uint32_t* __restrict__ counts, uint32_t n_lists, uint32_t* __restrict__ row_off)
+{
+    __shared__ uint32_t warp_sums[BLOCK / 64];
+    uint32_t carry = 0;
+    for (uint32_t chunk = 0; chunk < n_lists; chunk += BLOCK) {
+        const uint32_t l = chunk + threadIdx.x;
+        const uint32_t v = l < n_lists ? list_rows(jobs, counts, l) : 0u;
+        uint32_t before;
+        const uint32_t sum = block_scan(v, warp_sums, before);
+        if (l < n_lists) row_off[l] = carry + before;
+        carry += sum;
+    }
+    if (threadIdx.x == 0) row_off[n_lists] = carry;
+}
+
+// one workgroup per list: its rows (16 bytes each) to packed[row_off[l] ...]; rows that would lie behind `packed_cap` are
+// left out (the host sees row_off[n_lists] > packed_cap and packs again into a larger array)
+__global__ __launch_bounds__(BLOCK)
+void hash_pack_rows_kernel(const Job* __restrict__ jobs, const uint32_t* __restrict__ counts, const int4* __restrict__ hits,
+                           const uint32_t* __restrict__ row_off, int4* __restrict__ packed, uint64_t packed_cap)
+{
+    const uint32_t l = blockIdx.x;
+    const Job job = jobs[l >> 1];
+    const uint32_t n = list_rows(jobs, counts, l);
+    const int4* src = hits + job.hit_off + ((l & 1u) ? (uint64_t)job.hit_cap : 0ull);
+    const uint64_t dst = row_off[l];
+    for (uint32_t r = threadIdx.x; r < n; r += BLOCK)
+        if (dst + r < packed_cap) packed[dst + r] = src[r];
+}
+
 }  // namespace
+
+extern "C" int svx_hash_pack_hits(const SvxHashJob* d_jobs, uint32_t n_jobs, const int32_t* d_hits, const uint32_t* d_counts,
+                                  uint32_t* d_row_off, int32_t* d_packed, uint64_t packed_cap, void* stream)
+{
+    if (!d_row_off) return SVX_EINVAL;
+    if (n_jobs > 0x3fffffffu) return SVX_EINVAL;                                     // 2 * n_jobs + 1 offsets of 32 bits
+    if (n_jobs && (!d_jobs || !d_hits || !d_counts)) return SVX_EINVAL;
+    if (packed_cap && !d_packed) return SVX_EINVAL;
+    if (((uintptr_t)d_hits | (uintptr_t)d_packed) & 15) return SVX_EINVAL;           // rows move as 16-byte words
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const Job* jobs = reinterpret_cast<const Job*>(d_jobs);
+    hipLaunchKernelGGL(hash_row_offsets_kernel, dim3(1), dim3(BLOCK), 0, s, jobs, d_counts, 2 * n_jobs, d_row_off);
+    if (n_jobs)
+        hipLaunchKernelGGL(hash_pack_rows_kernel, dim3(2 * n_jobs), dim3(BLOCK), 0, s, jobs, d_counts, reinterpret_cast<const int4*>(d_hits),
+                           d_row_off, reinterpret_cast<int4*>(d_packed), packed_cap);
+    return hipGetLastError() == hipSuccess ? SVX_OK : SVX_ELAUNCH;
+}
 
 extern "C" int svx_hash_seeds(const uint8_t* d_bases, const SvxHashJob* d_jobs, uint32_t n_jobs, uint64_t* d_table,
                               int32_t* d_hits, uint32_t* d_counts, uint32_t k, uint32_t window, uint32_t max_x_len, void* stream)

@@ -405,43 +405,212 @@ def pack_bases(seq):
     return None if (codes == 255).any() else codes
 
 
-def hash_seeds(jobs, k, window, device):
+HASH_BUDGET = 4 << 30                # bytes of scratch table + hit lists one launch may ask for (a 20 kb window: 6.5 MB; 233 jobs on
+                                     # windows of 10-19 kb, the jobs of a 1 Mb HiFi window: ~1.3 GB -- one launch)
+HASH_PACKED_ROWS = 4096              # rows the first pack of a launch has room for (a window's jobs return a few hundred)
+
+
+def hash_job_arrays(jobs):
+    """[(x_codes, y_codes), ...] -> (bases uint8: all sequences end to end, desc int64 [n,4] = x_off, x_len, y_off, y_len):
+    the form :func:`hash_seeds_async` takes and the helpers' pipe carries."""
+    desc = np.zeros((len(jobs), 4), np.int64)
+    lens = np.fromiter((len(s) for job in jobs for s in job), np.int64, 2 * len(jobs))
+    offs = np.cumsum(lens) - lens
+    desc[:, 0], desc[:, 1], desc[:, 2], desc[:, 3] = offs[0::2], lens[0::2], offs[1::2], lens[1::2]
+    parts = [s for job in jobs for s in job]
+    return (np.concatenate(parts).astype(np.uint8, copy=False) if parts else np.zeros(0, np.uint8)), desc
+
+
+def hash_hit_caps(desc):
+    """Capacity of each of a job's two hit lists (a count above it: the job is redone on the host)."""
+    return 4 * np.asarray(desc, np.int64).reshape(-1, 4)[:, 3] + 64
+
+
+def hash_split_rows(desc, counts, row_off, rows):
+    """What a finished :class:`HashSeedsHandle` returns -> list of (hits_a, hits_b) int32 [n,4] per job, None for a job
+    with an overflowed list."""
+    counts = np.asarray(counts, np.int64)
+    cap = hash_hit_caps(desc)
+    if counts.size != 2 * cap.size or len(row_off) != counts.size + 1:
+        raise _lib.SvxError("hash_split_rows: %d counts / %d offsets for %d jobs" % (counts.size, len(row_off), cap.size))
+    rows = np.asarray(rows, np.int32).reshape(-1, 4)
+    off = np.asarray(row_off, np.int64).tolist()
+    if off[-1] != len(rows):
+        raise _lib.SvxError("hash_split_rows: %d rows where the offsets end at %d" % (len(rows), off[-1]))
+    over = ((counts[0::2] > cap) | (counts[1::2] > cap)).tolist()
+    return [None if over[j] else (rows[off[2 * j]:off[2 * j + 1]], rows[off[2 * j + 1]:off[2 * j + 2]]) for j in range(cap.size)]
+
+
+_HASH_STREAMS = {}
+
+
+def _hash_stream(dev):
+    """The re-aligner's own stream on ``dev``: its uploads, launches and read-backs wait for no other stream's work."""
+    key = (dev.type, dev.index if dev.index is not None else torch.cuda.current_device())
+    if key not in _HASH_STREAMS:
+        _HASH_STREAMS[key] = torch.cuda.Stream(dev)
+    return _HASH_STREAMS[key]
+
+
+class _HashLaunch:
+    """One launch of a :class:`HashSeedsHandle` under way: jobs [lo, lo + m) of the batch, its output array on the device
+    (counts [2 m], row_off [2 m + 1], padding to ``hdr`` words, then ``rows`` packed rows), and the read-back of it."""
+    __slots__ = ("index", "lo", "m", "hdr", "rows", "d_out", "h_out", "event")
+
+    def __init__(self, index, lo, m, hdr, rows, d_out):
+        self.index, self.lo, self.m, self.hdr, self.rows, self.d_out = index, lo, m, hdr, rows, d_out
+        self.h_out = self.event = None
+
+
+class HashSeedsHandle:
+    """A batch of re-aligner jobs under way on the device (:func:`hash_seeds_async`).  ``done()`` never blocks;
+    ``result()`` waits -> (counts uint32 [2 n], row_off uint32 [2 n + 1], rows int32 [total, 4]): the lists A0 B0 A1 B1 ...
+    compacted (``svx_hash_pack_hits``), to be cut up by :func:`hash_split_rows`.  ``launches``: seed launches so far.
+
+    A batch whose scratch table and hit lists exceed ``budget`` bytes runs as several launches over one scratch area; the
+    next is enqueued when the host has seen that the rows of the one before fitted its packed array (otherwise the pack,
+    not the seeds, is repeated with a larger one).  A single launch -- a window's jobs -- is enqueued whole: upload,
+    seeds, pack, download, one event."""
+
+    def __init__(self, bases, desc, k, window, device, budget=HASH_BUDGET, packed_rows=HASH_PACKED_ROWS):
+        self._lib = _lib.load()
+        dev = self._dev = torch.device(device)
+        if dev.type != "cuda":
+            raise _lib.SvxError("hash_seeds: needs a device (got %s); the hot path has no CPU fallback" % (dev,))
+        bases = np.ascontiguousarray(bases, np.uint8).reshape(-1)
+        desc = np.ascontiguousarray(desc, np.int64).reshape(-1, 4)
+        n = self._n = len(desc)
+        self._k, self._window, self._packed_rows = int(k), int(window), max(1, int(packed_rows))
+        self.launches = 0
+        self._parts, self._cur, self._result = [], None, None
+        x_off, x_len, y_off, y_len = (desc[:, c] for c in range(4))
+        if n and ((desc < 0).any() or (x_off + x_len > bases.size).any() or (y_off + y_len > bases.size).any()):
+            raise _lib.SvxError("hash_seeds: a job's sequence lies outside the base array")
+        if n and int(x_len.max()) > HASH_MAX_X:
+            raise _lib.SvxError("hash_seeds: piece longer than %d bases" % HASH_MAX_X)
+        if n and int(y_len.max()) >= 1 << 26:
+            raise _lib.SvxError("hash_seeds: window longer than 2^26 bases")
+        if n == 0:
+            self._result = (np.zeros(0, np.uint32), np.zeros(1, np.uint32), np.zeros((0, 4), np.int32))
+            return
+        want = 8 * np.maximum(y_len, 1)
+        slots = np.left_shift(1, np.ceil(np.log2(want)).astype(np.int64))          # power of two >= 8 * len(y)
+        slots = np.where(slots < want, slots * 2, slots)
+        cap = hash_hit_caps(desc)
+        cost = (slots + 2 * cap) * 16
+        # consecutive jobs to a launch while they fit the budget (a job larger than it goes alone)
+        self._chunks, lo, used = [], 0, 0
+        for j, c in enumerate(cost.tolist()):
+            if j > lo and used + c > budget:
+                self._chunks.append((lo, j))
+                lo, used = j, 0
+            used += c
+        self._chunks.append((lo, n))
+        jd = np.zeros(n, HASH_JOB_DTYPE)
+        jd["x_off"], jd["x_len"], jd["y_off"], jd["y_len"], jd["table_slots"], jd["hit_cap"] = x_off, x_len, y_off, y_len, slots, cap
+        max_slots = max_rows = 0
+        for lo, hi in self._chunks:
+            jd["table_off"][lo:hi] = np.cumsum(slots[lo:hi]) - slots[lo:hi]
+            jd["hit_off"][lo:hi] = 2 * (np.cumsum(cap[lo:hi]) - cap[lo:hi])
+            max_slots, max_rows = max(max_slots, int(slots[lo:hi].sum())), max(max_rows, 2 * int(cap[lo:hi].sum()))
+        self._stream = _hash_stream(dev)
+        raw = jd.view(np.uint8).reshape(-1)
+        with torch.cuda.stream(self._stream):
+            # one pinned staging buffer, one upload: the job records (SvxHashJob), then the bases (+ 16 bytes of slack)
+            self._h_in = torch.empty(raw.size + bases.size + 16, dtype=torch.uint8, pin_memory=True)
+            h = self._h_in.numpy()
+            h[:raw.size], h[raw.size:raw.size + bases.size], h[raw.size + bases.size:] = raw, bases, 0
+            self._d_in = torch.empty(self._h_in.numel(), dtype=torch.uint8, device=dev)
+            self._d_in.copy_(self._h_in, non_blocking=True)
+            self._d_table = torch.empty(2 * max_slots, dtype=torch.int64, device=dev)
+            self._d_hits = torch.empty(4 * max_rows, dtype=torch.int32, device=dev)
+        self._bases_at = raw.size
+        self._start(0)
+
+    def _start(self, ci):
+        lo, hi = self._chunks[ci]
+        m = hi - lo
+        hdr = (4 * m + 1 + 3) // 4 * 4                                 # counts [2 m], row_off [2 m + 1], then 16-byte aligned rows
+        with torch.cuda.stream(self._stream):
+            d_out = torch.empty(hdr + 4 * self._packed_rows, dtype=torch.int32, device=self._dev)
+            sp = ctypes.c_void_p(self._stream.cuda_stream)
+            rc = self._lib.svx_hash_seeds(self._d_in.data_ptr() + self._bases_at, self._d_in.data_ptr() + HASH_JOB_DTYPE.itemsize * lo, m, self._d_table.data_ptr(),
+                                          self._d_hits.data_ptr(), d_out.data_ptr(), self._k, self._window, HASH_MAX_X, sp)
+            _lib.check(rc, "svx_hash_seeds")
+            self.launches += 1
+        self._cur = _HashLaunch(ci, lo, m, hdr, self._packed_rows, d_out)
+        self._pack()
+
+    def _pack(self):
+        """Pack the current launch's lists into its output array and read that back (again, after the array has grown)."""
+        cur = self._cur
+        with torch.cuda.stream(self._stream):
+            sp = ctypes.c_void_p(self._stream.cuda_stream)
+            out = cur.d_out.data_ptr()
+            rc = self._lib.svx_hash_pack_hits(self._d_in.data_ptr() + HASH_JOB_DTYPE.itemsize * cur.lo, cur.m, self._d_hits.data_ptr(), out,
+                                              out + 4 * 2 * cur.m, out + 4 * cur.hdr, cur.rows, sp)
+            _lib.check(rc, "svx_hash_pack_hits")
+            cur.h_out = torch.empty(cur.d_out.numel(), dtype=torch.int32, pin_memory=True)
+            cur.h_out.copy_(cur.d_out, non_blocking=True)
+            cur.event = torch.cuda.Event()
+            cur.event.record(self._stream)
+
+    def _advance(self):
+        """The launch under way has finished: keep its rows (or pack again into a larger array), start the next."""
+        cur = self._cur
+        m, hdr = cur.m, cur.hdr
+        h = cur.h_out.numpy()
+        total = int(h[4 * m]) & 0xFFFFFFFF
+        if total > cur.rows:
+            with torch.cuda.stream(self._stream):
+                bigger = torch.empty(hdr + 4 * total, dtype=torch.int32, device=self._dev)
+                bigger[:2 * m].copy_(cur.d_out[:2 * m])                 # the counts: the pack reads them from its output array
+            cur.rows, cur.d_out = total, bigger
+            self._pack()
+            return
+        self._parts.append((h[:2 * m].view(np.uint32).copy(), h[2 * m:4 * m + 1].view(np.uint32).copy(), h[hdr:hdr + 4 * total].reshape(-1, 4).copy()))
+        self._cur = None
+        if cur.index + 1 < len(self._chunks):
+            self._start(cur.index + 1)
+            return
+        counts = np.concatenate([p[0] for p in self._parts])
+        row_off = np.zeros(2 * self._n + 1, np.uint32)
+        at = base = 0
+        for _c, off, _r in self._parts:
+            row_off[at:at + off.size] = off + np.uint32(base)
+            at, base = at + off.size - 1, base + int(off[-1])
+        self._result = (counts, row_off, np.concatenate([p[2] for p in self._parts]))
+        self._parts = self._d_in = self._h_in = self._d_table = self._d_hits = None
+
+    def done(self):
+        while self._result is None and self._cur.event.query():
+            self._advance()
+        return self._result is not None
+
+    def result(self):
+        while self._result is None:
+            self._cur.event.synchronize()
+            self._advance()
+        return self._result
+
+
+def hash_seeds_async(bases_u8, job_desc, k, window, device, budget=HASH_BUDGET, packed_rows=HASH_PACKED_ROWS):
+    """One contiguous array of packed bases (pack_bases symbols) + int64 [n,4] job descriptors (x_off, x_len, y_off, y_len:
+    :func:`hash_job_arrays`) -> :class:`HashSeedsHandle`.  Upload, ``svx_hash_seeds``, ``svx_hash_pack_hits`` and the
+    read-back of the packed rows are enqueued on the re-aligner's own stream, through pinned memory (a pageable copy
+    would wait behind the CNN's queued launches, see Sample.from_table); nothing here waits for another stream."""
+    return HashSeedsHandle(bases_u8, job_desc, k, window, device, budget, packed_rows)
+
+
+def hash_seeds(jobs, k, window, device, budget=HASH_BUDGET, packed_rows=HASH_PACKED_ROWS):
     """jobs: list of (x_codes, y_codes) uint8 arrays (pack_bases) -> list of (hits_a, hits_b) int32 arrays [n,4]
     = {y position, x position or position in x's reverse complement, match length, forward}, or None for a job whose
-    hit lists overflowed.  One launch for the whole batch.  See include/svx.h svx_hash_seeds."""
-    lib = _lib.load()
+    hit lists overflowed.  The synchronous form of :func:`hash_seeds_async`: one launch for the whole batch unless its
+    scratch exceeds ``budget`` bytes (then several, with the same results).  See include/svx.h svx_hash_seeds."""
     if not jobs:
         return []
-    dev = torch.device(device)
-    desc = np.zeros(len(jobs), HASH_JOB_DTYPE)
-    parts, off, slots, hit_off = [], 0, 0, 0
-    for j, (x, y) in enumerate(jobs):
-        if len(x) > HASH_MAX_X:
-            raise _lib.SvxError("hash_seeds: piece longer than %d bases" % HASH_MAX_X)
-        t = 1
-        while t < 8 * max(len(y), 1):
-            t <<= 1
-        cap = 4 * len(y) + 64
-        desc[j] = (off, off + len(x), len(x), len(y), slots, t, cap, hit_off)
-        parts += [x, y]
-        off += len(x) + len(y)
-        slots += t
-        hit_off += 2 * cap
-    d_bases = torch.from_numpy(np.concatenate(parts + [np.zeros(16, np.uint8)])).to(dev)
-    d_jobs = torch.from_numpy(desc.view(np.uint8).copy()).to(dev)
-    d_table = torch.empty(slots * 2, dtype=torch.int64, device=dev)
-    d_hits = torch.empty(hit_off * 4, dtype=torch.int32, device=dev)
-    d_counts = torch.empty(2 * len(jobs), dtype=torch.int32, device=dev)
-    rc = lib.svx_hash_seeds(d_bases.data_ptr(), d_jobs.data_ptr(), len(jobs), d_table.data_ptr(), d_hits.data_ptr(), d_counts.data_ptr(),
-                            int(k), int(window), HASH_MAX_X, _stream_ptr(dev))
-    _lib.check(rc, "svx_hash_seeds")
-    counts = d_counts.cpu().numpy().astype(np.int64)
-    hits = d_hits.cpu().numpy().reshape(-1, 4)
-    out = []
-    for j in range(len(jobs)):
-        na, nb, cap, ho = int(counts[2 * j]), int(counts[2 * j + 1]), int(desc[j]["hit_cap"]), int(desc[j]["hit_off"])
-        out.append(None if na > cap or nb > cap else (hits[ho:ho + na], hits[ho + cap:ho + cap + nb]))
-    return out
+    bases, desc = hash_job_arrays(jobs)
+    return hash_split_rows(desc, *hash_seeds_async(bases, desc, k, window, device, budget, packed_rows).result())
 
 
 def bgzf_block_table(raw):

@@ -413,10 +413,32 @@ def _worker_main(conn):
        owner -> ("chrom", key, meta) / ("drop", key)   a chromosome of a file-driven run arrives in / leaves shared memory
                                                         (ingest.ChromosomeFeed); key None = the Sample of the fork / "scan"
        owner -> ("opt", name, value)   a pool option changed (HelperPool.set_option: want_tsv on for bench.py's parity leg)
-       owner -> ("stop",)"""
+       owner -> ("stop",)
+       --hash, inside the collection of a "win":
+                    helper -> ("hash", wid, k, min_accept, bases uint8, desc int64[n,4])   the window's re-aligner jobs, packed
+       owner -> ("hashres", wid, counts, row_off, rows)   their raw hit lists (kernels.HashSeedsHandle.result); filter, merge
+                                                          and select_longest are replayed here.  counts None: the owner could
+                                                          not run them (logged there); the helper takes the host aligner
+    Neither side can block on a full pipe there: the helper sends "hash" while the owner is in its loop, which reads every
+    busy helper's pipe and sends a collecting helper nothing but the few small control messages below; the owner sends
+    "hashres" only to a helper that has sent "hash" and since then does nothing but read its pipe until that reply."""
     sample, options = _POOL_STATE["sample"], _POOL_STATE["options"]
     from .segmentplot import run_hash_lineplot
     run_hash_lineplot.DEVICE = None           # helpers never touch the GPU
+    backlog = collections.deque()             # control messages that arrived in front of a "hashres": handled in their turn
+    current = [None]                          # the window being collected
+
+    def remote_hash(bases, desc, k, min_accept):
+        """The device executor of the owner, for the jobs of the window this helper is collecting."""
+        conn.send(("hash", current[0], k, min_accept, bases, desc))
+        while True:
+            msg = conn.recv()
+            if msg[0] == "hashres" and msg[1] == current[0]:
+                return None if msg[2] is None else (msg[2], msg[3], msg[4])     # None: the owner could not run them -> host aligner here
+            backlog.append(msg)                # "chrom", "drop", "opt" (or "stop"): after this window
+
+    # (SVX_HASH_BATCH=0: the helpers run the host aligner job by job, as before the window's jobs went to the owner)
+    run_hash_lineplot.REMOTE = remote_hash if run_hash_lineplot.batch_enabled() else None
     if sample is not None:
         sample.device_buffers = None          # a helper forked from a live owner: its copy of the Sample is host-only
     # The cyclic collector finds nothing to free here (segments, signatures and lines die by reference count) but its
@@ -431,7 +453,7 @@ def _worker_main(conn):
     samples = {None: sample}
     header_dict = None
     while True:
-        msg = conn.recv()
+        msg = backlog.popleft() if backlog else conn.recv()
         if msg[0] == "stop":
             return
         if msg[0] == "chrom":
@@ -462,6 +484,7 @@ def _worker_main(conn):
             _t, wid, key, chrom, start, end, scan = msg
             t0 = time.perf_counter()
             smp = samples[key]
+            current[0] = wid
             if scan is not None:
                 smp.apply_window_scan(*scan)
 
@@ -700,6 +723,9 @@ class PooledHotPath(HotPath):
         remaining = len(windows)
         kept = {}                     # wid -> [(window offset, classes, probs)] (keep_predictions)
         prof = self.owner_profile = collections.defaultdict(float)
+        hashing = collections.deque()   # (conn index, wid, kernels.HashSeedsHandle) of the helpers' --hash requests under way
+        if self.options.hash:
+            prof.update({"hash.requests": 0, "hash.jobs": 0, "hash.launches": 0, "hash.wait_s": 0.0})
         clock = time.perf_counter
         t_loop = clock()
 
@@ -805,12 +831,29 @@ class PooledHotPath(HotPath):
                     forward(wid)
                 prof["last_fetch_at"] = clock() - t_loop
             t = lap("fetch+send", t)
+            for _n in range(len(hashing)):                            # re-aligner batches: on a stream of their own, polled like the launches
+                ci, wid, handle = hashing.popleft()
+                try:
+                    ready = handle.done()
+                    reply = ("hashres", wid) + handle.result() if ready else None
+                except Exception as exc:                              # noqa: BLE001 -- e.g. out of device memory: the helper re-aligns on the host
+                    logging.error("[ERROR]: %s. --hash jobs of window %s go back to its helper", exc, wid)
+                    ready, reply = True, ("hashres", wid, None, None, None)
+                    prof["hash.failed"] += 1
+                if ready:
+                    self.conns[ci].send(reply)
+                    prof["hash.launches"] += handle.launches
+                else:
+                    hashing.append((ci, wid, handle))
+            if prof.get("hash.requests"):
+                prof["hash.wait_s"] += clock() - t
+                t = clock()
             waiting = [self.conns[ci] for ci in busy]
             if not waiting and not inflight and not pending.images and nxt < len(windows):
                 self.feed.poll(block=True)                            # nothing to do but wait for the next chromosome
                 lap("feed.wait", t)
                 continue
-            got = mpc.wait(waiting, timeout=0.0005 if inflight or pending.images else (0.002 if nxt < len(windows) and idle else 0.05))
+            got = mpc.wait(waiting, timeout=0.0005 if inflight or pending.images or hashing else (0.002 if nxt < len(windows) and idle else 0.05))
             lap("wait", t)
             if not got and not inflight and not pending.images:
                 dead = [ci for ci in busy if not self.procs[ci].is_alive()]
@@ -833,6 +876,18 @@ class PooledHotPath(HotPath):
                         continue
                     w["total"] = n_images
                     forward(wid)
+                elif msg[0] == "hash":                                # a collecting helper's re-aligner jobs: enqueued, answered above
+                    _t, wid, k, min_accept, bases, desc = msg
+                    t_h = clock()
+                    prof["hash.requests"] += 1
+                    prof["hash.jobs"] += len(desc)
+                    try:
+                        hashing.append((ci, wid, kernels.hash_seeds_async(bases, desc, k, min_accept, self.device)))
+                    except Exception as exc:                          # noqa: BLE001 -- costs the request, not the run: answered at once
+                        logging.error("[ERROR]: %s. --hash jobs of window %s go back to its helper", exc, wid)
+                        c.send(("hashres", wid, None, None, None))
+                        prof["hash.failed"] += 1
+                    prof["hash.wait_s"] += clock() - t_h
                 else:
                     _t, wid, vcf, scores, n_sites, n_images, tsv, head, tail, host_s, edges = msg
                     prof["helper.collect_s"] += host_s[0]             # host seconds inside the helpers

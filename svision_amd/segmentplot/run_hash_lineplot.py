@@ -3,6 +3,8 @@
 Mirror of the reference's src/segmentplot/run_hash_lineplot.py (``hashplot_unmapped`` :52-85,
 ``select_longest`` :8-33).  ``cord_to_segments`` lives in :mod:`.classes`.
 """
+import os
+
 from .classes import Segment, cord_to_segments  # noqa: F401  (re-exported like upstream)
 from .hash_aligner import HashAligner
 
@@ -21,6 +23,13 @@ def select_longest(segments):
 
 
 DEVICE = None        # torch.device of the process that owns a GPU (set by Sample.from_table); None in the forked host helpers
+REMOTE = None        # in a host helper: callable (bases, desc, k, window) -> (counts, row_off, rows) or None, the owner's device by pipe (pipeline._worker_main)
+
+
+def batch_enabled():
+    """SVX_HASH_BATCH=0: the collection re-aligns piece by piece where the pieces arise (a launch per job in the process that
+    owns the device, the host aligner in the helpers) instead of a window's pieces together.  Read at call time."""
+    return os.environ.get("SVX_HASH_BATCH", "1") != "0"
 
 
 def hashplot_unmapped(ref, seq, k, min_accept):
@@ -48,13 +57,37 @@ def _hashplot_host(ref, seq, k, min_accept):
     return merged
 
 
+def hashplot_unmapped_many(pairs, k, min_accept):
+    """[(ref, seq), ...] -> [segments]: what :func:`hashplot_unmapped` gives for every pair, all pairs the device takes in one
+    batch (on ``DEVICE``, or on the owner's through ``REMOTE``), the others through the host passes in this process."""
+    got = hashplot_unmapped_batch(pairs, k, min_accept, DEVICE)
+    return [_hashplot_host(ref, seq, k, min_accept) if segs is None else segs for segs, (ref, seq) in zip(got, pairs)]
+
+
+def _replay(hits_a, hits_b, x_len, y_len, k, min_accept):
+    """The device's two raw hit lists of one job -> its segments, through the order-dependent host steps."""
+    self_pass = HashAligner(k, min_accept, 0, 2)
+    self_pass.compareDiffSegs = None
+    for i, pos, length, fwd in hits_a.tolist():          # the self pass: its off-diagonal hits are the window's repeats
+        self_pass._keep(Segment(pos, i, length, True, 0) if fwd else Segment((y_len - 1) - pos, i, length, False, 0))
+    placer = HashAligner(k, min_accept, 0, 2)
+    placer.compareDiffSegs = self_pass.getSelfDiffSegs()
+    for i, pos, length, fwd in hits_b.tolist():
+        placer._keep(Segment(pos, i, length, True, 0) if fwd else Segment((x_len - 1) - pos, i, length, False, 0))
+    merged = placer.getMergeSegments()
+    if len(merged) >= 2:
+        merged = select_longest(merged)
+    return merged
+
+
 def hashplot_unmapped_batch(pairs, k, min_accept, device):
-    """[(ref, seq), ...] -> [segments or None]: every pair's seed-and-extend passes in ONE device launch.
-    None = the pair cannot go through the device kernel (see :func:`hashplot_unmapped`)."""
+    """[(ref, seq), ...] -> [segments or None]: every pair's seed-and-extend passes in ONE call of the device executor
+    (``kernels.hash_seeds``; with ``device`` None in a helper process, the owner's executor through ``REMOTE``).
+    None = the pair cannot go through the device kernel (see :func:`hashplot_unmapped`), or there is no device to ask."""
     from .. import kernels
     out = [None] * len(pairs)
     jobs, where = [], []
-    if not (2 <= k <= 13):
+    if not (2 <= k <= 13) or (device is None and REMOTE is None):
         return out
     for n, (ref, seq) in enumerate(pairs):
         if len(seq) > kernels.HASH_MAX_X:
@@ -64,20 +97,17 @@ def hashplot_unmapped_batch(pairs, k, min_accept, device):
             continue
         jobs.append((x, y))
         where.append(n)
-    for n, res, (x, y) in zip(where, kernels.hash_seeds(jobs, k, min_accept, device), jobs):
-        if res is None:
-            continue
-        hits_a, hits_b = res
-        self_pass = HashAligner(k, min_accept, 0, 2)
-        self_pass.compareDiffSegs = None
-        for i, pos, length, fwd in hits_a.tolist():          # the self pass: its off-diagonal hits are the window's repeats
-            self_pass._keep(Segment(pos, i, length, True, 0) if fwd else Segment((len(y) - 1) - pos, i, length, False, 0))
-        placer = HashAligner(k, min_accept, 0, 2)
-        placer.compareDiffSegs = self_pass.getSelfDiffSegs()
-        for i, pos, length, fwd in hits_b.tolist():
-            placer._keep(Segment(pos, i, length, True, 0) if fwd else Segment((len(x) - 1) - pos, i, length, False, 0))
-        merged = placer.getMergeSegments()
-        if len(merged) >= 2:
-            merged = select_longest(merged)
-        out[n] = merged
+    if device is not None:
+        results = kernels.hash_seeds(jobs, k, min_accept, device)
+    elif jobs:
+        bases, desc = kernels.hash_job_arrays(jobs)
+        lists = REMOTE(bases, desc, k, min_accept)
+        if lists is None:                                      # the owner could not run them: every pair takes the host passes
+            return out
+        results = kernels.hash_split_rows(desc, *lists)
+    else:
+        results = []
+    for n, res, (x, y) in zip(where, results, jobs):
+        if res is not None:
+            out[n] = _replay(res[0], res[1], len(x), len(y), k, min_accept)
     return out
