@@ -50,7 +50,8 @@ struct Arena {
     std::string_view keep(std::string_view s)
     {
         if (s.size() > SLAB) { slabs.emplace_back(new char[s.size()]); memcpy(slabs.back().get(), s.data(), s.size()); used = SLAB; return {slabs.back().get(), s.size()}; }
-        if (used + s.size() > SLAB) { slabs.emplace_back(new char[SLAB]); used = 0; }
+        // (slabs.empty(): an empty name -- l_read_name 1 -- as a file's first fits into the room no slab has)
+        if (slabs.empty() || used + s.size() > SLAB) { slabs.emplace_back(new char[SLAB]); used = 0; }
         char* at = slabs.back().get() + used;
         memcpy(at, s.data(), s.size());
         used += s.size();

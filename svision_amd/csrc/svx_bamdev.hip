@@ -80,13 +80,18 @@ void bam_walk_count_kernel(const uint8_t* __restrict__ raw, const uint64_t* __re
     if (i >= n_starts) return;
     uint64_t p = starts[i];
     const uint64_t end = starts[i + 1];
+    // A record is judged against the end of the PART (the last start), not against the next start: a well-formed record that
+    // runs over the next start is status 1 -- what a stale index looks like --, and only what does not fit the part itself
+    // is malformed.  Nothing behind the part's end is read.
+    const uint64_t part_end = starts[n_starts];
     uint64_t n = 0, words = 0, name_bytes = 0, status = 0, bases = 0;
     while (p < end) {
-        if (p + 36 > end) { status = 2; break; }
+        if (p + 36 > part_end) { status = 2; break; }
         const uint32_t bs = ld32(raw + p);
         const uint8_t* rec = raw + p + 4;
         const uint32_t l_name = rec[8], n_cig = (uint32_t)rec[12] | (uint32_t)rec[13] << 8, l_seq = ld32(rec + 16);
-        if (bs < 32 || p + 4 + bs > end || 32ull + l_name + 4ull * n_cig + (l_seq + 1ull) / 2 + l_seq > bs) { status = 2; break; }
+        if (bs < 32 || p + 4 + bs > part_end || 32ull + l_name + 4ull * n_cig + (l_seq + 1ull) / 2 + l_seq > bs) { status = 2; break; }
+        if (p + 4 + bs > end) { status = 1; break; }
         uint32_t n_words = n_cig;
         if (is_cg_placeholder(rec, l_name, n_cig, l_seq)) {     // "<l_seq>S<span>N": the real CIGAR is in the CG tag
             if (find_cg_tag(rec, bs, l_name, n_cig, l_seq, &n_words) == nullptr) n_words = n_cig;     // (a look-alike without the tag is what it says: two operations, as in the host reader)

@@ -387,6 +387,9 @@ def test_feed_falls_back_to_the_host_engine_where_the_device_engine_refuses(tmp_
     with caplog.at_level(logging.WARNING):
         got, stats = _feed_tables(str(tmp_path / "bad.bam"), genome, "gpu")
     assert stats["engine"] == "gpu" and any("on the host" in r.getMessage() for r in caplog.records)
+    # the reason the warning carries names the index: the records are good, the walk stepped over the next start (status 1)
+    reasons = [r.getMessage() for r in caplog.records if "on the host" in r.getMessage()]
+    assert all("index does not match" in m and "malformed" not in m for m in reasons), reasons
     _same_feed_tables(got, want)
     # who decoded what: the refused reference (and, in its group, the one in front of it) by the host reader, the one behind it
     # by the device engine again
