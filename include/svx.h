@@ -289,7 +289,8 @@ int svx_span_position_distance(const double* d_start, const double* d_end, const
  * with length >= window; d_counts[2 j], d_counts[2 j + 1] = the numbers of hits of job j (they may exceed hit_cap:
  * the lists are then truncated and the caller must redo the job on the host).
  *   d_table  scratch, 16 bytes per slot, sum of table_slots slots; contents ignored
- * Requires repeat_thresh = 2 and mismatchNum = 0 (what hashplot_unmapped passes), 2 <= k <= 13, x_len <= max_x_len <= 2048. */
+ * Requires repeat_thresh = 2 and mismatchNum = 0 (what hashplot_unmapped passes), 2 <= k <= 13, x_len <= max_x_len <= 2048;
+ * a job with x_len > 2048 is left alone (svx_hash_seeds_long below takes it). */
 typedef struct SvxHashJob {
     uint64_t x_off, y_off;       /* byte offsets of the two sequences in d_bases                      */
     uint32_t x_len, y_len;
@@ -309,6 +310,18 @@ int svx_hash_seeds(const uint8_t* d_bases, const SvxHashJob* d_jobs, uint32_t n_
  * array (d_hits is untouched, the seeds are not repeated). */
 int svx_hash_pack_hits(const SvxHashJob* d_jobs, uint32_t n_jobs, const int32_t* d_hits, const uint32_t* d_counts,
                        uint32_t* d_row_off, int32_t* d_packed, uint64_t packed_cap, void* stream);
+/* (ABI 420, additive) svx_hash_seeds for pieces of 2,049 .. 65,536 bases: the same two lists per job, in the same order and
+ * record form, into the same d_hits / d_counts through the same SvxHashJob and d_table.  x's k-mer entries are sorted in
+ * tiles of 4,096 (the short kernel's LDS table) that are kept in a per-job workspace, so a job needs
+ * svx_hash_seeds_long_ws_bytes(x_len, y_len) = 16 x_len + 4 y_len bytes (rounded up to 16) of d_ws, at byte offset
+ * d_ws_off[j] (a multiple of 16; d_ws 16-byte aligned; contents ignored).  A batch's short and long jobs share one index space:
+ * launch svx_hash_seeds and svx_hash_seeds_long over the same d_jobs range -- this kernel leaves jobs with x_len <= 2048 (and
+ * their d_counts, d_ws_off) alone, svx_hash_seeds leaves those with x_len > 2048 alone.
+ * Requires 2 <= k <= 13, x_len <= max_x_len <= 65536. */
+size_t svx_hash_seeds_long_ws_bytes(uint32_t x_len, uint32_t y_len);
+int svx_hash_seeds_long(const uint8_t* d_bases, const SvxHashJob* d_jobs, uint32_t n_jobs, uint64_t* d_table,
+                        int32_t* d_hits, uint32_t* d_counts, void* d_ws, const uint64_t* d_ws_off,
+                        uint32_t k, uint32_t window, uint32_t max_x_len, void* stream);
 
 /* ---- host side: native BGZF/BAM ingestion (no device work) -------------------------------------------
  * Replaces the per-record pysam iteration of the reference (aln_file.fetch at

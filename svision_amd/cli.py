@@ -457,7 +457,14 @@ def _scores_of(pred_dir, chroms, options):
 
 
 def main(arguments=None):
-    run(parse_arguments(arguments))
+    options = parse_arguments(arguments)
+    if options.hash and os.environ.get("SVX_HASH_LONG", "1") != "0":
+        # pieces of up to 65,536 bases (--max_hash_len raised) re-align on the device too (svx_hash_seeds_long); a process
+        # global like DEVICE and REMOTE, set here, before run() forks the helpers (SVX_HASH_LONG=0: the host aligner, as before)
+        from . import kernels
+        from .segmentplot import run_hash_lineplot
+        run_hash_lineplot.MAX_PIECE = kernels.HASH_LONG_MAX_X
+    run(options)
 
 
 if __name__ == "__main__":

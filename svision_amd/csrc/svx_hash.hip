@@ -22,6 +22,12 @@
 //           of the reference's per-k-mer position lists -- and every non-avoided y position binary-searches them.
 // Hits are written in the reference's loop order (y position ascending, then list order): count -> workgroup prefix ->
 // emit, no atomics on the output, so the host can replay them through the order-dependent merge.
+// Pieces of 2,049 .. 65,536 bases (--max_hash_len raised) take svx_hash_seeds_long: the same passes, with x's k-mer entries cut
+// into tiles of 4,096 consecutive entries, each sorted in the same 32 KB of LDS and kept in a per-job global workspace; every
+// non-avoided y position counts its kept seeds tile by tile, one prefix over the y positions gives each its first row, and a
+// second walk over the stored tiles writes the rows.  Tiles are ascending ranges of insertion order, so a position's rows
+// come out in the same order as from one sorted table.  Both kernels run over the same job range of a batch; each leaves the
+// other's jobs alone.
 // Quirks kept: the k-mer loops stop at len - (k + 1); the extension never reads the last base; the seed rule looks at
 // the base before the k-mer on both sequences.
 #include <hip/hip_runtime.h>
@@ -32,6 +38,9 @@ namespace {
 
 constexpr int BLOCK = 256;
 constexpr int MAX_X = 2048;                       // longest piece handled on the device (--max_hash_len default: 1000); 32 KB of LDS
+constexpr int TILE = 2 * MAX_X;                   // entries of x's k-mer list sorted at a time (12 order bits)
+constexpr int LONG_MAX_X = 65536;                 // longest piece of the tiled kernel
+constexpr uint32_t AVOID = 0x80000000u;           // tiled kernel, per-position counter: the position's k-mer is avoided
 constexpr unsigned long long EMPTY = ~0ull;
 
 struct Job {                                      // mirrors SvxHashJob (include/svx.h)
@@ -103,6 +112,23 @@ __device__ inline uint32_t block_scan(uint32_t v, uint32_t* warp_sums, uint32_t&
     return total;
 }
 
+// xs[0 .. np2) ascending (np2 a power of two, the workgroup's threads all call it)
+__device__ inline void bitonic_sort(unsigned long long* xs, int np2, int tid)
+{
+    for (int size = 2; size <= np2; size <<= 1)
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            for (int e = tid; e < np2; e += BLOCK) {
+                const int p = e ^ stride;
+                if (p > e) {
+                    const unsigned long long a = xs[e], b = xs[p];
+                    const bool up = (e & size) == 0;
+                    if ((a > b) == up) { xs[e] = b; xs[p] = a; }
+                }
+            }
+            __syncthreads();
+        }
+}
+
 __global__ __launch_bounds__(BLOCK)
 void hash_seeds_kernel(const uint8_t* __restrict__ bases, const Job* __restrict__ jobs, unsigned long long* __restrict__ table,
                        int32_t* __restrict__ hits, uint32_t* __restrict__ counts, int k, int window)
@@ -110,6 +136,7 @@ void hash_seeds_kernel(const uint8_t* __restrict__ bases, const Job* __restrict_
     __shared__ unsigned long long xs[2 * MAX_X];          // pass B: x's k-mers, (code << 12 | insertion order)
     __shared__ uint32_t warp_sums[BLOCK / 64];
     const Job job = jobs[blockIdx.x];
+    if (job.x_len > (uint32_t)MAX_X) return;              // the tiled kernel's job (a longer piece would overrun xs)
     const uint8_t* x = bases + job.x_off;
     const uint8_t* y = bases + job.y_off;
     const int xl = (int)job.x_len, yl = (int)job.y_len;
@@ -154,18 +181,7 @@ void hash_seeds_kernel(const uint8_t* __restrict__ bases, const Job* __restrict_
         xs[e] = v;
     }
     __syncthreads();
-    for (int size = 2; size <= np2; size <<= 1)
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int e = tid; e < np2; e += BLOCK) {
-                const int p = e ^ stride;
-                if (p > e) {
-                    const unsigned long long a = xs[e], b = xs[p];
-                    const bool up = (e & size) == 0;
-                    if ((a > b) == up) { xs[e] = b; xs[p] = a; }
-                }
-            }
-            __syncthreads();
-        }
+    bitonic_sort(xs, np2, tid);
 
     // ---- seeds, in the reference's order: y position ascending, then table order; count -> prefix -> emit ----
     uint32_t total_a = 0, total_b = 0;
@@ -221,6 +237,158 @@ void hash_seeds_kernel(const uint8_t* __restrict__ bases, const Job* __restrict_
         }
         total_a += sum_a;
         total_b += sum_b;
+    }
+    if (tid == 0) { counts[2 * blockIdx.x] = total_a; counts[2 * blockIdx.x + 1] = total_b; }
+}
+
+// ---- pieces of more than MAX_X bases: x's k-mer list in tiles of TILE entries ----
+// y position i against one sorted tile (entries base .. base + tn of x's list): -> its kept seeds, in list order; with `out`
+// their rows go to out[slot ...] (those at or beyond `cap` are counted, not written)
+__device__ inline uint32_t tile_hits(const unsigned long long* xs, int tn, int base, const uint8_t* x, int xl, int nx, const uint8_t* y, int yl,
+                                     int i, int k, int window, unsigned long long code, int32_t* out, uint32_t slot, uint32_t cap)
+{
+    const unsigned long long key = code << 12;
+    int a = 0, b = tn;
+    while (a < b) { const int m = (a + b) >> 1; if (xs[m] < key) a = m + 1; else b = m; }
+    uint32_t n = 0;
+    for (int e = a; e < tn && (xs[e] >> 12) == code; ++e) {
+        const int ord = base + (int)(xs[e] & 0xfffu);
+        const int pos = ord >= nx ? -1 - (ord - nx) : ord;
+        const int len = seed(x, xl, y, yl, pos, i, k);
+        if (len >= window) {
+            if (out && slot + n < cap) {
+                int32_t* h = out + (size_t)(slot + n) * 4;
+                h[0] = i; h[1] = pos >= 0 ? pos : -1 - pos; h[2] = len; h[3] = pos >= 0 ? 1 : 0;
+            }
+            ++n;
+        }
+    }
+    return n;
+}
+
+// workspace of a job: the sorted tiles (8 bytes x 2 nx entries, within 16 x_len bytes), then one 32-bit word per y position:
+// its count of kept seeds, after the prefix its next row; AVOID set for a position that is not looked up.  A y position's
+// word is only ever touched by thread (position mod BLOCK).  The kept seeds of a job number at most 2 nx (the non-avoided
+// positions of y carry distinct k-mers, an entry of x matches one of them at most), so bit 31 is free.
+__global__ __launch_bounds__(BLOCK)
+void hash_seeds_long_kernel(const uint8_t* __restrict__ bases, const Job* __restrict__ jobs, unsigned long long* __restrict__ table,
+                            int32_t* __restrict__ hits, uint32_t* __restrict__ counts, uint8_t* ws, const uint64_t* __restrict__ ws_off,
+                            int k, int window)
+{
+    __shared__ unsigned long long xs[TILE];               // one tile of x's k-mers, (code << 12 | order within the tile)
+    __shared__ uint32_t warp_sums[BLOCK / 64];
+    const Job job = jobs[blockIdx.x];
+    if (job.x_len <= (uint32_t)MAX_X || job.x_len > (uint32_t)LONG_MAX_X) return;      // the other kernel's job / no workspace for it
+    const uint8_t* x = bases + job.x_off;
+    const uint8_t* y = bases + job.y_off;
+    const int xl = (int)job.x_len, yl = (int)job.y_len;
+    const int tid = threadIdx.x;
+    const int ny = yl - (k + 1) > 0 ? yl - (k + 1) : 0;
+    const int nx = xl - (k + 1);
+    unsigned long long* tab = table + job.table_off * 2;
+    const uint32_t mask = job.table_slots - 1;
+    int32_t* hits_a = hits + job.hit_off * 4;
+    int32_t* hits_b = hits_a + (size_t)job.hit_cap * 4;
+    unsigned long long* tiles = reinterpret_cast<unsigned long long*>(ws + ws_off[blockIdx.x]);
+    uint32_t* cur = reinterpret_cast<uint32_t*>(ws + ws_off[blockIdx.x] + 16ull * job.x_len);
+
+    // ---- pass A: count y's own k-mers (both strands), as in hash_seeds_kernel ----
+    for (uint32_t s = tid; s < job.table_slots; s += BLOCK) { tab[2 * s] = EMPTY; tab[2 * s + 1] = 0; }
+    __syncthreads();
+    for (int e = tid; e < 2 * ny; e += BLOCK) {
+        const bool rev = e >= ny;
+        const int i = rev ? e - ny : e;
+        const unsigned long long code = rev ? kmer_code<true>(y, yl, i, k) : kmer_code<false>(y, yl, i, k);
+        uint32_t s = hash_slot(code, mask);
+        while (true) {
+            const unsigned long long old = atomicCAS(&tab[2 * s], EMPTY, code);
+            if (old == EMPTY || old == code) break;
+            s = (s + 1) & mask;
+        }
+        atomicAdd(&tab[2 * s + 1], 1ull + ((unsigned long long)(uint32_t)(rev ? -1 - i : i) << 32));
+    }
+    __syncthreads();
+
+    // ---- list A (count -> prefix -> emit per chunk), and which y positions look x up at all ----
+    uint32_t total_a = 0;
+    for (int chunk = 0; chunk < ny; chunk += BLOCK) {
+        const int i = chunk + tid;
+        uint32_t ca = 0;
+        int pos_a = 0, len_a = 0;
+        if (i < ny) {
+            const unsigned long long code = kmer_code<false>(y, yl, i, k);
+            uint32_t s = hash_slot(code, mask);
+            while (tab[2 * s] != code) s = (s + 1) & mask;
+            const uint32_t cnt = (uint32_t)tab[2 * s + 1];
+            if (cnt == 1) {
+                pos_a = (int)(uint32_t)(tab[2 * s + 1] >> 32);
+                len_a = seed(y, yl, y, yl, pos_a, i, k);
+                ca = len_a >= window ? 1u : 0u;
+            }
+            cur[i] = cnt < 2 ? 0u : AVOID;
+        }
+        uint32_t before_a;
+        const uint32_t sum_a = block_scan(ca, warp_sums, before_a);
+        if (ca && total_a + before_a < job.hit_cap) {
+            int32_t* h = hits_a + (size_t)(total_a + before_a) * 4;
+            h[0] = i; h[1] = pos_a >= 0 ? pos_a : -1 - pos_a; h[2] = len_a; h[3] = pos_a >= 0 ? 1 : 0;
+        }
+        total_a += sum_a;
+    }
+
+    // ---- list B, count: every tile sorted once and kept; each position adds its kept seeds of the tile ----
+    const int nt = 2 * nx;
+    const int n_tiles = ny ? (nt + TILE - 1) / TILE : 0;
+    for (int t = 0; t < n_tiles; ++t) {
+        const int base = t * TILE;
+        const int tn = nt - base < TILE ? nt - base : TILE;
+        int np2 = 1;
+        while (np2 < tn) np2 <<= 1;
+        for (int e = tid; e < np2; e += BLOCK) {
+            unsigned long long v = ~0ull;
+            if (e < tn) {
+                const int g = base + e;
+                const bool rev = g >= nx;
+                const int i = rev ? g - nx : g;
+                const unsigned long long code = rev ? kmer_code<true>(x, xl, i, k) : kmer_code<false>(x, xl, i, k);
+                v = (code << 12) | (unsigned)e;
+            }
+            xs[e] = v;
+        }
+        __syncthreads();
+        bitonic_sort(xs, np2, tid);
+        for (int e = tid; e < tn; e += BLOCK) tiles[base + e] = xs[e];
+        for (int i = tid; i < ny; i += BLOCK) {
+            const uint32_t c = cur[i];
+            if (c & AVOID) continue;
+            cur[i] = c + tile_hits(xs, tn, base, x, xl, nx, y, yl, i, k, window, kmer_code<false>(y, yl, i, k), nullptr, 0u, 0u);
+        }
+        __syncthreads();
+    }
+
+    // ---- prefix over the y positions, running carry: count -> first row ----
+    uint32_t total_b = 0;
+    for (int chunk = 0; chunk < ny; chunk += BLOCK) {
+        const int i = chunk + tid;
+        const uint32_t c = i < ny ? cur[i] : AVOID;
+        uint32_t before;
+        const uint32_t sum = block_scan((c & AVOID) ? 0u : c, warp_sums, before);
+        if (i < ny) cur[i] = (c & AVOID) | (total_b + before);
+        total_b += sum;
+    }
+
+    // ---- list B, emit: the stored tiles in the same order; a position's word is its next row ----
+    for (int t = 0; t < n_tiles && total_b; ++t) {
+        const int base = t * TILE;
+        const int tn = nt - base < TILE ? nt - base : TILE;
+        __syncthreads();
+        for (int e = tid; e < tn; e += BLOCK) xs[e] = tiles[base + e];
+        __syncthreads();
+        for (int i = tid; i < ny; i += BLOCK) {
+            const uint32_t c = cur[i];
+            if (c & AVOID) continue;
+            cur[i] = c + tile_hits(xs, tn, base, x, xl, nx, y, yl, i, k, window, kmer_code<false>(y, yl, i, k), hits_b, c, job.hit_cap);
+        }
     }
     if (tid == 0) { counts[2 * blockIdx.x] = total_a; counts[2 * blockIdx.x + 1] = total_b; }
 }
@@ -293,5 +461,24 @@ extern "C" int svx_hash_seeds(const uint8_t* d_bases, const SvxHashJob* d_jobs, 
     static_assert(sizeof(SvxHashJob) == sizeof(Job), "SvxHashJob layout");
     hipLaunchKernelGGL(hash_seeds_kernel, dim3(n_jobs), dim3(BLOCK), 0, static_cast<hipStream_t>(stream), d_bases,
                        reinterpret_cast<const Job*>(d_jobs), reinterpret_cast<unsigned long long*>(d_table), d_hits, d_counts, (int)k, (int)window);
+    return hipGetLastError() == hipSuccess ? SVX_OK : SVX_ELAUNCH;
+}
+
+extern "C" size_t svx_hash_seeds_long_ws_bytes(uint32_t x_len, uint32_t y_len)
+{
+    return (size_t)((16ull * x_len + 4ull * y_len + 15ull) & ~15ull);
+}
+
+extern "C" int svx_hash_seeds_long(const uint8_t* d_bases, const SvxHashJob* d_jobs, uint32_t n_jobs, uint64_t* d_table,
+                                   int32_t* d_hits, uint32_t* d_counts, void* d_ws, const uint64_t* d_ws_off,
+                                   uint32_t k, uint32_t window, uint32_t max_x_len, void* stream)
+{
+    if (n_jobs == 0) return SVX_OK;
+    if (!d_bases || !d_jobs || !d_table || !d_hits || !d_counts || !d_ws || !d_ws_off) return SVX_EINVAL;
+    if (k < 2 || k > 13 || max_x_len > (uint32_t)LONG_MAX_X) return SVX_EINVAL;     // 4 bits x k + 12 order bits in 64; workspace
+    if ((uintptr_t)d_ws & 15) return SVX_EINVAL;
+    hipLaunchKernelGGL(hash_seeds_long_kernel, dim3(n_jobs), dim3(BLOCK), 0, static_cast<hipStream_t>(stream), d_bases,
+                       reinterpret_cast<const Job*>(d_jobs), reinterpret_cast<unsigned long long*>(d_table), d_hits, d_counts,
+                       static_cast<uint8_t*>(d_ws), d_ws_off, (int)k, (int)window);
     return hipGetLastError() == hipSuccess ? SVX_OK : SVX_ELAUNCH;
 }

@@ -389,7 +389,8 @@ def span_position_distance(starts, ends, part_off, normalizer=1000.0):
     return out, out_off
 
 
-HASH_MAX_X = 2048
+HASH_MAX_X = 2048                    # longest piece of svx_hash_seeds
+HASH_LONG_MAX_X = 65536              # longest piece of svx_hash_seeds_long (x's k-mers in tiles, --max_hash_len raised)
 _BASE_CODE = np.full(256, 255, np.uint8)
 for _i, _c in enumerate(b"ACGTNacgtnRYKMS"):
     _BASE_CODE[_c] = _i
@@ -470,9 +471,13 @@ class HashSeedsHandle:
     A batch whose scratch table and hit lists exceed ``budget`` bytes runs as several launches over one scratch area; the
     next is enqueued when the host has seen that the rows of the one before fitted its packed array (otherwise the pack,
     not the seeds, is repeated with a larger one).  A single launch -- a window's jobs -- is enqueued whole: upload,
-    seeds, pack, download, one event."""
+    seeds, pack, download, one event.
 
-    def __init__(self, bases, desc, k, window, device, budget=HASH_BUDGET, packed_rows=HASH_PACKED_ROWS):
+    ``max_piece`` above :data:`HASH_MAX_X` (up to :data:`HASH_LONG_MAX_X`) admits longer pieces: they run through
+    ``svx_hash_seeds_long`` in the same launches' index space, with a workspace from the same stream's pool that counts
+    under ``budget``."""
+
+    def __init__(self, bases, desc, k, window, device, budget=HASH_BUDGET, packed_rows=HASH_PACKED_ROWS, max_piece=HASH_MAX_X):
         self._lib = _lib.load()
         dev = self._dev = torch.device(device)
         if dev.type != "cuda":
@@ -486,8 +491,11 @@ class HashSeedsHandle:
         x_off, x_len, y_off, y_len = (desc[:, c] for c in range(4))
         if n and ((desc < 0).any() or (x_off + x_len > bases.size).any() or (y_off + y_len > bases.size).any()):
             raise _lib.SvxError("hash_seeds: a job's sequence lies outside the base array")
-        if n and int(x_len.max()) > HASH_MAX_X:
-            raise _lib.SvxError("hash_seeds: piece longer than %d bases" % HASH_MAX_X)
+        max_piece = self._max_piece = int(max_piece)
+        if not HASH_MAX_X <= max_piece <= HASH_LONG_MAX_X:
+            raise _lib.SvxError("hash_seeds: max_piece %d outside %d..%d" % (max_piece, HASH_MAX_X, HASH_LONG_MAX_X))
+        if n and int(x_len.max()) > max_piece:
+            raise _lib.SvxError("hash_seeds: piece longer than %d bases" % max_piece)
         if n and int(y_len.max()) >= 1 << 26:
             raise _lib.SvxError("hash_seeds: window longer than 2^26 bases")
         if n == 0:
@@ -497,7 +505,9 @@ class HashSeedsHandle:
         slots = np.left_shift(1, np.ceil(np.log2(want)).astype(np.int64))          # power of two >= 8 * len(y)
         slots = np.where(slots < want, slots * 2, slots)
         cap = hash_hit_caps(desc)
-        cost = (slots + 2 * cap) * 16
+        is_long = x_len > HASH_MAX_X                                       # svx_hash_seeds_long's jobs and their workspace
+        ws = np.where(is_long, (16 * x_len + 4 * y_len + 15) // 16 * 16, 0)
+        cost = (slots + 2 * cap) * 16 + ws
         # consecutive jobs to a launch while they fit the budget (a job larger than it goes alone)
         self._chunks, lo, used = [], 0, 0
         for j, c in enumerate(cost.tolist()):
@@ -508,13 +518,20 @@ class HashSeedsHandle:
         self._chunks.append((lo, n))
         jd = np.zeros(n, HASH_JOB_DTYPE)
         jd["x_off"], jd["x_len"], jd["y_off"], jd["y_len"], jd["table_slots"], jd["hit_cap"] = x_off, x_len, y_off, y_len, slots, cap
-        max_slots = max_rows = 0
+        ws_off = np.zeros(n, np.uint64)
+        max_slots = max_rows = max_ws = 0
         for lo, hi in self._chunks:
             jd["table_off"][lo:hi] = np.cumsum(slots[lo:hi]) - slots[lo:hi]
             jd["hit_off"][lo:hi] = 2 * (np.cumsum(cap[lo:hi]) - cap[lo:hi])
+            ws_off[lo:hi] = np.cumsum(ws[lo:hi]) - ws[lo:hi]
             max_slots, max_rows = max(max_slots, int(slots[lo:hi].sum())), max(max_rows, 2 * int(cap[lo:hi].sum()))
+            max_ws = max(max_ws, int(ws[lo:hi].sum()))
+        self._long = [bool(is_long[lo:hi].any()) for lo, hi in self._chunks]
         self._stream = _hash_stream(dev)
         raw = jd.view(np.uint8).reshape(-1)
+        if max_ws:                                                      # the workspace offsets ride behind the job records
+            raw = np.concatenate([raw, ws_off.view(np.uint8)])
+        self._ws_at = HASH_JOB_DTYPE.itemsize * n                      # (read only by a launch with a long job: then they were appended)
         with torch.cuda.stream(self._stream):
             # one pinned staging buffer, one upload: the job records (SvxHashJob), then the bases (+ 16 bytes of slack)
             self._h_in = torch.empty(raw.size + bases.size + 16, dtype=torch.uint8, pin_memory=True)
@@ -524,6 +541,7 @@ class HashSeedsHandle:
             self._d_in.copy_(self._h_in, non_blocking=True)
             self._d_table = torch.empty(2 * max_slots, dtype=torch.int64, device=dev)
             self._d_hits = torch.empty(4 * max_rows, dtype=torch.int32, device=dev)
+            self._d_ws = torch.empty(max_ws, dtype=torch.uint8, device=dev) if max_ws else None
         self._bases_at = raw.size
         self._start(0)
 
@@ -537,6 +555,11 @@ class HashSeedsHandle:
             rc = self._lib.svx_hash_seeds(self._d_in.data_ptr() + self._bases_at, self._d_in.data_ptr() + HASH_JOB_DTYPE.itemsize * lo, m, self._d_table.data_ptr(),
                                           self._d_hits.data_ptr(), d_out.data_ptr(), self._k, self._window, HASH_MAX_X, sp)
             _lib.check(rc, "svx_hash_seeds")
+            if self._long[ci]:                                          # the same jobs: each kernel leaves the other's alone
+                rc = self._lib.svx_hash_seeds_long(self._d_in.data_ptr() + self._bases_at, self._d_in.data_ptr() + HASH_JOB_DTYPE.itemsize * lo, m,
+                                                   self._d_table.data_ptr(), self._d_hits.data_ptr(), d_out.data_ptr(), self._d_ws.data_ptr(),
+                                                   self._d_in.data_ptr() + self._ws_at + 8 * lo, self._k, self._window, self._max_piece, sp)
+                _lib.check(rc, "svx_hash_seeds_long")
             self.launches += 1
         self._cur = _HashLaunch(ci, lo, m, hdr, self._packed_rows, d_out)
         self._pack()
@@ -580,7 +603,7 @@ class HashSeedsHandle:
             row_off[at:at + off.size] = off + np.uint32(base)
             at, base = at + off.size - 1, base + int(off[-1])
         self._result = (counts, row_off, np.concatenate([p[2] for p in self._parts]))
-        self._parts = self._d_in = self._h_in = self._d_table = self._d_hits = None
+        self._parts = self._d_in = self._h_in = self._d_table = self._d_hits = self._d_ws = None
 
     def done(self):
         while self._result is None and self._cur.event.query():
@@ -594,23 +617,25 @@ class HashSeedsHandle:
         return self._result
 
 
-def hash_seeds_async(bases_u8, job_desc, k, window, device, budget=HASH_BUDGET, packed_rows=HASH_PACKED_ROWS):
+def hash_seeds_async(bases_u8, job_desc, k, window, device, budget=HASH_BUDGET, packed_rows=HASH_PACKED_ROWS, max_piece=HASH_MAX_X):
     """One contiguous array of packed bases (pack_bases symbols) + int64 [n,4] job descriptors (x_off, x_len, y_off, y_len:
     :func:`hash_job_arrays`) -> :class:`HashSeedsHandle`.  Upload, ``svx_hash_seeds``, ``svx_hash_pack_hits`` and the
     read-back of the packed rows are enqueued on the re-aligner's own stream, through pinned memory (a pageable copy
-    would wait behind the CNN's queued launches, see Sample.from_table); nothing here waits for another stream."""
-    return HashSeedsHandle(bases_u8, job_desc, k, window, device, budget, packed_rows)
+    would wait behind the CNN's queued launches, see Sample.from_table); nothing here waits for another stream.
+    ``max_piece``: the longest piece admitted (default: the short kernel's 2048; up to HASH_LONG_MAX_X)."""
+    return HashSeedsHandle(bases_u8, job_desc, k, window, device, budget, packed_rows, max_piece)
 
 
-def hash_seeds(jobs, k, window, device, budget=HASH_BUDGET, packed_rows=HASH_PACKED_ROWS):
+def hash_seeds(jobs, k, window, device, budget=HASH_BUDGET, packed_rows=HASH_PACKED_ROWS, max_piece=HASH_MAX_X):
     """jobs: list of (x_codes, y_codes) uint8 arrays (pack_bases) -> list of (hits_a, hits_b) int32 arrays [n,4]
     = {y position, x position or position in x's reverse complement, match length, forward}, or None for a job whose
     hit lists overflowed.  The synchronous form of :func:`hash_seeds_async`: one launch for the whole batch unless its
-    scratch exceeds ``budget`` bytes (then several, with the same results).  See include/svx.h svx_hash_seeds."""
+    scratch exceeds ``budget`` bytes (then several, with the same results).  Pieces above 2048 bases are refused unless
+    ``max_piece`` admits them (svx_hash_seeds_long).  See include/svx.h svx_hash_seeds."""
     if not jobs:
         return []
     bases, desc = hash_job_arrays(jobs)
-    return hash_split_rows(desc, *hash_seeds_async(bases, desc, k, window, device, budget, packed_rows).result())
+    return hash_split_rows(desc, *hash_seeds_async(bases, desc, k, window, device, budget, packed_rows, max_piece).result())
 
 
 def bgzf_block_table(raw):

@@ -30,6 +30,7 @@ from .collection.output_clusters import collect_pair_lines, iter_pair_lines
 from .collection.run_collection import detect_window
 from .network.create_batch import PAD_DATA, parse_data_fields
 from .network.predict import Predict, SiteVoter
+from .segmentplot import run_hash_lineplot
 
 _PAD_REC = parse_data_fields(PAD_DATA.split("_"))
 
@@ -882,7 +883,8 @@ class PooledHotPath(HotPath):
                     prof["hash.requests"] += 1
                     prof["hash.jobs"] += len(desc)
                     try:
-                        hashing.append((ci, wid, kernels.hash_seeds_async(bases, desc, k, min_accept, self.device)))
+                        more = {} if run_hash_lineplot.MAX_PIECE is None else {"max_piece": run_hash_lineplot.MAX_PIECE}
+                        hashing.append((ci, wid, kernels.hash_seeds_async(bases, desc, k, min_accept, self.device, **more)))
                     except Exception as exc:                          # noqa: BLE001 -- costs the request, not the run: answered at once
                         logging.error("[ERROR]: %s. --hash jobs of window %s go back to its helper", exc, wid)
                         c.send(("hashres", wid, None, None, None))

@@ -23,6 +23,8 @@ def select_longest(segments):
 
 
 DEVICE = None        # torch.device of the process that owns a GPU (set by Sample.from_table); None in the forked host helpers
+MAX_PIECE = None     # longest piece the device takes: None = the short kernel's kernels.HASH_MAX_X; a --hash run of the command line sets
+                     # kernels.HASH_LONG_MAX_X before the helpers fork (svx_hash_seeds_long), SVX_HASH_LONG=0 leaves it None
 REMOTE = None        # in a host helper: callable (bases, desc, k, window) -> (counts, row_off, rows) or None, the owner's device by pipe (pipeline._worker_main)
 
 
@@ -36,7 +38,7 @@ def hashplot_unmapped(ref, seq, k, min_accept):
     """-> (None, segments): self-align the window to learn its repeats, then place ``seq`` (:52-85).
     In the GPU-owning process the two seed-and-extend passes run on the device (``svx_hash_seeds``); the hit lists
     are replayed through the same order-dependent host steps.  Sequences outside the alphabet ACGTN (upstream's
-    k-mers are raw strings), pieces longer than the kernel's table, k > 13 and overflowing hit lists take the host
+    k-mers are raw strings), pieces longer than the kernels take (``MAX_PIECE``), k > 13 and overflowing hit lists take the host
     passes below, which are also what the helper processes (no GPU) run."""
     if DEVICE is not None:
         got = hashplot_unmapped_batch([(ref, seq)], k, min_accept, DEVICE)[0]
@@ -89,8 +91,10 @@ def hashplot_unmapped_batch(pairs, k, min_accept, device):
     jobs, where = [], []
     if not (2 <= k <= 13) or (device is None and REMOTE is None):
         return out
+    longest = kernels.HASH_MAX_X if MAX_PIECE is None else MAX_PIECE
+    more = {} if MAX_PIECE is None else {"max_piece": MAX_PIECE}
     for n, (ref, seq) in enumerate(pairs):
-        if len(seq) > kernels.HASH_MAX_X:
+        if len(seq) > longest:
             continue
         x, y = kernels.pack_bases(seq), kernels.pack_bases(ref)
         if x is None or y is None:
@@ -98,7 +102,7 @@ def hashplot_unmapped_batch(pairs, k, min_accept, device):
         jobs.append((x, y))
         where.append(n)
     if device is not None:
-        results = kernels.hash_seeds(jobs, k, min_accept, device)
+        results = kernels.hash_seeds(jobs, k, min_accept, device, **more)
     elif jobs:
         bases, desc = kernels.hash_job_arrays(jobs)
         lists = REMOTE(bases, desc, k, min_accept)
