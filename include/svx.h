@@ -439,6 +439,39 @@ int            svx_bam_find_starts(const uint8_t* d_raw, const uint64_t* d_dst_o
                                    void* stream);
 int            svx_bam_walk_offsets(const uint8_t* d_raw, const uint64_t* d_starts, uint32_t n_starts, const uint64_t* d_base,
                                     uint64_t* d_rec_off, void* stream);
+/* The records of an UNSORTED BAM in coordinate order (svx_recsort.hip; ABI 420, additive): the walk above takes a file apart in
+ * file order, these put its arrays into the order of `samtools sort`.
+ *   svx_record_sort     d_order [n]: d_order[r] = the input index of the record of sorted rank r, by the key
+ *                       ((tid < 0 ? n_ref : tid) << 32) | (uint32)(pos + 1) ascending -- records without a reference last --,
+ *                       STABLE: records of equal key keep their input order.  d_tid / d_pos [n] int32, pos >= -1.  pos_bits
+ *                       (1 .. 32): the significant bits of pos + 1, bit_length(longest reference + 1); higher bits of pos + 1
+ *                       are ignored.  An LSD radix sort, 8 bits a pass, over pos_bits + bit_length(n_ref) bits: per pass a
+ *                       histogram per tile of SVX_RECORD_SORT_TILE records, one scan of the 256 x tiles table, a scatter
+ *                       whose in-tile ranks come from wave ballots and LDS counters, lanes and waves taken in order.
+ *                       d_ws: ws_bytes >= svx_record_sort_ws_bytes(n) (20 bytes a record + the table), 16-byte aligned
+ *   svx_record_gather   d_dst[r] = d_src[d_order[r]] for n elements of elem_bytes 1, 2 or 4 (tid, pos, flag, mapq, l_seq);
+ *                       both arrays aligned to elem_bytes
+ *   svx_record_gather_offsets   d_off_out [n + 1] = the exclusive prefix sum (int64) of the lengths d_off_in[s + 1] - d_off_in[s]
+ *                       taken in the order s = d_order[0], d_order[1], ...; the closing entry = the total.  d_off_in [n + 1].
+ *                       d_ws: ws_bytes >= svx_record_gather_offsets_ws_bytes(n), 16-byte aligned
+ *   svx_record_gather_segments  segment d_order[r] of d_src -- elements d_off_in[s] .. d_off_in[s + 1] of elem_bytes 1, 2 or 4 --
+ *                       copied to element d_off_out[r] of d_dst, a wave per record; segments of no element and of more than
+ *                       65,535 are fine.  4 for CIGAR words, 1 for QNAME bytes (the '\n' behind a name belongs to its
+ *                       segment) and for SEQ bytes (byte-aligned per record, as svx_bam_walk_extract_seq writes them).
+ *                       d_src is read in aligned dwords: 4-byte aligned, readable up to the next multiple of 4 behind its last
+ *                       byte; d_dst aligned to elem_bytes.  Exactly the total's bytes of d_dst are written: the 4 readable
+ *                       words svx_cigar_scan wants behind a gathered CIGAR array are the caller's to allocate.
+ * No atomics in any of them: the output is a pure function of the input.  n = 0 is fine everywhere (d_off_out[0] = 0). */
+#define SVX_RECORD_SORT_TILE 2048u
+size_t         svx_record_sort_ws_bytes(uint32_t n);
+int            svx_record_sort(const int32_t* d_tid, const int32_t* d_pos, uint32_t n, uint32_t n_ref, uint32_t pos_bits,
+                               uint32_t* d_order, void* d_ws, uint64_t ws_bytes, void* stream);
+int            svx_record_gather(const void* d_src, const uint32_t* d_order, void* d_dst, uint32_t n, uint32_t elem_bytes, void* stream);
+size_t         svx_record_gather_offsets_ws_bytes(uint32_t n);
+int            svx_record_gather_offsets(const int64_t* d_off_in, const uint32_t* d_order, uint32_t n, int64_t* d_off_out, void* d_ws,
+                                         uint64_t ws_bytes, void* stream);
+int            svx_record_gather_segments(const void* d_src, const int64_t* d_off_in, const uint32_t* d_order, const int64_t* d_off_out,
+                                          void* d_dst, uint32_t n, uint32_t elem_bytes, void* stream);
 /* host helpers of the device-side ingestion: parallel positional read into caller memory; the whole BGZF blocks of a
  * buffer (payload offset / size, ISIZE, file offset; -> their number or -1, *used = bytes they cover); QNAME ids by
  * first occurrence (-> number of distinct names, written '\n'-separated to uniq) */

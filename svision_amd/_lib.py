@@ -72,6 +72,12 @@ SYMBOLS = {
     "svx_bam_find_starts_ws_bytes": (_sz, [_u32]),
     "svx_bam_find_starts": (ctypes.c_int, [_vp, _vp, _u32, _u64, _u32, _vp, _vp, _vp, _vp, _u64, _vp]),
     "svx_bam_walk_offsets": (ctypes.c_int, [_vp, _vp, _u32, _vp, _vp, _vp]),
+    "svx_record_sort_ws_bytes": (_sz, [_u32]),                           # (ABI 420, additive: svx_recsort.hip)
+    "svx_record_sort": (ctypes.c_int, [_vp, _vp, _u32, _u32, _u32, _vp, _vp, _u64, _vp]),
+    "svx_record_gather": (ctypes.c_int, [_vp, _vp, _vp, _u32, _u32, _vp]),
+    "svx_record_gather_offsets_ws_bytes": (_sz, [_u32]),
+    "svx_record_gather_offsets": (ctypes.c_int, [_vp, _vp, _u32, _vp, _vp, _u64, _vp]),
+    "svx_record_gather_segments": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp]),
     "svx_read_range": (ctypes.c_int, [ctypes.c_char_p, _u64, _u64, _vp, ctypes.c_int]),
     "svx_bgzf_index": (ctypes.c_int64, [_vp, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _vp]),
     "svx_name_ids": (ctypes.c_int64, [_vp, _vp, _u64, _vp, _vp, _vp]),

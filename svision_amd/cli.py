@@ -134,6 +134,27 @@ def load_rank_table(options, rank, ws):
     return table
 
 
+def _load_unsorted(options):
+    """SVX_DEVICE_SORT=1 and a header that does not say ``SO:coordinate``: the whole file taken apart and its records sorted on the
+    device (svision_amd/ingest_sort.py) -> the resident Sample the run goes on with."""
+    import time
+    import torch
+    from .ingest_sort import SortIngestError, load_sample
+    t0 = time.perf_counter()
+    if torch.cuda.is_available():
+        torch.cuda.set_device(sdist.local_device_index())
+    stats = {}
+    try:
+        sample = load_sample(options.bam_path, Fasta(options.genome), options.min_sv_size, device=torch.device("cuda", torch.cuda.current_device()),
+                             with_seq=bool(options.hash or options.graph), stats=stats)
+    except SortIngestError as exc:
+        logging.error("%s", exc)
+        raise SystemExit(1)
+    logging.info("%s is not coordinate sorted: %d records sorted on the device in %.2f s (%d range(s), %d radix passes)", options.bam_path,
+                 stats["records"], time.perf_counter() - t0, stats["ranges"], stats["passes"])
+    return sample
+
+
 def run(options, sample=None, classifier=None):
     """Whole pipeline; returns the merged VCF path (rank 0) or None."""
     from . import sample as _sample
@@ -168,8 +189,18 @@ def run(options, sample=None, classifier=None):
         from .io.bam import find_index, read_bam_header
         head = read_bam_header(options.bam_path)
         if head.sort_order != "coordinate":
-            logging.error("This is not a coordinate sorted BAM file")
-            raise SystemExit(1)
+            if os.environ.get("SVX_DEVICE_SORT") != "1":
+                logging.error("This is not a coordinate sorted BAM file")
+                logging.error("(SVX_DEVICE_SORT=1 sorts its records on the device: one rank, the whole file resident)")
+                raise SystemExit(1)
+            if ws > 1:
+                # (every rank would read and sort the whole file; the ranks share chromosomes, not records in file order)
+                logging.error("SVX_DEVICE_SORT=1 sorts an unsorted BAM in a single-rank run only: sort and index %s first "
+                              "(`samtools sort`, then `python -m svision_amd.index`) and start the %d ranks again", options.bam_path, ws)
+                raise SystemExit(1)
+            sample = _load_unsorted(options)
+            _tick("unsorted BAM: records sorted on the device")
+    if sample is None:
         fasta = Fasta(options.genome)
         references, lengths = head.references, head.lengths
         index = find_index(options.bam_path)

@@ -17,6 +17,10 @@ yields every record's reference span -- except knowing where records start when 
 
 A corrupt block, a CRC mismatch, a malformed or cut record chain or a file that is not coordinate-sorted raises IndexBuildError
 (a ValueError); no file is left behind.  A plain loop: nothing here overlaps reading, inflating and walking.
+
+The pass itself -- ranges, carry, inflate, CRC, find-starts and the walk -- is :func:`record_ranges`, a generator that leaves every
+range's extracted arrays on the device; build_index adds the byte offsets and the scan per range, svision_amd/ingest_sort.py (an
+UNSORTED file: its records sorted on the device) keeps the arrays and sorts them.
 """
 import os
 import struct
@@ -106,8 +110,8 @@ def first_record(path, limit=1 << 30):
 class _Clock:
     """Wall time per stage, the device drained at every boundary (what a stage enqueued is counted as that stage's)."""
 
-    def __init__(self, torch, device):
-        self.torch, self.device, self.t, self.times = torch, device, time.perf_counter(), dict.fromkeys(STAGES, 0.0)
+    def __init__(self, torch, device, stages=STAGES):
+        self.torch, self.device, self.t, self.times = torch, device, time.perf_counter(), dict.fromkeys(stages, 0.0)
 
     def lap(self, stage, device_work=True):
         if device_work:
@@ -121,8 +125,19 @@ def _as_i64(t_np):
     return np.ascontiguousarray(t_np, np.uint64).view(np.int64)
 
 
-def _index_range(lib, torch, kernels, dev, pinned, blocks, entry, d_ref_len, n_ref, clock):
-    """One range on the device -> (exit offset, dst_off, per-record arrays tid, pos, flag, span, byte offset), or raises."""
+class RecordRange:
+    """One range of the file taken apart on the device (:func:`record_ranges`): its whole BGZF blocks (``blocks``, ``dst``: where each
+    one's inflated bytes lie in ``d_raw``; ``total`` of them), the chain's ``exit_off`` and the records that COMPLETE in the range, in
+    file order -- ``n_rec`` of them with ``words`` CIGAR words, ``name_bytes`` QNAME bytes and (``with_seq``) ``seq_bytes`` SEQ bytes --
+    as the device arrays svx_bam_walk_extract(_seq) filled (None where ``n_rec`` is 0).  ``d_starts`` / ``n_starts`` / ``d_base``: what
+    the walk kernels took.  ``before``: the clock's stage times when the range was begun."""
+    d_tid = d_pos = d_flag = d_mapq = d_l_seq = d_cig_off = d_cigar = d_name_off = d_names = d_seq_off = d_seq = None
+    d_starts = d_base = None
+    n_starts = n_rec = words = name_bytes = seq_bytes = 0
+
+
+def _inflate_range(lib, torch, kernels, dev, pinned, blocks, entry, d_ref_len, n_ref, clock):
+    """A range's blocks inflated and checked, the record starts found -> RecordRange with d_raw, dst, total, exit_off and starts."""
     n, used = blocks.k, blocks.used
     st = kernels._stream_ptr(dev)
     dst = np.zeros(n + 1, np.uint64)
@@ -162,15 +177,28 @@ def _index_range(lib, torch, kernels, dev, pinned, blocks, entry, d_ref_len, n_r
     if chain_status:
         at = min(max(int(np.searchsorted(dst[:n], np.uint64(exit_off), "right")) - 1, 0), n - 1)
         raise IndexBuildError("a malformed record %d bytes into the BGZF block at file offset %d" % (exit_off - int(dst[at]), int(blocks.coff[at])))
-    starts = np.unique(np.append(first[first != NO_START], np.uint64(exit_off)))
+    rng = RecordRange()
+    rng.blocks, rng.dst, rng.total, rng.exit_off, rng.d_raw = blocks, dst, total, exit_off, d_raw
+    rng.starts = np.unique(np.append(first[first != NO_START], np.uint64(exit_off)))
+    return rng
+
+
+def _walk_range(lib, torch, kernels, dev, rng, with_seq, clock):
+    """The existing walk over a range's starts: counts -> prefix sums -> the records' fields, CIGAR words, names and (``with_seq``)
+    bases, all left on the device."""
+    starts, d_raw = rng.starts, rng.d_raw
     n_starts = int(starts.size) - 1
-    empty = (np.empty(0, np.int32), np.empty(0, np.int32), np.empty(0, np.uint16), np.empty(0, np.int32), np.empty(0, np.uint64))
     if n_starts <= 0:
-        return exit_off, dst, empty
-    # the existing walk over those starts: counts -> prefix sums -> the records' fields, CIGAR words and byte offsets
+        return
+    st = kernels._stream_ptr(dev)
     d_starts = torch.from_numpy(starts.view(np.int64)).to(dev)
     d_counts = torch.empty((n_starts, 4), dtype=torch.int64, device=dev)
-    _lib.check(lib.svx_bam_walk_count(d_raw.data_ptr(), d_starts.data_ptr(), n_starts, d_counts.data_ptr(), st), "svx_bam_walk_count")
+    if with_seq:
+        d_seq_counts = torch.empty(n_starts, dtype=torch.int64, device=dev)
+        _lib.check(lib.svx_bam_walk_count_seq(d_raw.data_ptr(), d_starts.data_ptr(), n_starts, d_counts.data_ptr(), d_seq_counts.data_ptr(), st),
+                   "svx_bam_walk_count_seq")
+    else:
+        _lib.check(lib.svx_bam_walk_count(d_raw.data_ptr(), d_starts.data_ptr(), n_starts, d_counts.data_ptr(), st), "svx_bam_walk_count")
     counts = d_counts.cpu().numpy()
     if counts[:, 3].any():
         i = int(np.flatnonzero(counts[:, 3])[0])
@@ -180,52 +208,52 @@ def _index_range(lib, torch, kernels, dev, pinned, blocks, entry, d_ref_len, n_r
     n_rec, words, name_bytes = (int(v) for v in counts[:, :3].sum(axis=0))
     if n_rec == 0:
         clock.lap("walk")
-        return exit_off, dst, empty
+        return
     d_base = torch.from_numpy(base).to(dev)
     d_tid, d_pos, d_l_seq = (torch.empty(n_rec, dtype=torch.int32, device=dev) for _ in range(3))
     d_flag, d_mapq = torch.empty(n_rec, dtype=torch.int16, device=dev), torch.empty(n_rec, dtype=torch.uint8, device=dev)
     d_cig_off, d_name_off = (torch.empty(n_rec + 1, dtype=torch.int64, device=dev) for _ in range(2))
     d_cigar = torch.empty(max(words, 1) + 4, dtype=torch.int32, device=dev)
     d_names = torch.empty(max(name_bytes, 1), dtype=torch.uint8, device=dev)
-    d_rec_off = torch.empty(n_rec, dtype=torch.int64, device=dev)
-    _lib.check(lib.svx_bam_walk_extract(d_raw.data_ptr(), d_starts.data_ptr(), n_starts, d_base.data_ptr(), d_tid.data_ptr(), d_pos.data_ptr(),
-                                        d_flag.data_ptr(), d_mapq.data_ptr(), d_l_seq.data_ptr(), d_cig_off.data_ptr(), d_cigar.data_ptr(),
-                                        d_name_off.data_ptr(), d_names.data_ptr(), n_rec, st), "svx_bam_walk_extract")
-    _lib.check(lib.svx_bam_walk_offsets(d_raw.data_ptr(), d_starts.data_ptr(), n_starts, d_base.data_ptr(), d_rec_off.data_ptr(), st),
-               "svx_bam_walk_offsets")
+    if with_seq:
+        seq_counts = d_seq_counts.cpu().numpy()
+        seq_base = np.zeros(n_starts, np.int64)
+        seq_base[1:] = np.cumsum(seq_counts[:-1])
+        rng.seq_bytes = int(seq_counts.sum())
+        d_seq_base = torch.from_numpy(seq_base).to(dev)
+        rng.d_seq_off = torch.empty(n_rec + 1, dtype=torch.int64, device=dev)
+        rng.d_seq = torch.empty((max(rng.seq_bytes, 1) + 15) // 16 * 16, dtype=torch.uint8, device=dev)
+        _lib.check(lib.svx_bam_walk_extract_seq(d_raw.data_ptr(), d_starts.data_ptr(), n_starts, d_base.data_ptr(), d_tid.data_ptr(), d_pos.data_ptr(),
+                                                d_flag.data_ptr(), d_mapq.data_ptr(), d_l_seq.data_ptr(), d_cig_off.data_ptr(), d_cigar.data_ptr(),
+                                                d_name_off.data_ptr(), d_names.data_ptr(), d_seq_base.data_ptr(), rng.d_seq_off.data_ptr(),
+                                                rng.d_seq.data_ptr(), n_rec, st), "svx_bam_walk_extract_seq")
+    else:
+        _lib.check(lib.svx_bam_walk_extract(d_raw.data_ptr(), d_starts.data_ptr(), n_starts, d_base.data_ptr(), d_tid.data_ptr(), d_pos.data_ptr(),
+                                            d_flag.data_ptr(), d_mapq.data_ptr(), d_l_seq.data_ptr(), d_cig_off.data_ptr(), d_cigar.data_ptr(),
+                                            d_name_off.data_ptr(), d_names.data_ptr(), n_rec, st), "svx_bam_walk_extract")
+    rng.d_starts, rng.n_starts, rng.d_base = d_starts, n_starts, d_base
+    rng.n_rec, rng.words, rng.name_bytes = n_rec, words, name_bytes
+    rng.d_tid, rng.d_pos, rng.d_flag, rng.d_mapq, rng.d_l_seq = d_tid, d_pos, d_flag, d_mapq, d_l_seq
+    rng.d_cig_off, rng.d_cigar, rng.d_name_off, rng.d_names = d_cig_off, d_cigar, d_name_off, d_names
     clock.lap("walk")
-    # the reference span of every record: the scan's statistics (a CG-tag record: of its real CIGAR); no gap is long enough to be listed
-    scan = kernels.cigar_scan(d_cigar, d_cig_off, d_pos, 0x7FFFFFFF, n_words=words)
-    clock.lap("scan")
-    out = (d_tid.cpu().numpy(), d_pos.cpu().numpy(), d_flag.cpu().numpy().view(np.uint16), scan.stats[:, 0].contiguous().cpu().numpy(),
-           d_rec_off.cpu().numpy().view(np.uint64))
-    clock.lap("read_back")
-    return exit_off, dst, out
 
 
-def build_index(bam_path, out_path=None, device="cuda", range_bytes=None, stats=None):
-    """Write the ``.bai`` of ``bam_path`` to ``out_path`` (default ``bam_path + ".bai"``) and return that path.  ``range_bytes``:
-    compressed bytes a range (default: the device decoder's group size; tests).  ``stats``: a dict that receives the number of
-    ranges, blocks and records and the seconds per stage -- in total ("seconds") and per range ("per_range")."""
+def record_ranges(bam_path, head, dev, clock, range_bytes=None, with_seq=False):
+    """Generator: the whole file in ranges of about ``range_bytes`` compressed bytes (default: the device decoder's group size), each
+    read, inflated, CRC-checked and walked on the device -> one :class:`RecordRange` a range, whose records are those that complete
+    in it; a record the range's end cuts opens the next range, a range in which none completes is read again, twice as large.  The
+    last range has ``at_end`` set.  The pass of :func:`build_index` and of svision_amd.ingest_sort.load_sample.  Raises
+    IndexBuildError for a corrupt block, a CRC mismatch, a malformed chain or a file cut inside a record.  ``head``: read_bam_header's."""
     import torch
     from . import ingest, ingest_gpu, kernels
-    from .io.bam import read_bam_header
-    if not torch.cuda.is_available():
-        raise _lib.SvxError("build_index needs the GPU (svx_bam_find_starts); there is no CPU fallback")
     lib = _lib.load()
-    dev = torch.device(device)
-    if dev.index is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
-    out_path = out_path or bam_path + ".bai"
     base_bytes = int(range_bytes or ingest_gpu.LARGE_GROUP_BYTES)
-    clock = _Clock(torch, dev)
-    head = read_bam_header(bam_path)
     file_at, entry, n_ref = first_record(bam_path)
     if n_ref != len(head.references):
         raise IndexBuildError("%s: the header names %d references, its dictionary %d" % (bam_path, len(head.references), n_ref))
     size = os.path.getsize(bam_path)
     d_ref_len = torch.from_numpy(np.asarray(list(head.lengths) + [0], np.int32)).to(dev)
-    parts, per_range, n_blocks, want_bytes, end_voff = [], [], 0, base_bytes, None
+    want_bytes = base_bytes
     pinned = None                                               # a range's file bytes: read into pinned memory, reused from range to range
     threads = ingest.decode_threads()
     clock.lap("read", False)
@@ -246,28 +274,72 @@ def build_index(bam_path, out_path=None, device="cuda", range_bytes=None, stats=
         if blocks.k == 0:
             want_bytes *= 2
             continue
-        exit_off, dst, (tid, pos, flag, span, rec_off) = _index_range(lib, torch, kernels, dev, pinned, blocks, entry, d_ref_len, n_ref, clock)
-        total = int(dst[blocks.k])
+        rng = _inflate_range(lib, torch, kernels, dev, pinned, blocks, entry, d_ref_len, n_ref, clock)
+        exit_off, total = rng.exit_off, rng.total
         if exit_off == entry and not at_end and exit_off < total:
             want_bytes *= 2                                     # no record completes in the range: the same place again, twice as large
             continue
-        n_blocks += blocks.k
-        parts.append((tid, pos, flag, span, bai.virtual_offsets(dst, blocks.coff, rec_off)))
-        clock.lap("assembly", False)
-        per_range.append(dict({k: round(clock.times[k] - before[k], 6) for k in STAGES}, blocks=int(blocks.k), records=int(tid.size),
-                              compressed_bytes=int(blocks.used), inflated_bytes=total))
+        _walk_range(lib, torch, kernels, dev, rng, with_seq, clock)
+        rng.before, rng.at_end = before, at_end
+        if at_end and exit_off != total:
+            raise IndexBuildError("%s is cut inside a record: its last record starts %d bytes before the end of the data and does not fit"
+                                  % (bam_path, total - exit_off))
+        yield rng
         if at_end:
-            if exit_off != total:
-                raise IndexBuildError("%s is cut inside a record: its last record starts %d bytes before the end of the data and does not fit"
-                                      % (bam_path, total - exit_off))
-            end_voff = bai.virtual_offsets(dst, blocks.coff, [total])
-            break
+            return
         want_bytes = base_bytes
         if exit_off >= total:
             file_at, entry = file_at + blocks.used, 0
         else:                                                   # the block the cut record starts in opens the next range
-            b = int(np.searchsorted(dst[:blocks.k], np.uint64(exit_off), "right")) - 1
-            file_at, entry = int(blocks.coff[b]), exit_off - int(dst[b])
+            b = int(np.searchsorted(rng.dst[:blocks.k], np.uint64(exit_off), "right")) - 1
+            file_at, entry = int(blocks.coff[b]), exit_off - int(rng.dst[b])
+
+
+def _index_fields(lib, torch, kernels, dev, rng, clock):
+    """What the index wants of a range's records -> host arrays tid, pos, flag, reference span, byte offset in the range's stream."""
+    if rng.n_rec == 0:
+        return np.empty(0, np.int32), np.empty(0, np.int32), np.empty(0, np.uint16), np.empty(0, np.int32), np.empty(0, np.uint64)
+    d_rec_off = torch.empty(rng.n_rec, dtype=torch.int64, device=dev)
+    _lib.check(lib.svx_bam_walk_offsets(rng.d_raw.data_ptr(), rng.d_starts.data_ptr(), rng.n_starts, rng.d_base.data_ptr(), d_rec_off.data_ptr(),
+                                        kernels._stream_ptr(dev)), "svx_bam_walk_offsets")
+    clock.lap("walk")
+    # the reference span of every record: the scan's statistics (a CG-tag record: of its real CIGAR); no gap is long enough to be listed
+    scan = kernels.cigar_scan(rng.d_cigar, rng.d_cig_off, rng.d_pos, 0x7FFFFFFF, n_words=rng.words)
+    clock.lap("scan")
+    out = (rng.d_tid.cpu().numpy(), rng.d_pos.cpu().numpy(), rng.d_flag.cpu().numpy().view(np.uint16), scan.stats[:, 0].contiguous().cpu().numpy(),
+           d_rec_off.cpu().numpy().view(np.uint64))
+    clock.lap("read_back")
+    return out
+
+
+def build_index(bam_path, out_path=None, device="cuda", range_bytes=None, stats=None):
+    """Write the ``.bai`` of ``bam_path`` to ``out_path`` (default ``bam_path + ".bai"``) and return that path.  ``range_bytes``:
+    compressed bytes a range (default: the device decoder's group size; tests).  ``stats``: a dict that receives the number of
+    ranges, blocks and records and the seconds per stage -- in total ("seconds") and per range ("per_range")."""
+    import torch
+    from . import kernels
+    from .io.bam import read_bam_header
+    if not torch.cuda.is_available():
+        raise _lib.SvxError("build_index needs the GPU (svx_bam_find_starts); there is no CPU fallback")
+    lib = _lib.load()
+    dev = torch.device(device)
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    out_path = out_path or bam_path + ".bai"
+    clock = _Clock(torch, dev)
+    head = read_bam_header(bam_path)
+    n_ref = len(head.references)
+    parts, per_range, n_blocks, end_voff = [], [], 0, None
+    for rng in record_ranges(bam_path, head, dev, clock, range_bytes):
+        blocks, dst = rng.blocks, rng.dst
+        tid, pos, flag, span, rec_off = _index_fields(lib, torch, kernels, dev, rng, clock)
+        n_blocks += blocks.k
+        parts.append((tid, pos, flag, span, bai.virtual_offsets(dst, blocks.coff, rec_off)))
+        clock.lap("assembly", False)
+        per_range.append(dict({k: round(clock.times[k] - rng.before[k], 6) for k in STAGES}, blocks=int(blocks.k), records=int(tid.size),
+                              compressed_bytes=int(blocks.used), inflated_bytes=rng.total))
+        if rng.at_end:
+            end_voff = bai.virtual_offsets(dst, blocks.coff, [rng.total])
     tid, pos, flag, span, voff = (np.concatenate([p[i] for p in parts]) for i in range(5))
     voff_end = np.append(voff[1:], end_voff).astype(np.uint64)
     pos64 = pos.astype(np.int64)

@@ -758,3 +758,77 @@ def bgzf_inflate(d_comp, src_off, src_len, isize, wave=None, crc=None):
                                     d_status.data_ptr(), _stream_ptr(dev))
             _lib.check(rc, "svx_bgzf_crc32")
     return d_out[:total], d_status[:n]
+
+
+# ---- the records of an unsorted BAM in coordinate order (svx_recsort.hip; the loader: svision_amd/ingest_sort.py) ----
+RECORD_SORT_TILE = 2048              # SVX_RECORD_SORT_TILE: records a workgroup of the sort's histogram and scatter passes takes
+
+
+def _require_order(order, n=None):
+    _require_cuda(order, "order")
+    if order.dtype != torch.int32 or order.dim() != 1 or (n is not None and order.shape[0] != n):
+        raise _lib.SvxError("order must be an int32 [n] tensor (the bits of uint32 indices)")
+
+
+def record_sort(d_tid, d_pos, n_ref, pos_bits):
+    """tid / pos int32 [n] device tensors -> int32 [n] (the bits of uint32): the input index of the record of every sorted rank,
+    by (tid, unmapped last; pos), stable.  ``pos_bits``: bit_length(longest reference + 1).  See include/svx.h svx_record_sort."""
+    lib = _lib.load()
+    _require_cuda(d_tid, "tid")
+    _require_cuda(d_pos, "pos")
+    if d_tid.dtype != torch.int32 or d_pos.dtype != torch.int32 or d_tid.dim() != 1 or d_tid.shape != d_pos.shape:
+        raise _lib.SvxError("tid and pos must be int32 [n] tensors")
+    n, dev = int(d_tid.shape[0]), d_tid.device
+    order = torch.empty(n, dtype=torch.int32, device=dev)
+    ws = torch.empty(int(lib.svx_record_sort_ws_bytes(n)), dtype=torch.uint8, device=dev)
+    _lib.check(lib.svx_record_sort(d_tid.data_ptr(), d_pos.data_ptr(), n, int(n_ref), int(pos_bits), order.data_ptr(), ws.data_ptr(),
+                                   int(ws.numel()), _stream_ptr(dev)), "svx_record_sort")
+    return order
+
+
+def record_gather(src, order):
+    """out[r] = src[order[r]] for a 1-D device tensor of 1-, 2- or 4-byte elements.  See include/svx.h svx_record_gather."""
+    lib = _lib.load()
+    _require_cuda(src, "src")
+    _require_order(order)
+    if src.dim() != 1 or src.element_size() not in (1, 2, 4):
+        raise _lib.SvxError("src must be a 1-D tensor of 1-, 2- or 4-byte elements")
+    n = int(order.shape[0])
+    out = torch.empty(n, dtype=src.dtype, device=src.device)
+    _lib.check(lib.svx_record_gather(src.data_ptr(), order.data_ptr(), out.data_ptr(), n, src.element_size(), _stream_ptr(src.device)),
+               "svx_record_gather")
+    return out
+
+
+def record_gather_offsets(off_in, order):
+    """off_in int64 [n + 1] (CSR offsets in input order) -> int64 [n + 1]: the offsets of the same segments laid out in the order
+    ``order``, the closing entry their total.  See include/svx.h svx_record_gather_offsets."""
+    lib = _lib.load()
+    _require_cuda(off_in, "off_in")
+    n = int(off_in.shape[0]) - 1
+    _require_order(order, n)
+    if off_in.dtype != torch.int64 or off_in.dim() != 1 or n < 0:
+        raise _lib.SvxError("off_in must be an int64 [n + 1] tensor")
+    dev = off_in.device
+    out = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    ws = torch.empty(int(lib.svx_record_gather_offsets_ws_bytes(n)), dtype=torch.uint8, device=dev)
+    _lib.check(lib.svx_record_gather_offsets(off_in.data_ptr(), order.data_ptr(), n, out.data_ptr(), ws.data_ptr(), int(ws.numel()),
+                                             _stream_ptr(dev)), "svx_record_gather_offsets")
+    return out
+
+
+def record_gather_segments(src, off_in, order, off_out, out):
+    """Segment ``order[r]`` of ``src`` (elements off_in[s] .. off_in[s + 1]) -> element off_out[r] of ``out`` (same dtype, at least
+    off_out[n] elements; nothing else of it is written).  ``src``: readable up to the next multiple of 4 bytes behind its end.
+    See include/svx.h svx_record_gather_segments."""
+    lib = _lib.load()
+    for t, name in ((src, "src"), (off_in, "off_in"), (off_out, "off_out"), (out, "out")):
+        _require_cuda(t, name)
+    n = int(off_in.shape[0]) - 1
+    _require_order(order, n)
+    if off_in.dtype != torch.int64 or off_out.dtype != torch.int64 or off_out.shape != off_in.shape or out.dtype != src.dtype \
+            or src.element_size() not in (1, 2, 4):
+        raise _lib.SvxError("off_in / off_out must be int64 [n + 1], src / out of one dtype of 1, 2 or 4 bytes")
+    _lib.check(lib.svx_record_gather_segments(src.data_ptr(), off_in.data_ptr(), order.data_ptr(), off_out.data_ptr(), out.data_ptr(), n,
+                                              src.element_size(), _stream_ptr(src.device)), "svx_record_gather_segments")
+    return out
