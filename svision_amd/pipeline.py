@@ -15,10 +15,14 @@ process that owns the GPU.  The device stage replays a captured HIP graph per ba
 -> AlexNet -> pack) on a few streams, so the owner process spends microseconds per batch.
 """
 import collections
+import gc
 import io
 import os
 import multiprocessing as mp
 import multiprocessing.connection as mpc
+import shutil
+import tempfile
+import time
 
 import logging
 
@@ -403,7 +407,7 @@ class HotPath:
 _POOL_STATE = {}
 
 
-def _worker_main(conn):
+class _Helper:
     """Helper process: never touches the GPU.  Protocol on the duplex pipe:
        owner -> ("win", wid, key, chrom, start, end, scan of the window's rows or None)
                     helper -> ("part", wid, records int32[k,12]) ... as the clusters are worked through, then
@@ -422,97 +426,107 @@ def _worker_main(conn):
                                                           not run them (logged there); the helper takes the host aligner
     Neither side can block on a full pipe there: the helper sends "hash" while the owner is in its loop, which reads every
     busy helper's pipe and sends a collecting helper nothing but the few small control messages below; the owner sends
-    "hashres" only to a helper that has sent "hash" and since then does nothing but read its pipe until that reply."""
-    sample, options = _POOL_STATE["sample"], _POOL_STATE["options"]
-    from .segmentplot import run_hash_lineplot
-    run_hash_lineplot.DEVICE = None           # helpers never touch the GPU
-    backlog = collections.deque()             # control messages that arrived in front of a "hashres": handled in their turn
-    current = [None]                          # the window being collected
+    "hashres" only to a helper that has sent "hash" and since then does nothing but read its pipe until that reply.
 
-    def remote_hash(bases, desc, k, min_accept):
-        """The device executor of the owner, for the jobs of the window this helper is collecting."""
-        conn.send(("hash", current[0], k, min_accept, bases, desc))
+    One method per message of the owner, named like the message; :meth:`run` hands each its fields until "stop"."""
+
+    def __init__(self, conn):
+        self.conn, self.options = conn, _POOL_STATE["options"]
+        sample = _POOL_STATE["sample"]
+        run_hash_lineplot.DEVICE = None           # helpers never touch the GPU
+        self.backlog = collections.deque()        # control messages that arrived in front of a "hashres": handled in their turn
+        self.current = None                       # the window being collected
+        # (SVX_HASH_BATCH=0: the helpers run the host aligner job by job, as before the window's jobs went to the owner)
+        run_hash_lineplot.REMOTE = self.remote_hash if run_hash_lineplot.batch_enabled() else None
+        if sample is not None:
+            sample.device_buffers = None          # a helper forked from a live owner: its copy of the Sample is host-only
+        # The cyclic collector finds nothing to free here (segments, signatures and lines die by reference count) but its
+        # young-generation passes cost 20 % of a window and a full pass over the alignment table's objects ~70 ms: it runs
+        # by hand, rarely.
+        gc.freeze()                               # (everything inherited from the owner, its garbage included, is never collected here: HelperPool.__init__)
+        gc.disable()
+        self.held = {}                            # wid -> [the window's WindowVote, seconds of its collection, seconds of its vote so far]
+        self.n_done = 0
+        self.samples = {None: sample}             # by key; None: the Sample of the fork / "scan"
+        self.header_dict = None
+
+    def run(self):
+        handlers = {name: getattr(self, name) for name in ("chrom", "drop", "opt", "scan", "win", "pred")}
         while True:
-            msg = conn.recv()
-            if msg[0] == "hashres" and msg[1] == current[0]:
+            msg = self.backlog.popleft() if self.backlog else self.conn.recv()
+            if msg[0] == "stop":
+                return
+            handlers[msg[0]](*msg[1:])            # (an unknown message: KeyError)
+
+    def remote_hash(self, bases, desc, k, min_accept):
+        """The device executor of the owner, for the jobs of the window this helper is collecting."""
+        self.conn.send(("hash", self.current, k, min_accept, bases, desc))
+        while True:
+            msg = self.conn.recv()
+            if msg[0] == "hashres" and msg[1] == self.current:
                 return None if msg[2] is None else (msg[2], msg[3], msg[4])     # None: the owner could not run them -> host aligner here
-            backlog.append(msg)                # "chrom", "drop", "opt" (or "stop"): after this window
+            self.backlog.append(msg)           # "chrom", "drop", "opt" (or "stop"): after this window
 
-    # (SVX_HASH_BATCH=0: the helpers run the host aligner job by job, as before the window's jobs went to the owner)
-    run_hash_lineplot.REMOTE = remote_hash if run_hash_lineplot.batch_enabled() else None
-    if sample is not None:
-        sample.device_buffers = None          # a helper forked from a live owner: its copy of the Sample is host-only
-    # The cyclic collector finds nothing to free here (segments, signatures and lines die by reference count) but its
-    # young-generation passes cost 20 % of a window and a full pass over the alignment table's objects ~70 ms: it runs
-    # by hand, rarely.
-    import gc
-    import time
-    gc.freeze()                               # (everything inherited from the owner, its garbage included, is never collected here: HelperPool.__init__)
-    gc.disable()
-    held = {}
-    n_done = 0
-    samples = {None: sample}
-    header_dict = None
-    while True:
-        msg = backlog.popleft() if backlog else conn.recv()
-        if msg[0] == "stop":
+    def chrom(self, key, meta):
+        if "references" in meta:                              # the header's dictionary travels with a helper's first part of a file only
+            self.header_dict = (meta["references"], meta["lengths"])
+        elif self.header_dict is None:
+            raise RuntimeError("helper: part %r announced without the header's sequence dictionary" % (key,))
+        else:
+            meta = dict(meta, references=self.header_dict[0], lengths=self.header_dict[1])
+        if key not in self.samples:
+            from .ingest import load_shared_sample
+            sample = self.samples[None]
+            self.samples[key] = load_shared_sample(meta, sample.fasta if sample is not None else _POOL_STATE.get("fasta"))
+
+    def drop(self, key):
+        self.samples.pop(key, None)
+
+    def opt(self, name, value):
+        _POOL_STATE[name] = value
+
+    def scan(self, min_sv, gaps, gap_off, stats):
+        """Forked before the device scan existed: build the Sample now."""
+        from .sample import Sample
+        gaps, gap_off, stats = (np.load(p, mmap_mode="c") for p in (gaps, gap_off, stats))     # copy-on-write: windows' rescans land here
+        self.samples[None] = Sample.with_scan(_POOL_STATE["table"], _POOL_STATE["fasta"], min_sv, (gaps, gap_off, stats))
+
+    def win(self, wid, key, chrom, start, end, scan):
+        t0 = time.perf_counter()
+        smp = self.samples[key]
+        self.current = wid
+        if scan is not None:
+            smp.apply_window_scan(*scan)
+        lines, ok = _collect_parts(smp, self.options, chrom, start, end, self.send_part)
+        self.held[wid] = [WindowVote(smp, self.options, chrom, lines, start, end), time.perf_counter() - t0, 0.0]
+        self.conn.send(("rec", wid, len(lines), ok))
+
+    def send_part(self, part):
+        """Lines of the window being collected -> the owner, as records."""
+        self.conn.send(("part", self.current, np.asarray([ln.record() for ln in part], np.int32).reshape(-1, 12)))
+
+    def pred(self, wid, classes, probs, last):
+        state = self.held[wid]
+        vote = state[0]
+        t0 = time.perf_counter()
+        if vote.lines:                                        # (a window whose collection failed has none: whatever was predicted is dropped)
+            vote.feed(classes, probs)
+        if not last:
+            state[2] += time.perf_counter() - t0
             return
-        if msg[0] == "chrom":
-            meta = msg[2]
-            if "references" in meta:                          # the header's dictionary travels with a helper's first part of a file only
-                header_dict = (meta["references"], meta["lengths"])
-            elif header_dict is None:
-                raise RuntimeError("helper: part %r announced without the header's sequence dictionary" % (msg[1],))
-            else:
-                meta = dict(meta, references=header_dict[0], lengths=header_dict[1])
-            if msg[1] not in samples:
-                from .ingest import load_shared_sample
-                samples[msg[1]] = load_shared_sample(meta, sample.fasta if sample is not None else _POOL_STATE.get("fasta"))
-            continue
-        if msg[0] == "drop":
-            samples.pop(msg[1], None)
-            continue
-        if msg[0] == "opt":
-            _POOL_STATE[msg[1]] = msg[2]
-            continue
-        if msg[0] == "scan":                                  # forked before the device scan existed: build the Sample now
-            from .sample import Sample
-            _t, min_sv, gaps, gap_off, stats = msg
-            gaps, gap_off, stats = (np.load(p, mmap_mode="c") for p in (gaps, gap_off, stats))     # copy-on-write: windows' rescans land here
-            sample = samples[None] = Sample.with_scan(_POOL_STATE["table"], _POOL_STATE["fasta"], min_sv, (gaps, gap_off, stats))
-            continue
-        if msg[0] == "win":
-            _t, wid, key, chrom, start, end, scan = msg
-            t0 = time.perf_counter()
-            smp = samples[key]
-            current[0] = wid
-            if scan is not None:
-                smp.apply_window_scan(*scan)
+        vcf, scores, n_sites, head, tail = vote.finish()
+        lines = vote.lines
+        tsv = "".join(ln.text() for ln in lines) if _POOL_STATE.get("want_tsv") else None
+        del self.held[wid]
+        self.conn.send(("done", wid, vcf, scores, n_sites, len(lines), tsv, head, tail, (state[1], state[2] + time.perf_counter() - t0), _edge_regions(lines)))
+        self.n_done += 1
+        if self.n_done % 128 == 0:
+            gc.collect()
 
-            def emit(part, wid=wid):
-                conn.send(("part", wid, np.asarray([ln.record() for ln in part], np.int32).reshape(-1, 12)))
 
-            lines, ok = _collect_parts(smp, options, chrom, start, end, emit)
-            held[wid] = [WindowVote(smp, options, chrom, lines, start, end), time.perf_counter() - t0, 0.0]
-            conn.send(("rec", wid, len(lines), ok))
-        elif msg[0] == "pred":
-            _t, wid, classes, probs, last = msg
-            state = held[wid]
-            vote = state[0]
-            t0 = time.perf_counter()
-            if vote.lines:                                    # (a window whose collection failed has none: whatever was predicted is dropped)
-                vote.feed(classes, probs)
-            if not last:
-                state[2] += time.perf_counter() - t0
-                continue
-            vcf, scores, n_sites, head, tail = vote.finish()
-            lines = vote.lines
-            tsv = "".join(ln.text() for ln in lines) if _POOL_STATE.get("want_tsv") else None
-            del held[wid]
-            conn.send(("done", wid, vcf, scores, n_sites, len(lines), tsv, head, tail, (state[1], state[2] + time.perf_counter() - t0), _edge_regions(lines)))
-            n_done += 1
-            if n_done % 128 == 0:
-                gc.collect()
+def _worker_main(conn):
+    """Target of a helper process."""
+    _Helper(conn).run()
 
 
 class HelperPool:
@@ -529,7 +543,6 @@ class HelperPool:
         # collected HERE, by the process that owns the device: a forked helper that collected it would free them through a
         # runtime it must not touch (a segmentation fault in the helpers' first collection, seen once a test in the same process
         # had raised out of kernels.cigar_scan).
-        import gc
         gc.collect()
         self.conns, self.procs = [], []
         for _ in range(n_workers):
@@ -544,7 +557,6 @@ class HelperPool:
     def attach_scan(self, sample):
         """Hand the device scan's result to the helpers through one set of files in shared memory (mapped read-only by
         every helper) rather than through N pipes."""
-        import tempfile
         shm = "/dev/shm" if os.path.isdir("/dev/shm") and os.access("/dev/shm", os.W_OK) else None
         self._scan_dir = tempfile.mkdtemp(prefix="svx_scan_", dir=shm)
         paths = []
@@ -570,7 +582,6 @@ class HelperPool:
             p.join(timeout=5)
         self.conns, self.procs = [], []
         if getattr(self, "_scan_dir", None):
-            import shutil
             shutil.rmtree(self._scan_dir, ignore_errors=True)
             self._scan_dir = None
 
@@ -620,6 +631,307 @@ class ImageQueue:
         self.images -= sum(int(p[2].shape[0]) for p in self.parts if p[0] == wid)
         self.parts = keep
         self.seen.pop(wid, None)
+
+
+FLUSH_AFTER = 0.002                           # seconds a part may wait for a launch granule to fill up
+
+
+def launch_limits(sizes, batch, max_inflight):
+    """-> (granule, cap): the launch granule of a device stage with these launch ``sizes`` -- four batches, or its largest
+    launch when it has none of that size -- and the most images in flight."""
+    granule = 4 * batch if 4 * batch in sizes else max(sizes)
+    return granule, max(1, max_inflight) * 8 * granule
+
+
+def launch_size(pending, inflight_images, granule, cap_images, any_inflight, collecting, windows_left, oldest_age):
+    """-> (images of the next launch, is it a partial one); 0: none now.  ``pending`` images queued, the oldest for
+    ``oldest_age`` seconds; ``collecting`` windows whose last part has not arrived; ``windows_left`` to assign."""
+    room = cap_images - inflight_images
+    if pending <= 0 or room <= 0:
+        return 0, False
+    if pending >= granule:
+        # small groups: a window's predictions return as soon as its own launches are done (and, when nothing
+        # is being collected any more, launch by launch: the last vote is what the job's end waits for)
+        return min(pending, room, granule if collecting == 0 and not windows_left else 2 * granule) // granule * granule, False
+    if not any_inflight or collecting == 0 or oldest_age > FLUSH_AFTER:
+        return pending, True                                  # the device would idle / nothing else can arrive / it has waited
+    return 0, False
+
+
+def wait_timeout(device_busy, windows_left, helper_idle):
+    """Seconds the owner waits for its helpers' pipes: ``device_busy`` (launches in flight or pending, re-aligner batches under
+    way) it comes back to poll them; with a window and a helper for it but no part of its chromosome yet, to ask the feed."""
+    return 0.0005 if device_busy else (0.002 if windows_left and helper_idle else 0.05)
+
+
+class WindowPredictions:
+    """The predictions of one window on their way from the launch groups to helper ``ci``, which votes as they come.
+
+    ``add`` takes the chunks in launch order (= window order); ``take`` -> (classes, probs, last) of what has arrived since
+    the last call, or None.  None as long as the helper has not reported the window's size (``sized``): until then it is
+    collecting, not reading its pipe, and a send could block the owner on a full pipe.  ``last`` with the window's last
+    image -- at once, and empty, for a window without images or one whose collection failed (``fail``); what is still in
+    flight of a failed window is ignored.  ``add(..., keep=True)`` keeps a copy for :meth:`predictions`."""
+
+    def __init__(self, ci):
+        self.ci, self.total, self.got, self.chunks, self.kept, self.dropped, self.closed = ci, None, 0, [], [], False, False
+
+    def add(self, w_off, classes, probs, keep=False):
+        if self.dropped:
+            return
+        self.chunks.append((classes, probs))
+        if keep:
+            self.kept.append((w_off, np.array(classes), np.array(probs)))
+        self.got += len(classes)
+
+    def sized(self, n_images):
+        self.total = n_images
+
+    def fail(self):
+        self.chunks, self.total, self.got, self.dropped = [], 0, 0, True
+
+    def take(self):
+        if self.total is None or self.closed:
+            return None
+        last = self.got == self.total
+        chunks, self.chunks = self.chunks, []
+        if not chunks and not last:
+            return None
+        self.closed = last
+        return _joined([c[0] for c in chunks], [c[1] for c in chunks]) + (last,)
+
+    def predictions(self):
+        """The kept chunks in window order -> (classes, probs)."""
+        parts = sorted(self.kept, key=lambda t: t[0])
+        return _joined([t[1] for t in parts], [t[2] for t in parts])
+
+
+def _joined(classes, probs):
+    if len(classes) == 1:
+        return classes[0], probs[0]
+    if not classes:
+        return np.empty(0, np.int64), np.empty((0, 5), np.float32)
+    return np.concatenate(classes), np.concatenate(probs)
+
+
+class _OwnerRun:
+    """One run of :meth:`PooledHotPath.run_windows`: the loop's state, each stage a method.  A turn of the loop, in order:
+
+        assign      idle helpers get the next windows: the feed's part of the chromosome, its announcement, the window's
+                    device scan (enqueued ``ahead``, read back here) and "win".  Blocks on the scan's event; sends to
+                    idle helpers only, which read their pipes.
+        launch      pending images leave in launch groups (:func:`launch_size`).  Enqueues; never blocks.
+        fetch       finished groups give predictions, which go to the windows' :class:`WindowPredictions` and on to the
+                    helpers.  Sends to helpers that have reported "rec" only.
+        poll_hash   the re-aligner handles: a finished one is answered ("hashres", to the helper that waits for it).
+        wait        for a helper's message (:func:`wait_timeout`), or -- nothing assigned, launched or pending -- for the
+                    feed's next chromosome.  A helper that died while holding a window raises here.
+        receive     one message: ``on_part``, ``on_rec``, ``on_hash``, ``on_done`` (-> the window's WindowResult).
+
+    ``hp`` gives the device operations (``launch(group)``, ``fetch_predictions(group)``), ``stage.sizes``, ``batch``,
+    ``max_inflight``, the helpers' connections and the feed."""
+
+    def __init__(self, hp, windows, rescan):
+        self.hp, self.windows, self.rescan = hp, list(windows), rescan
+        self.launch_group, self.fetch_predictions = hp.launch, hp.fetch_predictions
+        self.nxt = 0                              # the next window to assign
+        self.idle = list(range(len(hp.conns)))
+        self.busy = {}                            # conn index -> wid
+        self.wins = {}                            # wid -> WindowPredictions, until the window's "done"
+        self.pending = ImageQueue()               # the parts not launched yet
+        self.inflight = collections.deque()       # (launch group as a WindowResult, [(wid, window offset, group offset, count)])
+        self.inflight_images = 0
+        self.collecting = 0                       # windows sent to a helper whose last part has not arrived
+        self.granule, self.cap_images = launch_limits(hp.stage.sizes, hp.batch, hp.max_inflight)
+        self.scans = collections.deque()          # handles of the window scans enqueued ahead (Sample.rescan_window_async)
+        self.ahead = min(16, len(hp.conns) + 2)   # every helper can turn idle in one burst; a scan takes ~15 ms on the saturated device
+        self.remaining = len(self.windows)
+        self.hashing = collections.deque()        # (conn index, wid, kernels.HashSeedsHandle) of the helpers' --hash requests under way
+        self.prof = collections.defaultdict(float)
+        if hp.options.hash:
+            self.prof.update({"hash.requests": 0, "hash.jobs": 0, "hash.launches": 0, "hash.wait_s": 0.0})
+        self.handlers = {"part": self.on_part, "rec": self.on_rec, "hash": self.on_hash, "done": self.on_done}
+        self.clock = time.perf_counter
+        self.t = self.t_loop = self.clock()       # t: where the running phase of the profile began
+
+    def lap(self, key, since):
+        now = self.clock()
+        self.prof[key] += now - since
+        return now
+
+    # ---- assign -------------------------------------------------------------------------------------------------------
+    def assign(self):
+        hp, windows = self.hp, self.windows
+        self.t = self.clock()                                         # a turn begins
+        while self.idle and self.nxt < len(windows):
+            chrom, start, end = windows[self.nxt]
+            key, smp = hp.feed.get(chrom, block=False, start=start)   # file-driven runs: is the window's part of the chromosome decoded + scanned yet?
+            for k, _c, meta in hp.feed.take_fresh():                  # where it lies in shared memory: told to a helper with its first window of it
+                hp._chrom_meta[k] = meta
+            if smp is None:
+                self.prof["feed.not_ready"] += 1
+                break
+            ci = self.idle.pop()
+            hp._announce(ci, key)
+            scan = self.window_scan() if self.rescan else None        # device scan of the window's block: the helper collects on ITS result
+            hp.conns[ci].send(("win", self.nxt, key, chrom, start, end, scan))
+            self.busy[ci] = self.nxt
+            self.wins[self.nxt] = WindowPredictions(ci)
+            self.collecting += 1
+            self.nxt += 1
+        self.t = self.lap("scan+send", self.t)
+
+    def window_scan(self):
+        """The scan of window ``nxt``'s rows, enqueued several windows ahead and read back here -> what its helper applies."""
+        sample, prof, windows, scans, nxt = self.hp.sample, self.prof, self.windows, self.scans, self.nxt
+        t_s = self.clock()
+        want = self.ahead if nxt else 1                               # the very first window leaves before the scans of the next ones are enqueued (0.25 ms each)
+        while len(scans) < want and nxt + len(scans) < len(windows):
+            scans.append(sample.rescan_window_async(*windows[nxt + len(scans)]))
+        t_s = self.lap("scan.enqueue", t_s)
+        handle = scans.popleft()
+        if handle is not None:
+            prof["scan.n"] += 1
+            prof["scan.ready_on_entry"] += 1 if handle.event.query() else 0
+            prof["scan.age_s"] += self.clock() - handle.enqueued_at
+            handle.event.synchronize()
+        t_s = self.lap("scan.sync", t_s)
+        scan = sample.last_window_scan if sample.finish_rescan(handle) else None
+        self.lap("scan.apply", t_s)
+        return scan
+
+    # ---- launch, fetch ------------------------------------------------------------------------------------------------
+    def launch(self):
+        pending, prof = self.pending, self.prof
+        while pending.images:
+            n, partial = launch_size(pending.images, self.inflight_images, self.granule, self.cap_images, bool(self.inflight), self.collecting,
+                                     self.nxt < len(self.windows), self.clock() - pending.oldest())
+            if n == 0:
+                break
+            if partial:
+                prof["launch.partial"] += 1
+            group = WindowResult()
+            group.records, mapping = pending.take(n)
+            group.n_images, group.lines, group.packed = n, None, None
+            prof.setdefault("first_launch_at", self.clock() - self.t_loop)
+            self.inflight.append((self.launch_group(group), mapping))
+            self.inflight_images += n
+        self.t = self.lap("launch", self.t)
+
+    def fetch(self):
+        inflight, keep = self.inflight, self.hp.keep_predictions
+        while inflight and inflight[0][0].done_event.query():
+            group, mapping = inflight.popleft()
+            self.inflight_images -= group.n_images
+            classes, probs = self.fetch_predictions(group)
+            touched = {}
+            for wid, w_off, g_off, k in mapping:
+                w = self.wins.get(wid)
+                if w is None:                                         # a failed window that is "done" already
+                    continue
+                w.add(w_off, classes[g_off:g_off + k], probs[g_off:g_off + k], keep)     # groups complete in launch order: window order
+                touched[wid] = True
+            for wid in touched:
+                self.forward(wid)
+            self.prof["last_fetch_at"] = self.clock() - self.t_loop
+        self.t = self.lap("fetch+send", self.t)
+
+    def forward(self, wid):
+        """Send the predictions that have arrived for a window on to its helper -- once it has reported the window's size
+        and so reads its pipe (:class:`WindowPredictions`)."""
+        w = self.wins[wid]
+        out = w.take()
+        if out is not None:
+            self.hp.conns[w.ci].send(("pred", wid) + out)
+
+    # ---- the re-aligner's handles ---------------------------------------------------------------------------------------
+    def poll_hash(self):
+        hashing, prof = self.hashing, self.prof
+        for _n in range(len(hashing)):                                # re-aligner batches: on a stream of their own, polled like the launches
+            ci, wid, handle = hashing.popleft()
+            try:
+                ready = handle.done()
+                reply = ("hashres", wid) + handle.result() if ready else None
+            except Exception as exc:                                  # noqa: BLE001 -- e.g. out of device memory: the helper re-aligns on the host
+                logging.error("[ERROR]: %s. --hash jobs of window %s go back to its helper", exc, wid)
+                ready, reply = True, ("hashres", wid, None, None, None)
+                prof["hash.failed"] += 1
+            if ready:
+                self.hp.conns[ci].send(reply)
+                prof["hash.launches"] += handle.launches
+            else:
+                hashing.append((ci, wid, handle))
+        if prof.get("hash.requests"):
+            self.t = self.lap("hash.wait_s", self.t)
+
+    # ---- wait, receive ------------------------------------------------------------------------------------------------
+    def wait(self):
+        """-> the connections that have a message."""
+        hp, busy = self.hp, self.busy
+        waiting = [hp.conns[ci] for ci in busy]
+        launched = bool(self.inflight or self.pending.images)
+        left = self.nxt < len(self.windows)
+        if not waiting and not launched and left:
+            hp.feed.poll(block=True)                                  # nothing to do but wait for the next chromosome
+            self.lap("feed.wait", self.t)
+            return []
+        got = mpc.wait(waiting, timeout=wait_timeout(launched or bool(self.hashing), left, bool(self.idle)))
+        self.lap("wait", self.t)
+        if not got and not launched:
+            dead = [ci for ci in busy if not hp.procs[ci].is_alive()]
+            if dead:
+                raise RuntimeError("host helper process %s died while holding window %s" % (dead, [busy[ci] for ci in dead]))
+        return got
+
+    def receive(self, c):
+        """One message of a helper -> the WindowResult it completes ("done"), else None."""
+        msg = c.recv()
+        return self.handlers[msg[0]](self.hp.conns.index(c), *msg[1:])     # (an unknown message: KeyError)
+
+    def on_part(self, ci, wid, records):
+        self.pending.add(wid, records, self.clock())
+
+    def on_rec(self, ci, wid, n_images, ok):
+        self.collecting -= 1
+        if ok:
+            self.wins[wid].sized(n_images)
+        else:                                                         # the window's collection failed after parts had left: drop them
+            self.pending.drop(wid)
+            self.wins[wid].fail()                                     # launches of it still in flight are ignored
+        self.forward(wid)                                             # (a failed window: an empty last message, the helper votes on no lines)
+
+    def on_hash(self, ci, wid, k, min_accept, bases, desc):
+        """A collecting helper's re-aligner jobs: enqueued, answered by :meth:`poll_hash`."""
+        prof = self.prof
+        t_h = self.clock()
+        prof["hash.requests"] += 1
+        prof["hash.jobs"] += len(desc)
+        try:
+            more = {} if run_hash_lineplot.MAX_PIECE is None else {"max_piece": run_hash_lineplot.MAX_PIECE}
+            self.hashing.append((ci, wid, kernels.hash_seeds_async(bases, desc, k, min_accept, self.hp.device, **more)))
+        except Exception as exc:                                      # noqa: BLE001 -- costs the request, not the run: answered at once
+            logging.error("[ERROR]: %s. --hash jobs of window %s go back to its helper", exc, wid)
+            self.hp.conns[ci].send(("hashres", wid, None, None, None))
+            prof["hash.failed"] += 1
+        prof["hash.wait_s"] += self.clock() - t_h
+
+    def on_done(self, ci, wid, vcf, scores, n_sites, n_images, tsv, head, tail, host_s, edges):
+        prof = self.prof
+        prof["helper.collect_s"] += host_s[0]                         # host seconds inside the helpers
+        prof["helper.vote_s"] += host_s[1]
+        res = WindowResult()
+        res.chrom, res.start, res.end = self.windows[wid]
+        res.wid, res.tsv = wid, tsv
+        res.vcf, res.scores, res.n_sites, res.n_images = vcf, scores, n_sites, n_images
+        res.head, res.tail, res.edges = head, tail, edges
+        res.n_records = vcf.count("\n")
+        w = self.wins.pop(wid)
+        res.classes, res.probs = w.predictions() if self.hp.keep_predictions else (None, None)
+        del self.busy[ci]
+        self.idle.append(ci)
+        self.remaining -= 1
+        prof["last_done_at"] = self.clock() - self.t_loop
+        return res
 
 
 class PooledHotPath(HotPath):
@@ -705,208 +1017,17 @@ class PooledHotPath(HotPath):
 
         ``self.owner_profile`` afterwards: where this (GPU-owning) thread spent its time -- seconds per phase of the
         loop, the scans found ready on entry, the host seconds the helpers report for collection and vote, and when the
-        first launch / last read-back / last result happened (SVX_TIMING=1 python bench.py prints it)."""
-        import time
-        windows = list(windows)
-        nxt = 0
-        idle = list(range(len(self.conns)))
-        busy = {}                     # conn index -> wid
-        wins = {}                     # wid -> state of a window whose predictions are not complete yet
-        pending = ImageQueue()        # the parts not launched yet
-        inflight = collections.deque()  # (launch group as a WindowResult, [(wid, window offset, group offset, count)])
-        inflight_images = 0
-        collecting = 0                # windows sent to a helper whose last part has not arrived
-        granule = 4 * self.batch if 4 * self.batch in self.stage.sizes else max(self.stage.sizes)
-        cap_images = max(1, self.max_inflight) * 8 * granule
-        flush_after = 0.002
-        scans = collections.deque()     # handles of the window scans enqueued ahead (Sample.rescan_window_async)
-        ahead = min(16, len(self.conns) + 2)    # every helper can turn idle in one burst; a scan takes ~15 ms on the saturated device
-        remaining = len(windows)
-        kept = {}                     # wid -> [(window offset, classes, probs)] (keep_predictions)
-        prof = self.owner_profile = collections.defaultdict(float)
-        hashing = collections.deque()   # (conn index, wid, kernels.HashSeedsHandle) of the helpers' --hash requests under way
-        if self.options.hash:
-            prof.update({"hash.requests": 0, "hash.jobs": 0, "hash.launches": 0, "hash.wait_s": 0.0})
-        clock = time.perf_counter
-        t_loop = clock()
+        first launch / last read-back / last result happened (SVX_TIMING=1 python bench.py prints it).
 
-        def lap(key, since):
-            now = clock()
-            prof[key] += now - since
-            return now
-
-        def take(n):
-            """The first ``n`` pending images as one launch group."""
-            records, mapping = pending.take(n)
-            group = WindowResult()
-            group.records, group.n_images, group.lines, group.packed = records, n, None, None
-            return group, mapping
-
-        def forward(wid):
-            """Send the predictions that have arrived for a window on to its helper, which votes as they come.  Only
-            once the helper has reported the window's size: until then it is collecting, not reading its pipe, and a
-            send could block this thread on a full pipe."""
-            w = wins[wid]
-            if w["total"] is None:
-                return
-            last = w["got"] == w["total"]
-            chunks, w["chunks"] = w["chunks"], []
-            if chunks:
-                classes = chunks[0][1] if len(chunks) == 1 else np.concatenate([c[1] for c in chunks])
-                probs = chunks[0][2] if len(chunks) == 1 else np.concatenate([c[2] for c in chunks])
-            elif last:
-                classes, probs = np.empty(0, np.int64), np.empty((0, 5), np.float32)
-            else:
-                return
-            self.conns[w["ci"]].send(("pred", wid, classes, probs, last))
-            if last:
-                del wins[wid]
-
-        while remaining:
-            t = clock()
-            while idle and nxt < len(windows):
-                chrom, start, end = windows[nxt]
-                key, smp = self.feed.get(chrom, block=False, start=start)     # file-driven runs: is the window's part of the chromosome decoded + scanned yet?
-                for k, _c, meta in self.feed.take_fresh():            # where it lies in shared memory: told to a helper with its first window of it
-                    self._chrom_meta[k] = meta
-                if smp is None:
-                    prof["feed.not_ready"] += 1
-                    break
-                ci = idle.pop()
-                self._announce(ci, key)
-                scan = None
-                if rescan:                                            # device scan of the window's block: the helper collects on ITS result
-                    t_s = clock()
-                    want = ahead if nxt else 1                        # the very first window leaves before the scans of the next ones are enqueued (0.25 ms each)
-                    while len(scans) < want and nxt + len(scans) < len(windows):     # enqueued several windows ahead, read back here
-                        scans.append(self.sample.rescan_window_async(*windows[nxt + len(scans)]))
-                    t_s = lap("scan.enqueue", t_s)
-                    handle = scans.popleft()
-                    if handle is not None:
-                        prof["scan.n"] += 1
-                        prof["scan.ready_on_entry"] += 1 if handle[5].query() else 0
-                        prof["scan.age_s"] += clock() - handle[7]
-                        handle[5].synchronize()
-                    t_s = lap("scan.sync", t_s)
-                    scan = self.sample.last_window_scan if self.sample.finish_rescan(handle) else None
-                    lap("scan.apply", t_s)
-                self.conns[ci].send(("win", nxt, key, chrom, start, end, scan))
-                busy[ci] = nxt
-                wins[nxt] = {"ci": ci, "total": None, "got": 0, "chunks": []}
-                collecting += 1
-                nxt += 1
-            t = lap("scan+send", t)
-            while pending.images and inflight_images < cap_images:
-                room = cap_images - inflight_images
-                if pending.images >= granule:
-                    # small groups: a window's predictions return as soon as its own launches are done (and, when nothing
-                    # is being collected any more, launch by launch: the last vote is what the job's end waits for)
-                    n = min(pending.images, room, granule if collecting == 0 and nxt >= len(windows) else 2 * granule) // granule * granule
-                    if n == 0:
-                        break
-                elif not inflight or collecting == 0 or clock() - pending.oldest() > flush_after:
-                    n = pending.images                                # the device would idle / nothing else can arrive / it has waited
-                    prof["launch.partial"] += 1
-                else:
-                    break
-                group, mapping = take(n)
-                prof.setdefault("first_launch_at", clock() - t_loop)
-                inflight.append((self.launch(group), mapping))
-                inflight_images += n
-            t = lap("launch", t)
-            while inflight and inflight[0][0].done_event.query():
-                group, mapping = inflight.popleft()
-                inflight_images -= group.n_images
-                classes, probs = self.fetch_predictions(group)
-                touched = {}
-                for wid, w_off, g_off, k in mapping:
-                    w = wins.get(wid)
-                    if w is None or w.get("drop"):
-                        continue
-                    w["chunks"].append((w_off, classes[g_off:g_off + k], probs[g_off:g_off + k]))     # groups complete in launch order: window order
-                    if self.keep_predictions:
-                        kept.setdefault(wid, []).append((w_off, np.array(classes[g_off:g_off + k]), np.array(probs[g_off:g_off + k])))
-                    w["got"] += k
-                    touched[wid] = True
-                for wid in touched:
-                    forward(wid)
-                prof["last_fetch_at"] = clock() - t_loop
-            t = lap("fetch+send", t)
-            for _n in range(len(hashing)):                            # re-aligner batches: on a stream of their own, polled like the launches
-                ci, wid, handle = hashing.popleft()
-                try:
-                    ready = handle.done()
-                    reply = ("hashres", wid) + handle.result() if ready else None
-                except Exception as exc:                              # noqa: BLE001 -- e.g. out of device memory: the helper re-aligns on the host
-                    logging.error("[ERROR]: %s. --hash jobs of window %s go back to its helper", exc, wid)
-                    ready, reply = True, ("hashres", wid, None, None, None)
-                    prof["hash.failed"] += 1
-                if ready:
-                    self.conns[ci].send(reply)
-                    prof["hash.launches"] += handle.launches
-                else:
-                    hashing.append((ci, wid, handle))
-            if prof.get("hash.requests"):
-                prof["hash.wait_s"] += clock() - t
-                t = clock()
-            waiting = [self.conns[ci] for ci in busy]
-            if not waiting and not inflight and not pending.images and nxt < len(windows):
-                self.feed.poll(block=True)                            # nothing to do but wait for the next chromosome
-                lap("feed.wait", t)
-                continue
-            got = mpc.wait(waiting, timeout=0.0005 if inflight or pending.images or hashing else (0.002 if nxt < len(windows) and idle else 0.05))
-            lap("wait", t)
-            if not got and not inflight and not pending.images:
-                dead = [ci for ci in busy if not self.procs[ci].is_alive()]
-                if dead:
-                    raise RuntimeError("host helper process %s died while holding window %s" % (dead, [busy[ci] for ci in dead]))
-            for c in got:
-                ci = self.conns.index(c)
-                msg = c.recv()
-                if msg[0] == "part":
-                    pending.add(msg[1], msg[2], clock())
-                elif msg[0] == "rec":
-                    _t, wid, n_images, ok = msg
-                    w = wins[wid]
-                    collecting -= 1
-                    if not ok:                                        # the window's collection failed after parts had left: drop them
-                        pending.drop(wid)
-                        w["chunks"], w["total"], w["got"] = [], 0, 0
-                        forward(wid)                                  # an empty last message: the helper votes on no lines
-                        wins[wid] = {"drop": True}                    # launches of it still in flight are ignored (entry never removed: wids are not reused)
-                        continue
-                    w["total"] = n_images
-                    forward(wid)
-                elif msg[0] == "hash":                                # a collecting helper's re-aligner jobs: enqueued, answered above
-                    _t, wid, k, min_accept, bases, desc = msg
-                    t_h = clock()
-                    prof["hash.requests"] += 1
-                    prof["hash.jobs"] += len(desc)
-                    try:
-                        more = {} if run_hash_lineplot.MAX_PIECE is None else {"max_piece": run_hash_lineplot.MAX_PIECE}
-                        hashing.append((ci, wid, kernels.hash_seeds_async(bases, desc, k, min_accept, self.device, **more)))
-                    except Exception as exc:                          # noqa: BLE001 -- costs the request, not the run: answered at once
-                        logging.error("[ERROR]: %s. --hash jobs of window %s go back to its helper", exc, wid)
-                        c.send(("hashres", wid, None, None, None))
-                        prof["hash.failed"] += 1
-                    prof["hash.wait_s"] += clock() - t_h
-                else:
-                    _t, wid, vcf, scores, n_sites, n_images, tsv, head, tail, host_s, edges = msg
-                    prof["helper.collect_s"] += host_s[0]             # host seconds inside the helpers
-                    prof["helper.vote_s"] += host_s[1]
-                    res = WindowResult()
-                    res.chrom, res.start, res.end = windows[wid]
-                    res.wid, res.tsv = wid, tsv
-                    res.vcf, res.scores, res.n_sites, res.n_images = vcf, scores, n_sites, n_images
-                    res.head, res.tail, res.edges = head, tail, edges
-                    res.n_records = vcf.count("\n")
-                    res.classes = res.probs = None
-                    if self.keep_predictions:
-                        parts = sorted(kept.pop(wid, []), key=lambda t: t[0])
-                        res.classes = np.concatenate([t[1] for t in parts]) if parts else np.empty(0, np.int64)
-                        res.probs = np.concatenate([t[2] for t in parts]) if parts else np.empty((0, 5), np.float32)
-                    del busy[ci]
-                    idle.append(ci)
-                    remaining -= 1
-                    prof["last_done_at"] = clock() - t_loop
+        One turn of the loop is the stages of :class:`_OwnerRun` in order; a result is yielded as its "done" is read."""
+        run = _OwnerRun(self, windows, rescan)
+        self.owner_profile = run.prof
+        while run.remaining:
+            run.assign()
+            run.launch()
+            run.fetch()
+            run.poll_hash()
+            for c in run.wait():
+                res = run.receive(c)
+                if res is not None:
                     yield res

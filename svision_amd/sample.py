@@ -6,9 +6,17 @@ This is the object the reference's ``sample_path`` argument stands for
 once per process, uploaded once, and every alignment's long gaps / reference span /
 clip lengths come from one ``svx_cigar_scan`` launch sequence).
 """
+import collections
+import time
+
 import numpy as np
 
 from .io.bam import Fasta, read_bam
+
+# A window scan under way (Sample.rescan_window_async): rows [lo, hi), ``cap`` gaps expected (``capd``: the device arrays'
+# capacity), the pinned ``host`` buffer its result is copied to, the ``event`` behind the copies, the device ``result``
+# (kept alive until then) and when it was enqueued.
+WindowScanHandle = collections.namedtuple("WindowScanHandle", "lo hi cap capd host event result enqueued_at")
 
 _CACHE = {}
 _MARK = None                                                 # (SVX_TIMING: ingest._run points this at the decoder's trace)
@@ -171,8 +179,7 @@ class Sample:
             host[n + 1 + capd * 6:need].copy_(res.stats.view(-1), non_blocking=True)
             ev = torch.cuda.Event()
             ev.record()
-        import time
-        return (lo, hi, cap, capd, host, ev, res, time.perf_counter())
+        return WindowScanHandle(lo, hi, cap, capd, host, ev, res, time.perf_counter())
 
     def finish_rescan(self, handle):
         """Wait for an enqueued window scan, check it against the resident scan and install it; -> number of rows."""
@@ -180,8 +187,8 @@ class Sample:
         if handle is None:
             self.last_window_scan = None
             return 0
-        lo, hi, cap, capd, host, ev, _res = handle[:7]
-        ev.synchronize()
+        lo, hi, cap, capd, host = handle.lo, handle.hi, handle.cap, handle.capd, handle.host
+        handle.event.synchronize()
         n = hi - lo
         h = host.numpy()
         gap_off = h[:n + 1].view(np.uint32).copy()

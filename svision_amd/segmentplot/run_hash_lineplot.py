@@ -25,7 +25,7 @@ def select_longest(segments):
 DEVICE = None        # torch.device of the process that owns a GPU (set by Sample.from_table); None in the forked host helpers
 MAX_PIECE = None     # longest piece the device takes: None = the short kernel's kernels.HASH_MAX_X; a --hash run of the command line sets
                      # kernels.HASH_LONG_MAX_X before the helpers fork (svx_hash_seeds_long), SVX_HASH_LONG=0 leaves it None
-REMOTE = None        # in a host helper: callable (bases, desc, k, window) -> (counts, row_off, rows) or None, the owner's device by pipe (pipeline._worker_main)
+REMOTE = None        # in a host helper: callable (bases, desc, k, window) -> (counts, row_off, rows) or None, the owner's device by pipe (pipeline._Helper.remote_hash)
 
 
 def batch_enabled():
