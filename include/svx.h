@@ -25,7 +25,9 @@ extern "C" {
                                     * svx_bgzf_inflate_fast / _on take the inflated byte count and refuse a workspace that is too small (380);
                                     * + svx_cigar_scan_flat: the scan of long alignments in one pass (390); svx_cigar_scan takes the word count of its launch, its workspace's size and shape flags (400);
                                     * the exports the default path never calls moved to svx_experimental.h, + svx_bgzf_inflate_fast_lz there (410);
-                                    * svx_bam_walk_extract takes the number of records (a wave per record copies: ONT-shaped slices 14.7 -> ~1 ms) (420) */
+                                    * svx_bam_walk_extract takes the number of records (a wave per record copies: ONT-shaped slices 14.7 -> ~1 ms) (420);
+                                    * svx_bgzf_inflate_fast / _on resolve the LZ copies in a table in LDS where the device has room for it, svx_bgzf_inflate_fast_lz takes lz_kernel 3 (420, additive:
+                                    * no signature changed) */
 
 #define SVX_OK            0
 #define SVX_EINVAL       (-1)      /* bad argument (null pointer, bad layout...) */

@@ -54,7 +54,9 @@ int            svx_bgzf_inflate_wave(const uint8_t* d_comp, const uint64_t* d_sr
                                      const uint64_t* d_dst_off, uint32_t n_blocks, uint8_t* d_out, uint32_t* d_status, void* stream);
 
 /* svx_bgzf_inflate_fast_on with the LZ kernel by name: lz_kernel 0 = by the size of the launch (what svx_bgzf_inflate_fast_on
- * does), 1 = one lane per block, 2 = one wave per block. */
+ * does), 1 = one lane per block, 2 = one wave per block, 3 = one workgroup per block, the copies resolved by pointer doubling in a
+ * table in LDS (svx_lz_table.hip; SVX_EINVAL on a device whose workgroups cannot have the table's 128 KB of LDS; blocks above
+ * 0xFF00 bytes are left to svx_bgzf_inflate_wave's kernel, like the blocks whose sequence stream does not fit its slot). */
 int            svx_bgzf_inflate_fast_lz(const uint8_t* d_comp, const uint64_t* d_src_off, const uint32_t* d_src_len,
                                         const uint64_t* d_dst_off, uint32_t n_blocks, uint64_t inflated_bytes, uint8_t* d_out,
                                         uint32_t* d_status, void* d_ws, uint64_t ws_bytes, int lz_kernel, void* stream_tokens,

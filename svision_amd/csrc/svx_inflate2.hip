@@ -22,13 +22,15 @@
 //      costs ~100 instructions instead of ~300; ~10 k turns per 64 KB block instead of 36 k.
 //
 // Byte-identical to zlib by construction (tests/test_gpu_inflate.py runs this pair through every case the other kernels
-// pass).  Blocks whose sequence stream would not fit its slot (1.5 x ISIZE + 1 KB: only pathological streams -- hundreds of
+// pass).  On gfx950 the entry point replaces B by bgzf_lz_table_kernel (svx_lz_table.hip: no order between the sequences at all).
+// Blocks whose sequence stream would not fit its slot (1.5 x ISIZE + 1 KB: only pathological streams -- hundreds of
 // tiny DEFLATE blocks -- get there) are left to the wave-per-block kernel of svx_inflate.hip by the entry point.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
 #include "../../include/svx.h"
 #include "svx_lz_core.hpp"
+#include "svx_lz_table_core.hpp"
 
 #ifndef SVX_TOK_DBG
 #define SVX_TOK_DBG 0                // measurements only (wrong output): 1 = the Huffman tables are built twice, 2 = no transcode pass, 4 = no S1 pass
@@ -305,7 +307,7 @@ __device__ __forceinline__ uint32_t wave_excl_sum(uint32_t v, uint32_t* total)
 }
 
 // where block b's sequence stream lies in the workspace: 1.5 x its inflated bytes + 1 KB
-__host__ __device__ inline uint64_t stream_base(const uint64_t* dst_off, uint32_t b) { const uint64_t d = dst_off[b] - dst_off[0]; return d + (d >> 1) + 1024ull * b; }
+__host__ __device__ inline uint64_t stream_base(const uint64_t* dst_off, uint32_t b) { return svx_lzt::slot_base(dst_off, b); }
 
 __device__ __forceinline__ void put32(uint8_t* p, uint32_t v) { __builtin_memcpy(p, &v, 4); }
 
@@ -723,7 +725,14 @@ extern "C" size_t svx_bgzf_inflate_fast_ws_bytes(uint64_t inflated_bytes, uint32
 extern "C" __attribute__((visibility("hidden"))) int svx_bgzf_inflate_wave_only(const uint8_t* d_comp, const uint64_t* d_src_off, const uint32_t* d_src_len, const uint64_t* d_dst_off,
                                           uint32_t n_blocks, uint8_t* d_out, uint32_t* d_status, uint32_t only, void* stream);
 
-// (include/svx_experimental.h: the LZ kernel by name -- 0 = by the size of the launch, 1 = lane per block, 2 = wave per block)
+// svx_lz_table.hip: the LZ copies by pointer doubling in LDS, a workgroup per block (SPLIT streams); blocks above 0xFF00 bytes get the
+// status `handover`.  _available: this device gives a workgroup the LDS the table needs.
+extern "C" __attribute__((visibility("hidden"))) int svx_bgzf_lz_table_available(void);
+extern "C" __attribute__((visibility("hidden"))) int svx_bgzf_lz_table(const uint8_t* streams, const void* stream_cnt, const uint64_t* d_dst_off, uint32_t n_blocks,
+                                                                        uint8_t* d_out, uint32_t* d_status, uint32_t handover, void* stream);
+
+// (include/svx_experimental.h: the LZ kernel by name -- 0 = by the size of the launch, 1 = lane per block, 2 = wave per block,
+// 3 = workgroup per block, the table kernel)
 extern "C" int svx_bgzf_inflate_fast_lz(const uint8_t* d_comp, const uint64_t* d_src_off, const uint32_t* d_src_len, const uint64_t* d_dst_off,
                                         uint32_t n_blocks, uint64_t inflated_bytes, uint8_t* d_out, uint32_t* d_status, void* d_ws, uint64_t ws_bytes,
                                         int lz_kernel, void* stream_tokens, void* stream_lz)
@@ -737,12 +746,16 @@ extern "C" int svx_bgzf_inflate_fast_lz(const uint8_t* d_comp, const uint64_t* d
     hipStream_t sa = static_cast<hipStream_t>(stream_tokens), sb = static_cast<hipStream_t>(stream_lz);
     uint2* stream_cnt = static_cast<uint2*>(d_ws);
     uint8_t* streams = static_cast<uint8_t*>(d_ws) + (((size_t)8 * n_blocks + 255) & ~(size_t)255);
-    // which LZ kernel: one wave per block (B': ~1 ms per block, 1,024 blocks at once) below WAVE_LZ_BELOW blocks, one lane per
-    // block (B: ~25 ms whatever the launch holds + 0.1 ms per 1,000 blocks) above.  lz_kernel 1 | 2: by name (measurements; an
-    // argument, not the environment: launches of several threads are in flight at once -- ADVICE r5).
+    // which LZ kernel: one workgroup per block (svx_lz_table.hip: 79 us per block and CU, the fastest at every launch size from 5 k
+    // to 85 k blocks -- profiles/lz_table.txt) wherever the device gives a workgroup the table's LDS; elsewhere one wave per block
+    // (B': ~1 ms per block, 1,024 blocks at once) below WAVE_LZ_BELOW blocks, one lane per block (B: ~25 ms whatever the launch
+    // holds + 0.1 ms per 1,000 blocks) above.  lz_kernel 1 | 2 | 3: by name (measurements; an argument, not the environment:
+    // launches of several threads are in flight at once -- ADVICE r5).
     static const uint32_t below = getenv("SVX_WAVE_LZ_BELOW") ? (uint32_t)atoi(getenv("SVX_WAVE_LZ_BELOW")) : (uint32_t)WAVE_LZ_BELOW;
-    if (lz_kernel < 0 || lz_kernel > 2) return SVX_EINVAL;
-    const bool wave_lz = lz_kernel ? lz_kernel == 2 : n_blocks < below;
+    if (lz_kernel < 0 || lz_kernel > 3) return SVX_EINVAL;
+    if (lz_kernel == 3 && !svx_bgzf_lz_table_available()) return SVX_EINVAL;
+    const bool table_lz = lz_kernel ? lz_kernel == 3 : svx_bgzf_lz_table_available() != 0;
+    const bool wave_lz = table_lz || (lz_kernel ? lz_kernel == 2 : n_blocks < below);     // (both read SPLIT streams)
     const char* only = getenv("SVX_INFLATE2_ONLY");                          // measurements: "A" = kernel A alone (the output stays unwritten),
     if (!only && getenv("SVX_INFLATE2_ONLY_A")) only = "A";                  // "B" = kernel B alone on the streams an earlier call left in the same workspace
     if (!only || only[0] != 'B') {
@@ -765,7 +778,8 @@ extern "C" int svx_bgzf_inflate_fast_lz(const uint8_t* d_comp, const uint64_t* d
         }
     }
     if (only && only[0] == 'A') return SVX_OK;
-    if (wave_lz) hipLaunchKernelGGL(bgzf_lz_wave_kernel, dim3(n_blocks), dim3(LANES), WRING + WSTAGE + 1024, sb, streams, stream_cnt, d_dst_off, n_blocks, d_out, d_status);
+    if (table_lz) { if (svx_bgzf_lz_table(streams, stream_cnt, d_dst_off, n_blocks, d_out, d_status, INF_TOKENS_OVERFLOW, sb) != SVX_OK) return SVX_ELAUNCH; }
+    else if (wave_lz) hipLaunchKernelGGL(bgzf_lz_wave_kernel, dim3(n_blocks), dim3(LANES), WRING + WSTAGE + 1024, sb, streams, stream_cnt, d_dst_off, n_blocks, d_out, d_status);
     else hipLaunchKernelGGL(bgzf_lz_kernel, dim3((n_blocks + LZ_LANES - 1) / LZ_LANES), dim3(LZ_LANES), LZ_LANES * RING_STRIDE, sb, streams, stream_cnt, d_dst_off, n_blocks, d_out, d_status);
     if (hipGetLastError() != hipSuccess) return SVX_ELAUNCH;
     // the (pathological) blocks whose sequence stream did not fit its slot: the wave-per-block kernel, those blocks only

@@ -40,7 +40,7 @@ import torch
 from . import _lib, kernels, streams
 from .io.bam import AlignmentTable, read_bai_linear
 
-FIRST_GROUP_BYTES = 192 << 20            # the first launch is small (~7 k blocks: the wave-per-block kernel): the pipeline starts after ~0.1 s
+FIRST_GROUP_BYTES = 192 << 20            # the first launch is small (~7 k blocks): the pipeline starts after ~0.1 s
 STAGE_BYTES = 64 << 20                   # a pinned staging slot of the reader (_StagingRing: eight of them)
 PIPE_GROUP_BYTES = 400 << 20             # the SECOND group: two slices (~14 k blocks) -- a ramp 192 / 400 / 600 MB.  Round 6, measured (profiles/r06_group_sweep.txt):
                                          # the five-window chr21 job (BASELINE configs[1]) is cut [1, 2, 2] instead of [1, 4] and takes 0.142 s instead of 0.172
@@ -48,7 +48,8 @@ PIPE_GROUP_BYTES = 400 << 20             # the SECOND group: two slices (~14 k b
                                          # The groups behind the first two: ~21 k blocks.  (Round 3 / early round 4: 768 MB, then 2.5 GB
 LARGE_GROUP_BYTES = 600 << 20            # -- a launch of the lane-per-block kernel cost 60-90 ms whatever it held.  The two-kernel inflate is
 LARGE_GROUP_BLOCKS = 94_000              # proportional to the launch, and once the read-backs no longer blocked each other (launch(), streams.py)
-                                         # a steady flow of small groups beat the large ones: the CNN behind never runs out of chromosomes.)
+                                         # a steady flow of small groups beat the large ones: the CNN behind never runs out of chromosomes.  With the table LZ kernel --
+                                         # no 25 ms floor per launch -- the sizes were swept again, profiles/lz_table.txt: nothing beat them by more than the spread.)
 GROUP_BYTES = 24 << 30                   # read by no code of the package any more (the serial decoder it sized is gone): tests/test_gpu_inflate.py saves and restores it with the other sizes
 SLICE_BYTES = 256 << 20                  # a chromosome is handed over in slices of whole collection windows of about this many compressed bytes
 MIN_MARGIN = 128 << 10                   # reference bases a slice's records reach beyond its windows on either side, at least (plan_units)

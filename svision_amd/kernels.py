@@ -693,7 +693,7 @@ def launch_inflate(lib, variant, comp_ptr, src_ptr, len_ptr, dst_ptr, n_blocks, 
     ``tokens_stream``: the "fast" form's first kernel goes there (svx_bgzf_inflate_fast_on), the rest stays on the current stream."""
     st = _stream_ptr(device)
     lz = None
-    if variant in ("fast-lane", "fast-wave"):                 # the "fast" form with its LZ kernel by name (tests, measurements)
+    if variant in ("fast-lane", "fast-wave", "fast-table"):   # the "fast" form with its LZ kernel by name (tests, measurements)
         lz, variant = variant[5:], "fast"
     if variant == "fast":
         d_ws = ws if ws is not None else inflate_workspace(lib, variant, inflated_bytes, n_blocks, device)
@@ -711,7 +711,7 @@ def _launch_fast(lib, comp_ptr, src_ptr, len_ptr, dst_ptr, n_blocks, inflated_by
     if lz is not None:                                        # the LZ kernel by name: an argument of the experimental entry point (svx_experimental.h)
         tok = ctypes.c_void_p(tokens_stream.cuda_stream) if tokens_stream is not None else st
         return lib.svx_bgzf_inflate_fast_lz(comp_ptr, src_ptr, len_ptr, dst_ptr, n_blocks, int(inflated_bytes), out_ptr, status_ptr, d_ws.data_ptr(), ws_bytes,
-                                            {"lane": 1, "wave": 2}[lz], tok, st)
+                                            {"lane": 1, "wave": 2, "table": 3}[lz], tok, st)
     if tokens_stream is not None:
         return lib.svx_bgzf_inflate_fast_on(comp_ptr, src_ptr, len_ptr, dst_ptr, n_blocks, int(inflated_bytes), out_ptr, status_ptr, d_ws.data_ptr(), ws_bytes,
                                             ctypes.c_void_p(tokens_stream.cuda_stream), st)

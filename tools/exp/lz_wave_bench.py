@@ -1,6 +1,8 @@
-"""The two LZ kernels of svx_bgzf_inflate_fast behind their tokens kernels, by launch size: one lane per block (B, svx_lz_core.hpp)
-against one wave per block (B', round 5).  HiFi-like BAM (random bases, binned qualities), its blocks tiled to the launch sizes.
-python tools/exp/lz_wave_bench.py [contig Mb, default 4]"""
+"""The three LZ kernels of svx_bgzf_inflate_fast behind their tokens kernels, by launch size: one lane per block (B, svx_lz_core.hpp),
+one wave per block (B', round 5) and one workgroup per block (the table kernel, svx_lz_table.hip).  HiFi-like BAM (random bases,
+binned qualities), its blocks tiled to the launch sizes.  Per size and kernel: the LZ kernel alone (SVX_INFLATE2_ONLY=B on the
+streams an earlier call left in the workspace) and tokens + LZ, HIP events around the launch, median of 7.
+python tools/exp/lz_wave_bench.py [contig Mb, default 4] [launch sizes in thousands of blocks, default 7,14,21,28,85]"""
 import os
 import sys
 import time
@@ -48,16 +50,57 @@ def run(variant, k, only=None):
     return best, out, status
 
 
-for variant in ("fast-lane", "fast-wave"):
+VARIANTS = ("fast-lane", "fast-wave", "fast-table")
+for variant in VARIANTS:
     _t, out, status = run(variant, 1)
     ok = not bool(status.any()) and out.cpu().numpy().tobytes() == want
     print(variant, "== zlib:", ok, flush=True)
-for k in (1, 2, 4, 8, 16, 32):
-    if n0 * k > 120_000:
-        break
-    row = ["%6d blocks" % (n0 * k)]
-    for variant in ("fast-lane", "fast-wave"):
-        ta, _o, _s = run(variant, k, only="A")
-        tt, _o, _s = run(variant, k)
-        row.append("%s: tokens %.1f ms, + LZ %.1f ms" % (variant, ta * 1e3, tt * 1e3))
-    print("   ".join(row), flush=True)
+    assert ok
+
+
+def events_ms(variant, k, only=None, reps=7):
+    """One launch of ``k`` copies of the file's blocks, everything uploaded and allocated beforehand -> median milliseconds."""
+    s, l, z = (np.concatenate([a] * k) for a in (src_off, src_len, isize))
+    n = len(z)
+    dst = np.zeros(n + 1, np.uint64)
+    dst[1:] = np.cumsum(z.astype(np.uint64))
+    total = int(dst[-1])
+    dev = d.device
+    d_src, d_len = torch.from_numpy(s.view(np.int64)).to(dev), torch.from_numpy(l.view(np.int32)).to(dev)
+    d_dst = torch.from_numpy(dst.view(np.int64)).to(dev)
+    d_out = torch.empty(total, dtype=torch.uint8, device=dev)
+    d_status = torch.zeros(n, dtype=torch.int32, device=dev)
+    ws = kernels.inflate_workspace(lib, "fast", total, n, dev)
+
+    def launch():
+        kernels.launch_inflate(lib, variant, d.data_ptr(), d_src.data_ptr(), d_len.data_ptr(), d_dst.data_ptr(), n, d_out.data_ptr(),
+                               d_status.data_ptr(), total, dev, ws=ws)
+    launch()                                                  # (leaves the streams in the workspace for the LZ-only runs)
+    torch.cuda.synchronize()
+    assert not bool(d_status.any())
+    times = []
+    if only:
+        os.environ["SVX_INFLATE2_ONLY"] = only
+    try:
+        for _ in range(reps):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            launch()
+            b.record()
+            torch.cuda.synchronize()
+            times.append(a.elapsed_time(b))
+    finally:
+        os.environ.pop("SVX_INFLATE2_ONLY", None)
+    return float(np.median(times)), n
+
+
+sizes = [int(float(v) * 1000) for v in (sys.argv[2] if len(sys.argv) > 2 else "7,14,21,28,85").split(",")]
+print("blocks   " + "   ".join("%-34s" % (v + ": LZ alone | tokens + LZ (ms)") for v in VARIANTS), flush=True)
+for size in sizes:
+    k = max(1, round(size / n0))
+    row = []
+    for variant in VARIANTS:
+        lz_ms, n = events_ms(variant, k, only="B")
+        all_ms, n = events_ms(variant, k)
+        row.append("%-34s" % ("%7.2f | %7.2f" % (lz_ms, all_ms)))
+    print("%6d   " % n + "   ".join(row), flush=True)
