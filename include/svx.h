@@ -474,6 +474,30 @@ int            svx_record_gather_offsets(const int64_t* d_off_in, const uint32_t
                                          uint64_t ws_bytes, void* stream);
 int            svx_record_gather_segments(const void* d_src, const int64_t* d_off_in, const uint32_t* d_order, const int64_t* d_off_out,
                                           void* d_dst, uint32_t n, uint32_t elem_bytes, void* stream);
+/* BGZF members FROM inflated bytes (svx_deflate.hip; ABI 420, additive): the encoder of svision_amd/sort.py, which writes the
+ * device-sorted BAM.
+ *   svx_bgzf_deflate    block b = the bytes d_in[d_in_off[b] .. d_in_off[b + 1]) -- any offsets, no alignment, 0 .. 0xFF00 bytes a block --
+ *                       becomes ONE complete BGZF member in slot b of d_slots [n_blocks][SVX_BGZF_SLOT]: the 18-byte header (1f 8b 08 04,
+ *                       MTIME 0, XFL 0, OS ff, XLEN 6, 'B' 'C' 2, BSIZE - 1), one final DEFLATE block, CRC32 of the input (the device
+ *                       function svx_bgzf_crc32 checks with), ISIZE.  d_member_len [b] = the member's bytes (a block of more than
+ *                       0xFF00 bytes: 0, nothing written), d_stored [b] = 1 where the DEFLATE block is stored.  The block: a greedy
+ *                       LZ77 parse -- lengths 3 .. 258, distances 1 .. 32,768, one hash-table candidate and the nearest one in the same
+ *                       wave per position -- in the FIXED Huffman code (BTYPE 01), or the bytes stored (BTYPE 00) whenever the fixed
+ *                       form would not be smaller: no member is longer than its block + 31 bytes, 65,311 for a full one.  An empty
+ *                       block gives the 28-byte BGZF end-of-file marker.  One workgroup per block, block and table in LDS.
+ *                       The member's bytes are a pure function of the block's bytes: the same on every run and under every
+ *                       scheduling (the LDS atomics are max and or; every other access is ordered by a barrier, but for the parse's
+ *                       marks, whose final set is the same in every order: svx_deflate_core.hpp).  The kernel needs 153 KB of
+ *                       dynamic LDS; the opt-in is made on the device that is current at the call, once per device
+ *   svx_bgzf_pack       d_file_off [n_blocks + 1] = the exclusive prefix sum of d_member_len, computed on the device, the closing entry
+ *                       = the file bytes; member b copied from its slot to d_out + d_file_off[b].  A member that would end behind
+ *                       out_bytes is not copied: out_bytes >= the inflated bytes + 31 n_blocks always holds them all */
+#define SVX_BGZF_SLOT 65536u
+#define SVX_BGZF_BLOCK_MAX 0xFF00u
+int            svx_bgzf_deflate(const uint8_t* d_in, const uint64_t* d_in_off, uint32_t n_blocks, uint8_t* d_slots, uint32_t* d_member_len,
+                                uint32_t* d_stored, void* stream);
+int            svx_bgzf_pack(const uint8_t* d_slots, const uint32_t* d_member_len, uint32_t n_blocks, uint64_t* d_file_off, uint8_t* d_out,
+                             uint64_t out_bytes, void* stream);
 /* host helpers of the device-side ingestion: parallel positional read into caller memory; the whole BGZF blocks of a
  * buffer (payload offset / size, ISIZE, file offset; -> their number or -1, *used = bytes they cover); QNAME ids by
  * first occurrence (-> number of distinct names, written '\n'-separated to uniq) */

@@ -218,6 +218,39 @@ def _load_unsorted(options):
     return sample
 
 
+def _write_sorted(options):
+    """SVX_DEVICE_SORT=write and a header that does not say ``SO:coordinate``: the coordinate-sorted BAM and its .bai written into the
+    output directory (svision_amd/sort.py) -> the sorted file's path, which stays there.  The sort runs in a process of its own: this
+    one has not touched the device when the helpers of ``-t N`` are forked."""
+    import json
+    import subprocess
+    import sys
+    import time
+    t0 = time.perf_counter()
+    name = os.path.basename(options.bam_path)
+    out = os.path.join(options.out_path, (name[:-4] if name.endswith(".bam") else name) + ".sorted.bam")
+    stats_path = out + ".stats.json"
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, PYTHONPATH=os.pathsep.join([root] + [p for p in os.environ.get("PYTHONPATH", "").split(os.pathsep) if p]))
+    r = subprocess.run([sys.executable, "-m", "svision_amd.sort", options.bam_path, "-o", out, "--stats-json", stats_path,
+                        "--device", "cuda:%d" % int(os.environ.get("LOCAL_RANK", "0"))], capture_output=True, text=True, env=env)
+    try:
+        if r.stderr.strip():                                        # the child's whole stderr (a traceback with its context) for the log
+            logging.debug("svision_amd.sort (exit status %d) wrote:\n%s", r.returncode, r.stderr.rstrip())
+        if r.returncode != 0:
+            logging.error("%s", (r.stderr.strip().splitlines() or ["svision_amd.sort failed"])[-1])
+            raise SystemExit(1)
+        with open(stats_path) as f:
+            stats = json.load(f)
+    finally:
+        if os.path.exists(stats_path):
+            os.unlink(stats_path)
+    logging.info("%s is not coordinate sorted: %d records sorted on the device in %.2f s (%d range(s), %d radix passes)", options.bam_path,
+                 stats["records"], time.perf_counter() - t0, stats["ranges"], stats["passes"])
+    logging.info("sorted file: %s (+ .bai), %d BGZF blocks, %d -> %d bytes", out, stats["blocks"], stats["inflated_bytes"], stats["compressed_bytes"])
+    return out
+
+
 # What a run reads.  ``sample``: the resident Sample (handed in, or sorted on the device), None when the file is streamed chromosome by
 # chromosome; ``index`` / ``build_index``: the streamed file's .bai, or that it is to be built on the device (both unset for a Sample).
 RunInput = collections.namedtuple("RunInput", "sample fasta references lengths index build_index")
@@ -226,7 +259,9 @@ RunInput = collections.namedtuple("RunInput", "sample fasta references lengths i
 def _open_input(options, sample, ws, tick):
     """Input step.  Needs the options, the caller's Sample or None, and the world size; touches no device and no process group unless
     an unsorted file is sorted (one rank, before any fork).  -> RunInput.  Refuses with SystemExit(1): a file that is not coordinate
-    sorted without SVX_DEVICE_SORT=1, and SVX_DEVICE_SORT=1 or SVX_BUILD_INDEX=1 (with no .bai) in a run of several ranks."""
+    sorted without SVX_DEVICE_SORT=1 / =write, and SVX_DEVICE_SORT=1 / =write or SVX_BUILD_INDEX=1 (with no .bai) in a run of several
+    ranks.  SVX_DEVICE_SORT=write: the sorted file is written into the output directory by a child process, ``options.bam_path`` is set to
+    it, and the step answers as for any sorted, indexed file."""
     from . import sample as _sample
     from .io.bam import find_index, read_bam_header
     if sample is None:
@@ -242,6 +277,15 @@ def _open_input(options, sample, ws, tick):
                               "`python -m svision_amd.index %s` and start the %d ranks again", options.bam_path, ws)
                 raise SystemExit(1)
             return RunInput(None, fasta, head.references, head.lengths, index, build_index)
+        if os.environ.get("SVX_DEVICE_SORT") == "write":
+            if ws > 1:
+                # (every rank would write the same file; one sort in front of the launch serves them all)
+                logging.error("SVX_DEVICE_SORT=write sorts an unsorted BAM in a single-rank run only: write the sorted file first with "
+                              "`python -m svision_amd.sort %s -o sorted.bam` and start the %d ranks on it", options.bam_path, ws)
+                raise SystemExit(1)
+            options.bam_path = _write_sorted(options)
+            tick("unsorted BAM: sorted file written on the device")
+            return _open_input(options, None, ws, tick)             # the ordinary file-driven run on the sorted, indexed file
         if os.environ.get("SVX_DEVICE_SORT") != "1":
             logging.error("This is not a coordinate sorted BAM file")
             logging.error("(SVX_DEVICE_SORT=1 sorts its records on the device: one rank, the whole file resident)")

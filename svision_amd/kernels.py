@@ -832,3 +832,44 @@ def record_gather_segments(src, off_in, order, off_out, out):
     _lib.check(lib.svx_record_gather_segments(src.data_ptr(), off_in.data_ptr(), order.data_ptr(), off_out.data_ptr(), out.data_ptr(), n,
                                               src.element_size(), _stream_ptr(src.device)), "svx_record_gather_segments")
     return out
+
+
+# ---- BGZF members from inflated bytes (svx_deflate.hip; the writer: svision_amd/sort.py) ----
+BGZF_SLOT = 65536                    # SVX_BGZF_SLOT: bytes of a member's slot in svx_bgzf_deflate's output
+BGZF_BLOCK_MAX = 0xFF00              # SVX_BGZF_BLOCK_MAX: the largest block the encoder takes (htslib's block size)
+BGZF_MEMBER_EXTRA = 31               # a member is never longer than its block + header 18 + stored 5 + footer 8
+
+
+def bgzf_deflate(d_in, d_in_off):
+    """d_in: uint8 device tensor, d_in_off: int64 [n + 1] device tensor -- block b = d_in[d_in_off[b]:d_in_off[b + 1]], 0 .. 0xFF00
+    bytes, any alignment -> (uint8 [n, 65536] slots, int32 [n] member lengths, int32 [n] 1 where the block is stored).  Fixed
+    Huffman code or stored, whichever is smaller; the bytes are a pure function of the input.  See include/svx.h svx_bgzf_deflate."""
+    lib = _lib.load()
+    _require_cuda(d_in, "d_in")
+    _require_cuda(d_in_off, "d_in_off")
+    if d_in.dtype != torch.uint8 or d_in_off.dtype != torch.int64 or d_in_off.dim() != 1 or d_in_off.shape[0] < 1:
+        raise _lib.SvxError("d_in must be uint8, d_in_off int64 [n + 1]")
+    n, dev = int(d_in_off.shape[0]) - 1, d_in.device
+    slots = torch.empty((n, BGZF_SLOT), dtype=torch.uint8, device=dev)
+    member_len = torch.zeros(n, dtype=torch.int32, device=dev)
+    stored = torch.zeros(n, dtype=torch.int32, device=dev)
+    _lib.check(lib.svx_bgzf_deflate(d_in.data_ptr(), d_in_off.data_ptr(), n, slots.data_ptr(), member_len.data_ptr(), stored.data_ptr(),
+                                    _stream_ptr(dev)), "svx_bgzf_deflate")
+    return slots, member_len, stored
+
+
+def bgzf_pack(slots, member_len, out_bytes):
+    """The members of :func:`bgzf_deflate` end to end -> (uint8 [out_bytes] device tensor whose first file_off[n] bytes are the file
+    bytes, int64 [n + 1] device tensor file_off: the exclusive prefix sum of the lengths, taken on the device).  ``out_bytes``: at
+    least the blocks' bytes + 31 a block.  See include/svx.h svx_bgzf_pack."""
+    lib = _lib.load()
+    _require_cuda(slots, "slots")
+    _require_cuda(member_len, "member_len")
+    n, dev = int(member_len.shape[0]), slots.device
+    if slots.dtype != torch.uint8 or member_len.dtype != torch.int32 or slots.numel() != n * BGZF_SLOT:
+        raise _lib.SvxError("slots must be uint8 [n, 65536], member_len int32 [n]")
+    out = torch.empty(max(int(out_bytes), 1), dtype=torch.uint8, device=dev)
+    file_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    _lib.check(lib.svx_bgzf_pack(slots.data_ptr(), member_len.data_ptr(), n, file_off.data_ptr(), out.data_ptr(), int(out_bytes), _stream_ptr(dev)),
+               "svx_bgzf_pack")
+    return out, file_off
