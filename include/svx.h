@@ -507,6 +507,32 @@ int64_t        svx_bgzf_index(const uint8_t* bytes, uint64_t n, uint64_t base_co
 int64_t        svx_name_ids(const uint8_t* names, const int64_t* name_off, uint64_t n, int32_t* name_id, uint8_t* uniq,
                             uint64_t* uniq_bytes);
 
+/* The staging reader of the device-side ingestion (svx_stage.hip over svx_stage_core.hpp; ABI 420, additive): the file ranges
+ * of a run's groups go through a ring of the caller's pinned slots to the device.  One descriptor and one pool of pread threads
+ * per handle, alive from open to close; a slot is 65,536 bytes of head-room + payload, filled at fixed file offsets (the head of
+ * a block cut by a slot's end is carried to the head-room of the next one), so the reads run ahead of the index and into the
+ * next range as far as slots are free.  Every HIP call is made by the calling thread.
+ *   svx_stage_open    ranges = n_ranges pairs [c0, c1) of file offsets, each c0 at a BGZF block; slot_ptrs = n_slots (>= 2) host
+ *                     addresses of slot_bytes (>= 131,072) each, not touched by anyone else until the close; copy_stream = the
+ *                     hipStream_t the uploads go to.  -> opaque handle or NULL (svx_bam_error tells why)
+ *   svx_stage_group   the next range, completely: per slot wait for its bytes, carry, index, hipMemcpyAsync of the whole blocks
+ *                     to d_comp + (the block's file offset - c0) and the slot's event behind it.  -> the number of whole blocks
+ *                     of the range (>= 1), *used = the bytes they cover, waits [3] = seconds the call waited for bytes / for a
+ *                     slot's earlier copy / took in all, stamps [2 x up to stamps_cap] = per slot the seconds since the open at
+ *                     which its bytes were there and its copy was enqueued (may be NULL) -- or, with the text in svx_bam_error,
+ *                     -1 bad argument, -2 read error or a range past the end of the file, -3 no BGZF block at the start of the
+ *                     range, -4 not BGZF further inside, -5 a HIP call failed or d_comp_bytes is too small, -7 no range left.
+ *                     After an error every further call fails the same way; the handle is still to be closed
+ *   svx_stage_tables  the last group's blocks: payload offset in d_comp, payload bytes, ISIZE, file offset; cap >= their number
+ *   svx_stage_close   from any state: the pool is joined, the descriptor closed, the events destroyed.  The copies that are
+ *                     enqueued are the caller's to wait for (its stream) before it reuses the slots */
+void*          svx_stage_open(const char* path, int threads, const uint64_t* ranges, int n_ranges, const uint64_t* slot_ptrs, int n_slots,
+                              uint64_t slot_bytes, int device, void* copy_stream);
+int64_t        svx_stage_group(void* stage, uint8_t* d_comp, uint64_t d_comp_bytes, uint64_t* used, double* waits, double* stamps,
+                               uint64_t stamps_cap);
+int            svx_stage_tables(void* stage, uint64_t* src_off, uint32_t* src_len, uint32_t* isize, uint64_t* coff, uint64_t cap);
+void           svx_stage_close(void* stage);
+
 /* Streaming ingestion, one reference sequence at a time (replaces the reference's window-by-window
  * AlignmentFile.fetch(chrom, start, end), run_collection.py:23-26, by one pass over the file that hands chromosome k
  * to the caller while chromosome k+1 is being read and inflated on the handle's own threads):

@@ -83,6 +83,10 @@ SYMBOLS = {
     "svx_read_range": (ctypes.c_int, [ctypes.c_char_p, _u64, _u64, _vp, ctypes.c_int]),
     "svx_bgzf_index": (ctypes.c_int64, [_vp, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _vp]),
     "svx_name_ids": (ctypes.c_int64, [_vp, _vp, _u64, _vp, _vp, _vp]),
+    "svx_stage_open": (_vp, [ctypes.c_char_p, ctypes.c_int, _vp, ctypes.c_int, _vp, ctypes.c_int, _u64, ctypes.c_int, _vp]),     # (ABI 420, additive: svx_stage.hip)
+    "svx_stage_group": (ctypes.c_int64, [_vp, _vp, _u64, _vp, _vp, _vp, _u64]),
+    "svx_stage_tables": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _u64]),
+    "svx_stage_close": (None, [_vp]),
     "svx_bam_stream_open": (_vp, [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int]),
     "svx_bam_stream_next": (_vp, [_vp, _vp]),
     "svx_bam_stream_close": (None, [_vp]),

@@ -36,6 +36,7 @@
 #include <vector>
 
 #include "../../include/svx.h"
+#include "svx_stage_core.hpp"
 
 namespace {
 
@@ -884,6 +885,9 @@ int default_threads()
 
 }  // namespace
 
+// (svx_stage.hip: the staging reader reports through svx_bam_error too, on the thread that called it)
+namespace svx_host { void set_bam_error(const std::string& why) { g_bam_error = why; } }
+
 extern "C" {
 
 void* svx_bam_open(const char* path, int threads, int flags) { return bam_open_impl(path, threads, flags, false, 0, 0); }
@@ -1042,31 +1046,15 @@ int svx_read_range(const char* path, uint64_t off, uint64_t n, uint8_t* dst, int
 int64_t svx_bgzf_index(const uint8_t* b, uint64_t n, uint64_t base_coff, uint64_t cap, uint64_t* src_off, uint32_t* src_len,
                        uint32_t* isize, uint64_t* coff, uint64_t* used)
 {
-    uint64_t p = 0, k = 0;
-    while (p + 18 <= n && k < cap) {
-        if (!(b[p] == 0x1f && b[p + 1] == 0x8b && b[p + 2] == 8 && (b[p + 3] & 4))) return -1;
-        const uint32_t xlen = rd16(&b[p + 10]);
-        if (p + 12 + xlen > n) break;
-        uint32_t bsize = 0;
-        bool found = false;
-        for (uint64_t q = p + 12; q + 4 <= p + 12 + xlen;) {
-            const uint32_t slen = rd16(&b[q + 2]);
-            if (b[q] == 'B' && b[q + 1] == 'C') { bsize = rd16(&b[q + 4]); found = true; }
-            q += 4 + slen;
-        }
-        if (!found) return -1;
-        if (p + bsize + 1 > n) break;
-        const uint64_t data = p + 12 + xlen, end = p + bsize + 1;
-        if (end < data + 8) return -1;
-        src_off[k] = data;
-        src_len[k] = (uint32_t)(end - 8 - data);
-        isize[k] = rd32(&b[end - 4]);
-        coff[k] = base_coff + p;
-        ++k;
-        p = end;
-    }
-    *used = p;
-    return (int64_t)k;
+    uint64_t covered = 0;                                      // (the scan is the staging reader's too: svx_stage_core.hpp)
+    const int64_t k = svx_stage::bgzf_scan(b, n, cap, &covered, [&](uint64_t i, uint64_t p, uint64_t data, uint64_t end, uint32_t isz) {
+        src_off[i] = data;
+        src_len[i] = (uint32_t)(end - 8 - data);
+        isize[i] = isz;
+        coff[i] = base_coff + p;
+    });
+    if (k >= 0) *used = covered;
+    return k;
 }
 
 // QNAME ids by first occurrence (what the host decoder computes while it chains the records): names = the records'

@@ -19,8 +19,10 @@ Map of a run (DeviceDecoder.units_pipelined -> _Pipeline; the streams are those 
 
   planning   the caller's thread: plan_units / whole_units -> Units (file ranges), cut_groups -> the groups, one inflate
              launch each.  No device work.
-  reader     thread "svx-read" (_Pipeline.reader, read_group): pread into the staging ring, BGZF block index, record starts
-             from the linear index; the compressed bytes go to the device on the "copy" stream.        -> Queue(maxsize=1)
+  reader     thread "svx-read" (_Pipeline.reader, read_group): one native call per group (svx_stage_group, csrc/svx_stage.hip) --
+             a pool of pread threads, alive from run()'s start to its end, reads ahead into the staging ring, across groups;
+             per slot the BGZF block index and the copy to the device on the "copy" stream --, then the record starts from the
+             linear index.  (SVX_STAGE_READER=py: read, index, enqueue slot by slot in Python.)          -> Queue(maxsize=1)
   driver     thread "svx-inflate-driver" (drive, pump, launch, finish_group): inflate, CRC32, walk-count, then per unit the
              extraction and its read-back, on "ingest0" / "ingest1" in turn -- the tokens kernel of every group on "tokens"
              --; the large buffers are allocated on the thread's default stream.  (Thread "svx-inflate-warm": the first two
@@ -598,6 +600,15 @@ class _StagingRing:
             self.stats["slot_wait_s"] = self.stats.get("slot_wait_s", 0.0) + (time.perf_counter() - t_w)
         return s
 
+    def pointers(self, n):
+        """The native reader's view of the ring: the host addresses of its first ``n`` slots (at most ``n_slots``, at least two),
+        allocated here where they do not exist yet.  The reader keeps an event per slot of its own; the torch events of
+        :meth:`slot` are not used."""
+        n = max(2, min(int(n), self.n_slots))
+        while len(self.slots) < n:
+            self.slots.append([torch.empty(STAGE_BYTES, dtype=torch.uint8, pin_memory=True), None])
+        return [s[0].data_ptr() for s in self.slots[:n]]
+
     def release(self):
         """The process-wide slots are free for the next decoder (only once no thread of this one can touch them)."""
         if self.shared:
@@ -644,7 +655,13 @@ class _Pipeline:
         self.tokens_stream = streams.get("tokens", self.dev) if os.environ.get("SVX_TOKENS_STREAM", "1") != "0" else None
         self.group_streams = [streams.get("ingest%d" % i, self.dev) for i in range(self.depth)]
         self.inflight = collections.deque()                    # driver thread only: the groups launched and not yet finished
+        self.n_read = 0                                        # reader thread only: groups read (read_group takes them in order, as the native reader does)
         self.done, self.error, self.launched = False, None, 0  # driver thread only: the reader has ended / what it ended with / groups launched
+        # the file range of every group, whole BGZF blocks from the first unit's block to the last one's (its last block included)
+        self.ranges = [(min(u.vlo >> 16 for u in g), min(dec.size, max(u.vhi >> 16 for u in g) + 65536 + 64)) for g in self.groups]
+        # SVX_STAGE_READER=py: the per-slot loop in Python (read_slots_py), kept for A/B runs and as the tests' reference
+        self.native = os.environ.get("SVX_STAGE_READER", "native") != "py"
+        self.stage = None                                      # the native reader's handle (svx_stage_open), open inside run() only
         self.ring = _StagingRing(self.stats)                   # (last: from here on run()'s finally gives the shared slots back)
 
     # ---- reader thread ------------------------------------------------------------------------------------------------
@@ -667,18 +684,46 @@ class _Pipeline:
         except BaseException as exc:                             # noqa: BLE001
             hand(exc)
 
-    def read_group(self, units):
-        """Reader thread: the file range of ``units`` -> a :class:`_Group` whose compressed bytes are on their way to the
-        device.  Allocates ``d_comp`` on this thread's default stream; the copies out of the staging slots go to the "copy"
-        stream (``copied``: the event behind the last one).  The host work: pread, BGZF block index, record starts."""
+    def open_stage(self):
+        """The caller's thread, inside :meth:`run`: the native reader over every group's file range and the ring's slots -- its
+        pread pool starts on the first group at once.  (A slot is 64 KB of head-room + payload: svx_stage_core.hpp.)"""
+        payload = STAGE_BYTES - 65536
+        ptrs = self.ring.pointers(sum((c1 - c0 + payload - 1) // payload for c0, c1 in self.ranges))
+        ranges = np.asarray(self.ranges, np.uint64).reshape(-1)
+        slots = np.asarray(ptrs, np.uint64)
+        index = self.dev.index if self.dev.index is not None else torch.cuda.current_device()
+        self.stage = self.lib.svx_stage_open(self.dec.path.encode(), self.dec.threads, ranges.ctypes.data, len(self.ranges), slots.ctypes.data, len(ptrs),
+                                             STAGE_BYTES, index, self.copy_stream.cuda_stream)
+        if not self.stage:
+            raise DeviceIngestError(self.lib.svx_bam_error().decode())
+
+    def read_slots_native(self, d_comp, nbytes, tids_of):
+        """Reader thread: ONE native call stages the group -- per slot it waits for the pool's bytes, indexes the BGZF blocks and
+        enqueues the copy on the "copy" stream (svx_stage_group; the interpreter lock is released for the whole call) -- then
+        the tables are copied out.  -> (src_off, src_len, isize, coff, copied)."""
+        lib = self.lib
+        cap = nbytes // (STAGE_BYTES - 65536) + 1
+        used, waits, stamps = np.zeros(1, np.uint64), np.zeros(3, np.float64), np.zeros(2 * cap, np.float64)
+        k = int(lib.svx_stage_group(self.stage, d_comp.data_ptr(), d_comp.numel(), used.ctypes.data, waits.ctypes.data, stamps.ctypes.data, cap))
+        if k < 0:
+            raise DeviceIngestError(lib.svx_bam_error().decode(), tids_of)
+        with torch.cuda.stream(self.copy_stream):
+            copied = torch.cuda.Event()
+            copied.record()
+        src_off, coff = np.empty(k, np.uint64), np.empty(k, np.uint64)
+        src_len, isize = np.empty(k, np.uint32), np.empty(k, np.uint32)
+        _lib.check(lib.svx_stage_tables(self.stage, src_off.ctypes.data, src_len.ctypes.data, isize.ctypes.data, coff.ctypes.data, k), "svx_stage_tables")
+        self.stats["pread_s"] = self.stats.get("pread_s", 0.0) + float(waits[0])
+        self.stats["slot_wait_s"] = self.stats.get("slot_wait_s", 0.0) + float(waits[1])
+        n = int(np.count_nonzero(stamps[1::2]))
+        if n:                                                   # (seconds since the reader was opened)
+            self.mark("staged: %d slots, bytes of the first at %.4f, of the last at %.4f, last copy enqueued at %.4f" % (n, stamps[0], stamps[2 * n - 2], stamps[2 * n - 1]))
+        return src_off, src_len, isize, coff, copied
+
+    def read_slots_py(self, d_comp, c0, nbytes, tids_of):
+        """Reader thread, SVX_STAGE_READER=py: slot by slot -- svx_read_range (threads started and joined per slot), svx_bgzf_index,
+        the copy and the slot's torch event on the "copy" stream, then the next read.  -> (src_off, src_len, isize, coff, copied)."""
         dec, lib = self.dec, self.lib
-        tids_of = sorted({u.tid for u in units})
-        c0 = min(u.vlo >> 16 for u in units)
-        c1 = min(dec.size, max(u.vhi >> 16 for u in units) + 65536 + 64)
-        nbytes = c1 - c0
-        t0 = time.perf_counter()
-        self.mark("read %s: start" % units[:2])
-        d_comp = torch.empty((nbytes + 31) // 16 * 16, dtype=torch.uint8, device=self.dev)
         off, tables, copied = 0, [], None
         while off < nbytes:
             want = min(STAGE_BYTES, nbytes - off)
@@ -700,8 +745,31 @@ class _Pipeline:
             slot[1] = copied
             tables.append((blocks.src_off + np.uint64(off), blocks.src_len, blocks.isize, blocks.coff))
             off += blocks.used                                 # (a block cut by the end of the slot is read again, at the head of the next one)
-        d_comp.record_stream(self.copy_stream)
         src_off, src_len, isize, coff = (np.concatenate([t[i] for t in tables]) for i in range(4))
+        return src_off, src_len, isize, coff, copied
+
+    def read_group(self, units):
+        """Reader thread: the file range of ``units`` -> a :class:`_Group` whose compressed bytes are on their way to the
+        device.  Allocates ``d_comp`` on this thread's default stream; the copies out of the staging slots go to the "copy"
+        stream (``copied``: the event behind the last one).  The host work: waiting for the staged slots (read_slots_native; or
+        pread and BGZF block index here, read_slots_py), record starts, the pinned table.
+
+        ``stats``: ``read_s`` = the time this thread spends in here; ``pread_s`` = of that, the time it waited for a slot's
+        bytes (the pool reads ahead, so what is left is what the reads could not hide; py: the svx_read_range calls);
+        ``slot_wait_s`` = the time it waited for a slot's earlier copy to leave it."""
+        dec = self.dec
+        tids_of = sorted({u.tid for u in units})
+        c0, c1 = self.ranges[self.n_read]
+        self.n_read += 1
+        nbytes = c1 - c0
+        t0 = time.perf_counter()
+        self.mark("read %s: start" % units[:2])
+        d_comp = torch.empty((nbytes + 31) // 16 * 16, dtype=torch.uint8, device=self.dev)
+        if self.native:
+            src_off, src_len, isize, coff, copied = self.read_slots_native(d_comp, nbytes, tids_of)
+        else:
+            src_off, src_len, isize, coff, copied = self.read_slots_py(d_comp, c0, nbytes, tids_of)
+        d_comp.record_stream(self.copy_stream)
         nb = int(src_off.size)
         dst = np.zeros(nb + 1, np.uint64)
         dst[1:] = np.cumsum(isize.astype(np.uint64))
@@ -992,12 +1060,17 @@ class _Pipeline:
     def run(self):
         """The caller's thread, generator: starts the three threads and yields what the driver puts out; an exception of the
         reader or the driver is raised here.  No device work; on exit (exhausted, failed or abandoned) the threads are told
-        to stop, the reader is joined and the "copy" stream synchronised before the staging slots go back."""
+        to stop, the reader is joined and the "copy" stream synchronised before the native reader is closed (its pread pool exists
+        between open_stage() here and that close only) and the staging slots go back."""
         reader = threading.Thread(target=self.reader, name="svx-read", daemon=True)
-        reader.start()
-        threading.Thread(target=self.warm, name="svx-inflate-warm", daemon=True).start()
-        threading.Thread(target=self.drive, name="svx-inflate-driver", daemon=True).start()
+        started = False
         try:
+            if self.native and self.groups:
+                self.open_stage()
+            reader.start()
+            started = True
+            threading.Thread(target=self.warm, name="svx-inflate-warm", daemon=True).start()
+            threading.Thread(target=self.drive, name="svx-inflate-driver", daemon=True).start()
             while True:
                 part = self.out_q.get()
                 if part is None:
@@ -1008,8 +1081,12 @@ class _Pipeline:
         finally:
             self.stop.set()
             try:
-                reader.join(timeout=10)                        # (an abandoned run: the reader may be in the middle of a group)
+                if started:
+                    reader.join(timeout=10)                    # (an abandoned run: the reader may be in the middle of a group)
                 self.copy_stream.synchronize()                 # the slots go back to the process-wide ring: no copy may still read them
             finally:
                 if not reader.is_alive():
+                    if self.stage:                             # the pool is joined in here: no native thread outlives the run
+                        self.lib.svx_stage_close(self.stage)
+                        self.stage = None
                     self.ring.release()

@@ -19,7 +19,7 @@ else:
         if cluster[0][0] - r[1] > 100e6:
             break
         cluster.insert(0, r)
-lz = [r for r in rows if "bgzf_lz_kernel" in r[2] and r[0] >= cluster[0][0]]
+lz = [r for r in rows if "bgzf_lz_" in r[2] and r[0] >= cluster[0][0]]      # (bgzf_lz_kernel, bgzf_lz_wave_kernel, bgzf_lz_table_kernel)
 t_start = cluster[0][0] - 20e6                               # read + index of the first group in front of its launch
 cnn = ("conv_wave", "fc_splitk", "fc_reduce", "encode_conv1", "bias_relu_pool", "active_", "fc8_softmax")
 after = [r for r in rows if r[0] >= t_start]
