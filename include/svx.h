@@ -491,11 +491,30 @@ int            svx_record_gather_segments(const void* d_src, const int64_t* d_of
  *                       dynamic LDS; the opt-in is made on the device that is current at the call, once per device
  *   svx_bgzf_pack       d_file_off [n_blocks + 1] = the exclusive prefix sum of d_member_len, computed on the device, the closing entry
  *                       = the file bytes; member b copied from its slot to d_out + d_file_off[b].  A member that would end behind
- *                       out_bytes is not copied: out_bytes >= the inflated bytes + 31 n_blocks always holds them all */
+ *                       out_bytes is not copied: out_bytes >= the inflated bytes + 31 n_blocks always holds them all
+ *   svx_bgzf_deflate_dyn  (additive) svx_bgzf_deflate with a third form of the DEFLATE block: the SAME parse, its tokens kept in d_ws
+ *                       and counted in LDS, then Huffman codes built in the workgroup from those counts -- literal/length and
+ *                       distance codes of at most 15 bits, their lengths run-length coded with 16 / 17 / 18 the way zlib does it, that
+ *                       sequence's code of at most 7 bits, HLIT / HDIST / HCLEN trimmed; every code complete (Kraft sum 1, at least two
+ *                       symbols: an unused distance alphabet gets two codes of 1 bit) --, the sizes of the three forms counted before a
+ *                       bit is written, and the smallest written: the bytes stored at a tie, then the fixed code, then DYNAMIC codes
+ *                       (BTYPE 10).  d_btype [b] = 0, 1 or 2, the block's BTYPE.  Where it is 0 or 1 the member is svx_bgzf_deflate's,
+ *                       byte for byte; no member is longer than that one.  A block of more than 0xFF00 bytes: length 0, nothing
+ *                       written.  Ties between symbols of one count are broken by symbol index and the limit's repair is a fixed rule,
+ *                       the LDS atomics are max, or and integer add: the member's bytes are a pure function of the block's bytes.
+ *                       d_ws: svx_bgzf_deflate_dyn_ws_bytes(n_blocks) bytes, 8-byte aligned (SVX_EINVAL otherwise) -- 73,440 a block:
+ *                       one byte a position, where a match keeps its 23 bits, and one bit a position for the tokens' starts --;
+ *                       ws_bytes below that: SVX_ECAPACITY, nothing launched, nothing written.  A workspace with 32 bytes a block to
+ *                       spare also receives, behind those bytes, four uint64 a block: the 100 MHz clock at the kernel's start, after
+ *                       the parse, after the code construction and at its end (tools/sort_write_time.py).  153 KB of dynamic LDS +
+ *                       1,280 bytes for the two histograms; the opt-in as above */
 #define SVX_BGZF_SLOT 65536u
 #define SVX_BGZF_BLOCK_MAX 0xFF00u
 int            svx_bgzf_deflate(const uint8_t* d_in, const uint64_t* d_in_off, uint32_t n_blocks, uint8_t* d_slots, uint32_t* d_member_len,
                                 uint32_t* d_stored, void* stream);
+size_t         svx_bgzf_deflate_dyn_ws_bytes(uint32_t n_blocks);
+int            svx_bgzf_deflate_dyn(const uint8_t* d_in, const uint64_t* d_in_off, uint32_t n_blocks, uint8_t* d_slots, uint32_t* d_member_len,
+                                    uint32_t* d_btype, void* d_ws, uint64_t ws_bytes, void* stream);
 int            svx_bgzf_pack(const uint8_t* d_slots, const uint32_t* d_member_len, uint32_t n_blocks, uint64_t* d_file_off, uint8_t* d_out,
                              uint64_t out_bytes, void* stream);
 /* host helpers of the device-side ingestion: parallel positional read into caller memory; the whole BGZF blocks of a

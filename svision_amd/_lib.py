@@ -79,6 +79,8 @@ SYMBOLS = {
     "svx_record_gather_offsets": (ctypes.c_int, [_vp, _vp, _u32, _vp, _vp, _u64, _vp]),
     "svx_record_gather_segments": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp]),
     "svx_bgzf_deflate": (ctypes.c_int, [_vp, _vp, _u32, _vp, _vp, _vp, _vp]),     # (ABI 420, additive: svx_deflate.hip)
+    "svx_bgzf_deflate_dyn_ws_bytes": (_sz, [_u32]),                      # (ABI 420, additive: dynamic Huffman tables)
+    "svx_bgzf_deflate_dyn": (ctypes.c_int, [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _u64, _vp]),
     "svx_bgzf_pack": (ctypes.c_int, [_vp, _vp, _u32, _vp, _vp, _u64, _vp]),
     "svx_read_range": (ctypes.c_int, [ctypes.c_char_p, _u64, _u64, _vp, ctypes.c_int]),
     "svx_bgzf_index": (ctypes.c_int64, [_vp, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _vp]),

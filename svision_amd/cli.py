@@ -221,7 +221,8 @@ def _load_unsorted(options):
 def _write_sorted(options):
     """SVX_DEVICE_SORT=write and a header that does not say ``SO:coordinate``: the coordinate-sorted BAM and its .bai written into the
     output directory (svision_amd/sort.py) -> the sorted file's path, which stays there.  The sort runs in a process of its own: this
-    one has not touched the device when the helpers of ``-t N`` are forked."""
+    one has not touched the device when the helpers of ``-t N`` are forked.  It inherits the environment: ``SVX_SORT_TABLES=dynamic``
+    there is ``--tables dynamic`` (Huffman codes built per block; default: the fixed code)."""
     import json
     import subprocess
     import sys

@@ -858,6 +858,32 @@ def bgzf_deflate(d_in, d_in_off):
     return slots, member_len, stored
 
 
+def bgzf_deflate_dynamic(d_in, d_in_off, phase_ticks=False):
+    """:func:`bgzf_deflate` with dynamic Huffman tables as a third form -> (uint8 [n, 65536] slots, int32 [n] member lengths, int32 [n]
+    block types: 0 stored, 1 fixed code, 2 dynamic codes -- the smallest of the three, stored at a tie, then fixed).  The same parse:
+    where the type is 0 or 1 the member is :func:`bgzf_deflate`'s, byte for byte.  :func:`bgzf_pack` takes the output as it is.
+    ``phase_ticks``: also return int64 [n, 4], the device's 100 MHz clock at each block's start, after its parse, after its code
+    construction and at its end.  See include/svx.h svx_bgzf_deflate_dyn."""
+    lib = _lib.load()
+    _require_cuda(d_in, "d_in")
+    _require_cuda(d_in_off, "d_in_off")
+    if d_in.dtype != torch.uint8 or d_in_off.dtype != torch.int64 or d_in_off.dim() != 1 or d_in_off.shape[0] < 1:
+        raise _lib.SvxError("d_in must be uint8, d_in_off int64 [n + 1]")
+    n, dev = int(d_in_off.shape[0]) - 1, d_in.device
+    slots = torch.empty((n, BGZF_SLOT), dtype=torch.uint8, device=dev)
+    member_len = torch.zeros(n, dtype=torch.int32, device=dev)
+    btype = torch.zeros(n, dtype=torch.int32, device=dev)
+    need = int(lib.svx_bgzf_deflate_dyn_ws_bytes(n))
+    ws = torch.empty(max(need + (32 * n if phase_ticks else 0), 8), dtype=torch.uint8, device=dev)
+    if phase_ticks:
+        ws[need:] = 0
+    _lib.check(lib.svx_bgzf_deflate_dyn(d_in.data_ptr(), d_in_off.data_ptr(), n, slots.data_ptr(), member_len.data_ptr(), btype.data_ptr(),
+                                        ws.data_ptr(), int(ws.numel()) if n else 0, _stream_ptr(dev)), "svx_bgzf_deflate_dyn")
+    if phase_ticks:
+        return slots, member_len, btype, ws[need:need + 32 * n].view(torch.int64).view(n, 4).clone()
+    return slots, member_len, btype
+
+
 def bgzf_pack(slots, member_len, out_bytes):
     """The members of :func:`bgzf_deflate` end to end -> (uint8 [out_bytes] device tensor whose first file_off[n] bytes are the file
     bytes, int64 [n + 1] device tensor file_off: the exclusive prefix sum of the lengths, taken on the device).  ``out_bytes``: at

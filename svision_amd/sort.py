@@ -14,7 +14,8 @@ and a genome browser read --, with every record byte kept: qualities and aux tag
   output    svx_record_gather_offsets gives every sorted record its offset in the output stream.  That stream is cut every 0xFF00
             bytes whatever the records (they straddle blocks the way htslib's do) and taken in chunks of ``chunk_bytes``: the records
             that touch the chunk gathered (svx_record_gather_segments), its blocks deflated (svx_bgzf_deflate: fixed Huffman code or
-            stored), packed (svx_bgzf_pack), downloaded through pinned memory and appended to a temporary file
+            stored; ``tables="dynamic"``: svx_bgzf_deflate_dyn, the same parse under Huffman codes built per block wherever that is
+            smaller), packed (svx_bgzf_pack), downloaded through pinned memory and appended to a temporary file
   header    the input's header with its @HD line set to SO:coordinate (VN kept, GO and SS dropped; no @HD: one is prepended; nothing
             else is added, no @PG line: the output is reproducible byte for byte), in blocks of its own through the same encoder; the
             first record opens a new block.  The encoder's member of an empty block is the 28-byte end-of-file marker, which closes
@@ -24,9 +25,11 @@ and a genome browser read --, with every record byte kept: qualities and aux tag
 
 Device memory: the records' inflated bytes once (the stream is allocated before the pass, sized by the sum of the BGZF members' ISIZE
 fields, and every range's slice is copied straight into it), one range of the pass, 8 bytes of key + 20 of sort workspace a
-record, and one chunk -- ``chunk_bytes`` three times over (gathered bytes, 65,536-byte slots, packed members).
-``DEFAULT_CHUNK_BYTES`` is 1,024 blocks, 64 MB.  Compression is the fixed Huffman code over a greedy parse: larger files than
-zlib's dynamic tables write (profiles/sort_write.txt).
+record, and one chunk -- ``chunk_bytes`` three times over (gathered bytes, 65,536-byte slots, packed members); with
+``tables="dynamic"`` the encoder's token workspace besides, 73,440 bytes a block (svx_bgzf_deflate_dyn_ws_bytes), 1.125 times
+``chunk_bytes``.  ``DEFAULT_CHUNK_BYTES`` is 1,024 blocks, 64 MB.  Compression by default is the fixed Huffman code over a greedy
+parse: larger files than zlib's dynamic tables write.  ``tables="dynamic"`` (``--tables dynamic``, ``SVX_SORT_TABLES=dynamic``)
+writes the same inflated bytes in a smaller file, at or below zlib level 1's size on the measured data (profiles/sort_write.txt).
 
 A corrupt block, a CRC mismatch, a malformed or cut chain, a device allocation or a write that fails raises SortWriteError (a
 ValueError); no file and no temporary is left behind.
@@ -43,6 +46,7 @@ from . import _lib
 
 BLOCK = 0xFF00                                                  # htslib's block size: inflated bytes a BGZF block of the output
 DEFAULT_CHUNK_BYTES = 1024 * BLOCK
+TABLES = ("fixed", "dynamic")                                   # the encoder: svx_bgzf_deflate / svx_bgzf_deflate_dyn
 STAGES = ("read", "upload", "inflate", "crc", "find_starts", "walk", "scan", "read_back", "keep", "join", "sort", "gather", "deflate", "pack",
           "download", "write", "index")
 
@@ -122,13 +126,26 @@ def sorted_header_bytes(head):
 
 
 # ---- the device steps ----
-def _deflate_blocks(torch, kernels, dev, d_bytes, first, n_bytes):
-    """The bytes d_bytes[first : first + n_bytes] (n_bytes > 0) cut every 0xFF00 and deflated -> (slots, member lengths, stored flags:
-    device tensors, the number of blocks)."""
+def _encoder(kernels, tables):
+    """-> deflate(d_in, d_in_off) -> (slots, member lengths, 1 where stored, 1 where dynamic: device tensors) of the chosen encoder."""
+    if tables == "dynamic":
+        def deflate(d_in, d_in_off):
+            slots, member_len, btype = kernels.bgzf_deflate_dynamic(d_in, d_in_off)
+            return slots, member_len, btype == 0, btype == 2
+    else:
+        def deflate(d_in, d_in_off):
+            slots, member_len, stored = kernels.bgzf_deflate(d_in, d_in_off)
+            return slots, member_len, stored, stored[:0]
+    return deflate
+
+
+def _deflate_blocks(torch, deflate, dev, d_bytes, first, n_bytes):
+    """The bytes d_bytes[first : first + n_bytes] (n_bytes > 0) cut every 0xFF00 and deflated -> (slots, member lengths, stored flags,
+    dynamic flags: device tensors, the number of blocks)."""
     n = (n_bytes + BLOCK - 1) // BLOCK
     off = np.minimum(np.arange(n + 1, dtype=np.int64) * BLOCK, n_bytes) + first
-    slots, member_len, stored = kernels.bgzf_deflate(d_bytes, torch.from_numpy(off).to(dev))
-    return slots, member_len, stored, n
+    slots, member_len, stored, dynamic = deflate(d_bytes, torch.from_numpy(off).to(dev))
+    return slots, member_len, stored, dynamic, n
 
 
 def _download(torch, d, n_bytes):
@@ -138,19 +155,23 @@ def _download(torch, d, n_bytes):
     return h[:n_bytes].numpy()
 
 
-def sort_bam(bam_path, out_path, device="cuda", range_bytes=None, chunk_bytes=None, stats=None):
+def sort_bam(bam_path, out_path, device="cuda", range_bytes=None, chunk_bytes=None, stats=None, tables="fixed"):
     """Write the records of ``bam_path`` in coordinate order to ``out_path`` and its index to ``out_path + ".bai"`` (see the head of the
     module); returns ``out_path``.  ``range_bytes``: compressed bytes a range of the pass (default: the device decoder's group size),
     ``chunk_bytes``: inflated bytes a chunk of the output (default DEFAULT_CHUNK_BYTES; whole blocks, at least one) -- tests pass small
-    values.  ``stats``: a dict that receives ranges, records, blocks, stored_blocks, compressed_bytes, inflated_bytes, chunks and the
-    seconds per stage."""
+    values.  ``tables``: "fixed" -- every block in the fixed Huffman code or stored -- or "dynamic": Huffman codes built per block where
+    they are smaller; the inflated bytes and the index's records are the same.  ``stats``: a dict that receives ranges, records,
+    blocks, stored_blocks, dynamic_blocks, compressed_bytes, inflated_bytes, chunks and the seconds per stage."""
     import torch
     from . import index, ingest_sort, kernels
     from .io import bai
     from .io.bam import read_bam_header
     if not torch.cuda.is_available():
         raise _lib.SvxError("sort_bam needs the GPU (svx_record_sort, svx_bgzf_deflate); there is no CPU fallback")
+    if tables not in TABLES:
+        raise ValueError("tables: %r is none of %s" % (tables, ", ".join(TABLES)))
     lib = _lib.load()
+    deflate = _encoder(kernels, tables)
     dev = torch.device(device)
     if dev.index is None:
         dev = torch.device("cuda", torch.cuda.current_device())
@@ -222,14 +243,14 @@ def sort_bam(bam_path, out_path, device="cuda", range_bytes=None, chunk_bytes=No
             clock.lap("sort")
             # ---- output
             fd, tmp_bam = tempfile.mkstemp(prefix=os.path.basename(out_path) + ".", suffix=".tmp", dir=out_dir)
-            member_lens, block_bytes, n_stored, chunks = [], [], 0, 0
+            member_lens, block_bytes, n_stored, n_dynamic, chunks = [], [], 0, 0, 0
             with os.fdopen(fd, "wb") as f:
                 # the header's blocks and, behind them, an empty block: the end-of-file marker, kept for the end
                 d_head = torch.from_numpy(np.frombuffer(header, np.uint8).copy()).to(dev)
                 n_head = (len(header) + BLOCK - 1) // BLOCK
                 h_off = np.minimum(np.arange(n_head + 2, dtype=np.int64) * BLOCK, len(header))
                 h_off[n_head + 1] = len(header)
-                slots, d_len, d_stored = kernels.bgzf_deflate(d_head, torch.from_numpy(h_off).to(dev))
+                slots, d_len, d_stored, d_dynamic = deflate(d_head, torch.from_numpy(h_off).to(dev))
                 clock.lap("deflate")
                 d_packed, d_file_off = kernels.bgzf_pack(slots, d_len, len(header) + kernels.BGZF_MEMBER_EXTRA * (n_head + 1))
                 clock.lap("pack")
@@ -237,6 +258,7 @@ def sort_bam(bam_path, out_path, device="cuda", range_bytes=None, chunk_bytes=No
                 packed = _download(torch, d_packed, int(m.sum()))
                 eof = packed[int(m[:n_head].sum()):].tobytes()
                 n_stored += int(d_stored[:n_head].sum())
+                n_dynamic += int(d_dynamic[:n_head].sum())
                 clock.lap("download")
                 f.write(packed[:int(m[:n_head].sum())].tobytes())
                 member_lens.append(m[:n_head])
@@ -258,7 +280,7 @@ def sort_bam(bam_path, out_path, device="cuda", range_bytes=None, chunk_bytes=No
                     _lib.check(lib.svx_record_gather_segments(d_stream.data_ptr(), d_off_in.data_ptr(), d_rows.data_ptr(), d_rebased.data_ptr(),
                                                               d_chunk.data_ptr(), r_hi - r_lo, 1, st), "svx_record_gather_segments")
                     clock.lap("gather")
-                    slots, d_len, d_stored, nb = _deflate_blocks(torch, kernels, dev, d_chunk, lo - base, hi - lo)
+                    slots, d_len, d_stored, d_dynamic, nb = _deflate_blocks(torch, deflate, dev, d_chunk, lo - base, hi - lo)
                     clock.lap("deflate")
                     d_packed, d_file_off = kernels.bgzf_pack(slots, d_len, hi - lo + kernels.BGZF_MEMBER_EXTRA * nb)
                     clock.lap("pack")
@@ -266,6 +288,7 @@ def sort_bam(bam_path, out_path, device="cuda", range_bytes=None, chunk_bytes=No
                     if (m < 26).any():
                         raise SortWriteError("%s: svx_bgzf_deflate refused a block" % bam_path)
                     n_stored += int(d_stored.sum())
+                    n_dynamic += int(d_dynamic.sum())
                     packed = _download(torch, d_packed, int(m.sum()))
                     clock.lap("download")
                     f.write(packed.tobytes())
@@ -316,7 +339,7 @@ def sort_bam(bam_path, out_path, device="cuda", range_bytes=None, chunk_bytes=No
             if t is not None and os.path.exists(t):
                 os.unlink(t)
     if stats is not None:
-        stats.update(ranges=ranges, records=n, blocks=int(member_lens.size), stored_blocks=n_stored, chunks=chunks,
+        stats.update(ranges=ranges, records=n, blocks=int(member_lens.size), stored_blocks=n_stored, dynamic_blocks=n_dynamic, chunks=chunks,
                      compressed_bytes=int(member_lens.sum()), inflated_bytes=int(dst[-1]), pos_bits=pos_bits,
                      passes=len(ingest_sort.digit_plan(n_ref, pos_bits)), seconds={k: round(v, 6) for k, v in clock.times.items()})
     return out_path
@@ -330,20 +353,25 @@ def main(argv=None):
     ap.add_argument("-o", "--output", required=True, help="the sorted BAM to write (its index: OUTPUT + .bai)")
     ap.add_argument("--device", default="cuda")
     ap.add_argument("--chunk-bytes", type=int, default=None, help="inflated bytes a chunk of the output (default %d)" % DEFAULT_CHUNK_BYTES)
+    ap.add_argument("--tables", choices=TABLES, default=os.environ.get("SVX_SORT_TABLES") or "fixed",
+                    help="the encoder's Huffman codes: fixed, or built per block where that is smaller (default: $SVX_SORT_TABLES, or fixed)")
     ap.add_argument("--stats-json", default=None, help="also write the statistics to this file")
     args = ap.parse_args(argv)
+    if args.tables not in TABLES:
+        ap.error("SVX_SORT_TABLES=%s: fixed or dynamic" % args.tables)
     stats = {}
     try:
-        path = sort_bam(args.bam, args.output, device=args.device, chunk_bytes=args.chunk_bytes, stats=stats)
+        path = sort_bam(args.bam, args.output, device=args.device, chunk_bytes=args.chunk_bytes, stats=stats, tables=args.tables)
     except (SortWriteError, _lib.SvxError, OSError) as exc:
         print("svision_amd.sort: %s" % exc, file=sys.stderr)
         return 1
     if args.stats_json:
         with open(args.stats_json, "w") as f:
             json.dump(stats, f)
-    print("%s: %d records in %d BGZF blocks (%d stored), %d -> %d bytes, %d range(s), %d chunk(s), %.2f s"
-          % (path, stats["records"], stats["blocks"], stats["stored_blocks"], stats["inflated_bytes"], stats["compressed_bytes"], stats["ranges"],
-             stats["chunks"], sum(stats["seconds"].values())))
+    print("%s: %d records in %d BGZF blocks (%s), %d -> %d bytes, %d range(s), %d chunk(s), %.2f s"
+          % (path, stats["records"], stats["blocks"],
+             "%d stored" % stats["stored_blocks"] + (", %d dynamic" % stats["dynamic_blocks"] if args.tables == "dynamic" else ""),
+             stats["inflated_bytes"], stats["compressed_bytes"], stats["ranges"], stats["chunks"], sum(stats["seconds"].values())))
     return 0
 
 
