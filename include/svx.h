@@ -463,6 +463,20 @@ int            svx_bam_walk_offsets(const uint8_t* d_raw, const uint64_t* d_star
  *                       d_src is read in aligned dwords: 4-byte aligned, readable up to the next multiple of 4 behind its last
  *                       byte; d_dst aligned to elem_bytes.  Exactly the total's bytes of d_dst are written: the 4 readable
  *                       words svx_cigar_scan wants behind a gathered CIGAR array are the caller's to allocate.
+ *   svx_record_invert   d_rank [n]: d_rank[d_order[r]] = r, the sorted rank of every input record (a thread per element)
+ *   svx_record_scatter_segments  the gather turned round, for an output stream that is filled in pieces (svision_amd/sort.py: a
+ *                       file whose records do not fit the device).  n INPUT records lie in d_src at the byte offsets
+ *                       d_src_off [n + 1]; d_rank [n] are their ranks in the whole output, d_off_out that output's offsets
+ *                       (svx_record_gather_offsets: indexed by RANK, entries up to rank_hi are read).  A wave per input record:
+ *                       where rank_lo <= d_rank[i] < rank_hi the bytes d_src[d_src_off[i] .. d_src_off[i + 1]) go to
+ *                       d_dst + d_off_out[rank] - out_base; the waves of all other records return at once.  The alignment
+ *                       rule is the gather's, the destination decides.  d_src is read only in the aligned dwords that hold a
+ *                       segment's bytes: 4-byte aligned, readable up to the next multiple of 4 behind its last byte (the
+ *                       d_raw of the walk has 16).  d_dst: any alignment; only the bytes of the window's records are written.
+ *                       A record whose length d_src_off[i + 1] - d_src_off[i] is not d_off_out[rank + 1] - d_off_out[rank]
+ *                       is NOT copied and d_status[0] is set to 1 (a plain store of the one value from any number of waves;
+ *                       the caller zeroes it); the other records are copied.  Segments of no byte and of more than 65,535
+ *                       bytes are fine; n = 0 and an empty window launch nothing
  * No atomics in any of them: the output is a pure function of the input.  n = 0 is fine everywhere (d_off_out[0] = 0). */
 #define SVX_RECORD_SORT_TILE 2048u
 size_t         svx_record_sort_ws_bytes(uint32_t n);
@@ -474,6 +488,10 @@ int            svx_record_gather_offsets(const int64_t* d_off_in, const uint32_t
                                          uint64_t ws_bytes, void* stream);
 int            svx_record_gather_segments(const void* d_src, const int64_t* d_off_in, const uint32_t* d_order, const int64_t* d_off_out,
                                           void* d_dst, uint32_t n, uint32_t elem_bytes, void* stream);
+int            svx_record_invert(const uint32_t* d_order, uint32_t n, uint32_t* d_rank, void* stream);
+int            svx_record_scatter_segments(const void* d_src, const int64_t* d_src_off, const uint32_t* d_rank, uint32_t rank_lo,
+                                           uint32_t rank_hi, const int64_t* d_off_out, int64_t out_base, void* d_dst, uint32_t n,
+                                           int32_t* d_status, void* stream);
 /* BGZF members FROM inflated bytes (svx_deflate.hip; ABI 420, additive): the encoder of svision_amd/sort.py, which writes the
  * device-sorted BAM.
  *   svx_bgzf_deflate    block b = the bytes d_in[d_in_off[b] .. d_in_off[b + 1]) -- any offsets, no alignment, 0 .. 0xFF00 bytes a block --

@@ -222,7 +222,9 @@ def _write_sorted(options):
     """SVX_DEVICE_SORT=write and a header that does not say ``SO:coordinate``: the coordinate-sorted BAM and its .bai written into the
     output directory (svision_amd/sort.py) -> the sorted file's path, which stays there.  The sort runs in a process of its own: this
     one has not touched the device when the helpers of ``-t N`` are forked.  It inherits the environment: ``SVX_SORT_TABLES=dynamic``
-    there is ``--tables dynamic`` (Huffman codes built per block; default: the fixed code)."""
+    there is ``--tables dynamic`` (Huffman codes built per block; default: the fixed code), ``SVX_SORT_MEMORY=BYTES`` (K, M or G) is
+    ``--memory``: the device memory for the records' inflated bytes, beyond which the file is written in spans, a pass over the input
+    for each (default: half of the free device memory)."""
     import json
     import subprocess
     import sys
@@ -248,7 +250,8 @@ def _write_sorted(options):
             os.unlink(stats_path)
     logging.info("%s is not coordinate sorted: %d records sorted on the device in %.2f s (%d range(s), %d radix passes)", options.bam_path,
                  stats["records"], time.perf_counter() - t0, stats["ranges"], stats["passes"])
-    logging.info("sorted file: %s (+ .bai), %d BGZF blocks, %d -> %d bytes", out, stats["blocks"], stats["inflated_bytes"], stats["compressed_bytes"])
+    logging.info("sorted file: %s (+ .bai), %d BGZF blocks, %d -> %d bytes, written in %d span(s) under a budget of %d bytes for the records "
+                 "(SVX_SORT_MEMORY)", out, stats["blocks"], stats["inflated_bytes"], stats["compressed_bytes"], stats["spans"], stats["memory_bytes"])
     return out
 
 

@@ -21,11 +21,17 @@
 //   svx_record_gather_offsets   off_out[r] = sum of the lengths of the segments order[0 .. r), the same three-launch scan (int64)
 //   svx_record_gather_segments  a WAVE per record copies segment order[r] to off_out[r]: aligned dword stores, the source read in
 //                               aligned dwords and shifted into place, at most 3 single bytes at either end
+//   svx_record_invert           rank[order[r]] = r: the sorted rank of every input record
+//   svx_record_scatter_segments the gather turned round, for a record stream that is taken in pieces (svision_amd/sort.py, a file
+//                               larger than the device): a WAVE per INPUT record; where the record's rank lies in the window
+//                               [rank_lo, rank_hi) its bytes go to off_out[rank] - out_base, by the copy routine of
+//                               svx_recsort_core.hpp (the gather's alignment rule); the other waves leave at once
 // No atomics, no cross-workgroup dependency inside a launch: the output is a pure function of the input, identical in every run.
 // A counter in LDS is written by ONE lane a round (the leader of its digit, in the wave's own row) with a barrier behind it.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/svx.h"
+#include "svx_recsort_core.hpp"
 
 namespace {
 
@@ -303,6 +309,25 @@ void gather_segments_kernel(const uint8_t* __restrict__ src, const int64_t* __re
     if (done + lane < len) to[done + lane] = from[done + lane];
 }
 
+__global__ __launch_bounds__(256)
+void invert_kernel(const uint32_t* __restrict__ order, uint32_t* __restrict__ rank, uint32_t n)
+{
+    const uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (r < n) rank[order[r]] = (uint32_t)r;
+}
+
+// A wave per input record; the destinations of different records are disjoint, a length that does not fit is reported and
+// not copied (svx_recsort_core.hpp).
+__global__ __launch_bounds__(WAVE * SEG_WAVES)
+void scatter_segments_kernel(const uint8_t* __restrict__ src, const int64_t* __restrict__ src_off, const uint32_t* __restrict__ rank,
+                             uint32_t rank_lo, uint32_t rank_hi, const int64_t* __restrict__ off_out, int64_t out_base,
+                             uint8_t* __restrict__ dst, uint32_t n, int32_t* __restrict__ status)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * SEG_WAVES + (threadIdx.x >> 6);
+    if (i >= n) return;                                         // (whole waves: no barrier in this kernel)
+    svx_recsort::scatter_record(src, src_off, rank, rank_lo, rank_hi, off_out, out_base, dst, i, threadIdx.x & 63u, status);
+}
+
 struct SortWs {
     uint64_t* key[2];
     uint32_t* idx;
@@ -409,5 +434,26 @@ extern "C" int svx_record_gather_segments(const void* d_src, const int64_t* d_of
     const dim3 grid((uint32_t)(((uint64_t)n + SEG_WAVES - 1) / SEG_WAVES));
     hipLaunchKernelGGL(gather_segments_kernel, grid, dim3(WAVE * SEG_WAVES), 0, static_cast<hipStream_t>(stream),
                        static_cast<const uint8_t*>(d_src), d_off_in, d_order, d_off_out, static_cast<uint8_t*>(d_dst), n, elem_bytes);
+    return hipGetLastError() == hipSuccess ? SVX_OK : SVX_ELAUNCH;
+}
+
+extern "C" int svx_record_invert(const uint32_t* d_order, uint32_t n, uint32_t* d_rank, void* stream)
+{
+    if (n == 0) return SVX_OK;
+    if (!d_order || !d_rank) return SVX_EINVAL;
+    hipLaunchKernelGGL(invert_kernel, dim3((uint32_t)(((uint64_t)n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), d_order, d_rank, n);
+    return hipGetLastError() == hipSuccess ? SVX_OK : SVX_ELAUNCH;
+}
+
+extern "C" int svx_record_scatter_segments(const void* d_src, const int64_t* d_src_off, const uint32_t* d_rank, uint32_t rank_lo, uint32_t rank_hi,
+                                           const int64_t* d_off_out, int64_t out_base, void* d_dst, uint32_t n, int32_t* d_status, void* stream)
+{
+    if (rank_lo > rank_hi) return SVX_EINVAL;
+    if (n == 0 || rank_lo == rank_hi) return SVX_OK;
+    if (!d_src || !d_src_off || !d_rank || !d_off_out || !d_dst || !d_status) return SVX_EINVAL;
+    if (reinterpret_cast<uintptr_t>(d_src) & 3u) return SVX_EINVAL;
+    const dim3 grid((uint32_t)(((uint64_t)n + SEG_WAVES - 1) / SEG_WAVES));
+    hipLaunchKernelGGL(scatter_segments_kernel, grid, dim3(WAVE * SEG_WAVES), 0, static_cast<hipStream_t>(stream),
+                       static_cast<const uint8_t*>(d_src), d_src_off, d_rank, rank_lo, rank_hi, d_off_out, out_base, static_cast<uint8_t*>(d_dst), n, d_status);
     return hipGetLastError() == hipSuccess ? SVX_OK : SVX_ELAUNCH;
 }

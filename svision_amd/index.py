@@ -183,9 +183,10 @@ def _inflate_range(lib, torch, kernels, dev, pinned, blocks, entry, d_ref_len, n
     return rng
 
 
-def _walk_range(lib, torch, kernels, dev, rng, with_seq, clock):
+def _walk_range(lib, torch, kernels, dev, rng, with_seq, clock, extract=True):
     """The existing walk over a range's starts: counts -> prefix sums -> the records' fields, CIGAR words, names and (``with_seq``)
-    bases, all left on the device."""
+    bases, all left on the device.  ``extract=False``: the counts and prefix sums alone -- ``n_rec``, ``d_starts``, ``n_starts`` and
+    ``d_base``, what svx_bam_walk_offsets takes; no field, CIGAR word or name is extracted."""
     starts, d_raw = rng.starts, rng.d_raw
     n_starts = int(starts.size) - 1
     if n_starts <= 0:
@@ -210,6 +211,11 @@ def _walk_range(lib, torch, kernels, dev, rng, with_seq, clock):
         clock.lap("walk")
         return
     d_base = torch.from_numpy(base).to(dev)
+    if not extract:
+        rng.d_starts, rng.n_starts, rng.d_base = d_starts, n_starts, d_base
+        rng.n_rec, rng.words, rng.name_bytes = n_rec, words, name_bytes
+        clock.lap("walk")
+        return
     d_tid, d_pos, d_l_seq = (torch.empty(n_rec, dtype=torch.int32, device=dev) for _ in range(3))
     d_flag, d_mapq = torch.empty(n_rec, dtype=torch.int16, device=dev), torch.empty(n_rec, dtype=torch.uint8, device=dev)
     d_cig_off, d_name_off = (torch.empty(n_rec + 1, dtype=torch.int64, device=dev) for _ in range(2))
@@ -238,12 +244,17 @@ def _walk_range(lib, torch, kernels, dev, rng, with_seq, clock):
     clock.lap("walk")
 
 
-def record_ranges(bam_path, head, dev, clock, range_bytes=None, with_seq=False):
+def record_ranges(bam_path, head, dev, clock, range_bytes=None, with_seq=False, places=None, extract=True):
     """Generator: the whole file in ranges of about ``range_bytes`` compressed bytes (default: the device decoder's group size), each
     read, inflated, CRC-checked and walked on the device -> one :class:`RecordRange` a range, whose records are those that complete
     in it; a record the range's end cuts opens the next range, a range in which none completes is read again, twice as large.  The
     last range has ``at_end`` set.  The pass of :func:`build_index` and of svision_amd.ingest_sort.load_sample.  Raises
-    IndexBuildError for a corrupt block, a CRC mismatch, a malformed chain or a file cut inside a record.  ``head``: read_bam_header's."""
+    IndexBuildError for a corrupt block, a CRC mismatch, a malformed chain or a file cut inside a record.  ``head``: read_bam_header's.
+
+    Every range carries its ``place`` (file offset, compressed bytes asked for, entry offset).  ``places``: a list of such places of
+    an earlier pass over the same file -- those ranges again and no others, in the list's order (svision_amd/sort.py reads the ranges
+    a span of its output needs); a place that no longer gives a range raises IndexBuildError.  ``extract=False``: the walk stops at its
+    counts (:func:`_walk_range`): ``n_rec`` and what svx_bam_walk_offsets takes, no fields, CIGAR words or names."""
     import torch
     from . import ingest, ingest_gpu, kernels
     lib = _lib.load()
@@ -256,8 +267,14 @@ def record_ranges(bam_path, head, dev, clock, range_bytes=None, with_seq=False):
     want_bytes = base_bytes
     pinned = None                                               # a range's file bytes: read into pinned memory, reused from range to range
     threads = ingest.decode_threads()
+    places = None if places is None else iter(places)
     clock.lap("read", False)
     while True:
+        if places is not None:
+            place = next(places, None)
+            if place is None:
+                return
+            file_at, want_bytes, entry = place
         want = int(min(want_bytes, size - file_at))
         if want <= 0:
             raise IndexBuildError("%s ends without a whole BGZF block behind file offset %d" % (bam_path, file_at))
@@ -272,19 +289,25 @@ def record_ranges(bam_path, head, dev, clock, range_bytes=None, with_seq=False):
             raise IndexBuildError("%s: no whole BGZF block at file offset %d" % (bam_path, file_at + max(blocks.used, 0)))
         clock.lap("read", False)
         if blocks.k == 0:
+            if places is not None:
+                raise IndexBuildError("%s: no whole BGZF block at file offset %d, where an earlier pass read a range" % (bam_path, file_at))
             want_bytes *= 2
             continue
         rng = _inflate_range(lib, torch, kernels, dev, pinned, blocks, entry, d_ref_len, n_ref, clock)
         exit_off, total = rng.exit_off, rng.total
         if exit_off == entry and not at_end and exit_off < total:
+            if places is not None:
+                raise IndexBuildError("%s: no record completes in the range at file offset %d, where an earlier pass found some" % (bam_path, file_at))
             want_bytes *= 2                                     # no record completes in the range: the same place again, twice as large
             continue
-        _walk_range(lib, torch, kernels, dev, rng, with_seq, clock)
-        rng.before, rng.at_end = before, at_end
+        _walk_range(lib, torch, kernels, dev, rng, with_seq, clock, extract)
+        rng.before, rng.at_end, rng.place = before, at_end, (file_at, want_bytes, entry)
         if at_end and exit_off != total:
             raise IndexBuildError("%s is cut inside a record: its last record starts %d bytes before the end of the data and does not fit"
                                   % (bam_path, total - exit_off))
         yield rng
+        if places is not None:
+            continue
         if at_end:
             return
         want_bytes = base_bytes

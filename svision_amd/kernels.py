@@ -834,6 +834,38 @@ def record_gather_segments(src, off_in, order, off_out, out):
     return out
 
 
+def record_invert(order):
+    """order int32 [n] (record_sort's) -> int32 [n] (the bits of uint32): rank[order[r]] = r.  See include/svx.h svx_record_invert."""
+    lib = _lib.load()
+    _require_order(order)
+    n = int(order.shape[0])
+    rank = torch.empty(n, dtype=torch.int32, device=order.device)
+    _lib.check(lib.svx_record_invert(order.data_ptr(), n, rank.data_ptr(), _stream_ptr(order.device)), "svx_record_invert")
+    return rank
+
+
+def record_scatter_segments(src, src_off, rank, rank_lo, rank_hi, off_out, out_base, out, status):
+    """The n input records src[src_off[i]:src_off[i + 1]] (uint8; int64 [n + 1]) whose ``rank[i]`` (int32 [n], the bits of uint32) lies
+    in [rank_lo, rank_hi) -> ``out`` (uint8) at byte off_out[rank] - out_base; ``off_out``: int64, indexed by rank, at least rank_hi + 1
+    entries.  ``status``: int32 [1], set to 1 where a record's length is not off_out's (that record is not copied).  ``src``: 4-byte
+    aligned and readable up to the next multiple of 4 bytes behind its end; ``out`` must hold every record of the window whole.
+    See include/svx.h svx_record_scatter_segments."""
+    lib = _lib.load()
+    for t, name in ((src, "src"), (src_off, "src_off"), (off_out, "off_out"), (out, "out"), (status, "status")):
+        _require_cuda(t, name)
+    n = int(src_off.shape[0]) - 1
+    _require_order(rank, n)
+    rank_lo, rank_hi = int(rank_lo), int(rank_hi)
+    if src_off.dtype != torch.int64 or off_out.dtype != torch.int64 or src.dtype != torch.uint8 or out.dtype != torch.uint8 \
+            or status.dtype != torch.int32 or status.numel() < 1:
+        raise _lib.SvxError("src_off / off_out must be int64, src / out uint8, status int32 [1]")
+    if not 0 <= rank_lo <= rank_hi < int(off_out.shape[0]):
+        raise _lib.SvxError("the window [%d, %d) does not lie in off_out's %d ranks" % (rank_lo, rank_hi, int(off_out.shape[0]) - 1))
+    _lib.check(lib.svx_record_scatter_segments(src.data_ptr(), src_off.data_ptr(), rank.data_ptr(), rank_lo, rank_hi, off_out.data_ptr(), int(out_base),
+                                               out.data_ptr(), n, status.data_ptr(), _stream_ptr(src.device)), "svx_record_scatter_segments")
+    return out
+
+
 # ---- BGZF members from inflated bytes (svx_deflate.hip; the writer: svision_amd/sort.py) ----
 BGZF_SLOT = 65536                    # SVX_BGZF_SLOT: bytes of a member's slot in svx_bgzf_deflate's output
 BGZF_BLOCK_MAX = 0xFF00              # SVX_BGZF_BLOCK_MAX: the largest block the encoder takes (htslib's block size)

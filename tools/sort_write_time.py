@@ -1,6 +1,6 @@
 """Numbers for profiles/sort_write.txt: what svision_amd.sort writes, how small, how fast.
 
-    python tools/sort_write_time.py [--mb 400] [--coverage 30] [--out DIR] [--tables fixed|dynamic]
+    python tools/sort_write_time.py [--mb 400] [--coverage 30] [--out DIR] [--tables fixed|dynamic] [--memory BYTES] [--sort-only]
 
   file         a synthetic HiFi sample (svision_amd.synth, one contig of --mb megabases at --coverage x, random bases), its records
                shuffled (seed 1) and written under SO:unsorted with the product's writer
@@ -12,6 +12,12 @@
                bytes; svx_bgzf_deflate_dyn timed the same way beside svx_bgzf_deflate; and the phases of the dynamic kernel from
                its per-block clock readings (kernels.bgzf_deflate_dynamic(phase_ticks=True)): parse, code construction, emit as
                shares of the blocks' summed time
+  --memory BYTES     sort_bam(memory_bytes=BYTES), K / M / G as the command line takes them: below the records' inflated bytes the
+               file is written in spans (profiles/sort_spans.txt).  The result names the budget used, the spans and
+               torch.cuda.max_memory_allocated over the timed run
+  --sort-only        stop behind sort_bam's two runs: no compression table, no encoder timing, no load_sample.  With --out DIR the
+               shuffled input of an earlier call with the same --mb / --coverage is taken from DIR, not made again -- several
+               fresh processes time the same file
 Prints one JSON object."""
 import argparse
 import json
@@ -49,25 +55,44 @@ def main():
     ap.add_argument("--coverage", type=int, default=30)
     ap.add_argument("--out", default=None)
     ap.add_argument("--tables", choices=sort.TABLES, default="fixed")
+    ap.add_argument("--memory", type=sort.parse_memory, default=None)
+    ap.add_argument("--sort-only", action="store_true")
     args = ap.parse_args()
     d = args.out or tempfile.mkdtemp(prefix="sort_write_")
+    shuffled = os.path.join(d, "hifi.%d.%d.shuffled.bam" % (args.mb, args.coverage))
+    if not (args.sort_only and os.path.exists(shuffled)):
+        make_input(args, d, shuffled)
+    res = {"records": None, "input_bytes": os.path.getsize(shuffled)}
+    # ---- sort_bam: stage seconds (second run: allocator and page cache warm)
+    out = os.path.join(d, "hifi.sorted.bam")
+    kw = {} if args.memory is None else {"memory_bytes": args.memory}
+    for _ in range(2):
+        stats = {}
+        torch.cuda.reset_peak_memory_stats()
+        t0 = time.perf_counter()
+        sort.sort_bam(shuffled, out, stats=stats, tables=args.tables, **kw)
+        wall = time.perf_counter() - t0
+    res["records"] = stats["records"]
+    res["sort_bam"] = dict(stats, wall_seconds=round(wall, 4), tables=args.tables, max_memory_allocated=int(torch.cuda.max_memory_allocated()),
+                           device_memory_free=int(torch.cuda.mem_get_info()[0]))
+    res["sort_bam"].pop("range_records", None)
+    if args.sort_only:
+        print(json.dumps(res))
+        return
+    rest(args, d, shuffled, out, res)
+
+
+def make_input(args, d, shuffled):
     table, _g, _ = synth.simulate(synth.SimConfig(contigs=[("c1", args.mb * 1_000_000)], coverage=args.coverage, seed=4), with_genome=False)
     seg = bam.encode_reference_segment(table, seq="random", seed=1)
     sorted_in = os.path.join(d, "hifi.bam")
     bam.write_bam_segments(sorted_in, table.references, table.lengths, [seg], index=False)
     src = bam.read_bam(sorted_in, with_seq=True)
     perm = np.random.default_rng(1).permutation(len(src))
-    shuffled = os.path.join(d, "hifi.shuffled.bam")
     bam.write_bam(shuffled, sortcases.reorder_table(src, perm, sortcases.retitled(src.header_text, "unsorted")), with_seq=True, index=False)
-    res = {"records": len(src), "input_bytes": os.path.getsize(shuffled)}
-    # ---- sort_bam: stage seconds (second run: allocator and page cache warm)
-    out = os.path.join(d, "hifi.sorted.bam")
-    for _ in range(2):
-        stats = {}
-        t0 = time.perf_counter()
-        sort.sort_bam(shuffled, out, stats=stats, tables=args.tables)
-        wall = time.perf_counter() - t0
-    res["sort_bam"] = dict(stats, wall_seconds=round(wall, 4), tables=args.tables)
+
+
+def rest(args, d, shuffled, out, res):
     # ---- compression on the same blocks
     stream = b"".join(data for _c, data in baicases.bgzf_blocks(open(out, "rb").read()))
     blocks = [stream[at:at + BLOCK] for at in range(0, len(stream), BLOCK)]
