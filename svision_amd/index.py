@@ -6,7 +6,8 @@ the whole file.  Everything such a pass needs is on the device already -- inflat
 yields every record's reference span -- except knowing where records start when nothing says so: svx_bam_find_starts
 (csrc/svx_bamindex.hip) finds, per BGZF block, the first record that starts in it.  The pass:
 
-  header     host: read_bam_header (references) + the first blocks through zlib -> where the first record starts
+  header     host: read_bam_header (references) + the first blocks through zlib -> where the first record starts (header_place over
+             bgzf_members, the one walk of a file's members: svision_amd/sort.py takes the header's bytes and the ISIZE sum from it)
   per range  whole BGZF blocks, the decoder's group size of file a range (svx_read_range, svx_bgzf_index), then on the device
              svx_bgzf_inflate_fast -> svx_bgzf_crc32 -> svx_bam_find_starts -> svx_bam_walk_count / _extract ->
              svx_bam_walk_offsets -> svx_cigar_scan (its per-record reference span) -> tid, pos, flag, span, byte offset back
@@ -22,6 +23,7 @@ The pass itself -- ranges, carry, inflate, CRC, find-starts and the walk -- is :
 range's extracted arrays on the device; build_index adds the byte offsets and the scan per range, svision_amd/ingest_sort.py (an
 UNSORTED file: its records sorted on the device) keeps the arrays and sorts them.
 """
+import collections
 import os
 import struct
 import sys
@@ -42,37 +44,53 @@ class IndexBuildError(ValueError):
     pass
 
 
-def first_record(path, limit=1 << 30):
-    """Host: the BAM header through zlib, block by block -> (file offset of the BGZF block the first record starts in, the
-    record's offset in that block's inflated bytes, number of references)."""
-    need, have, n_ref, step, at = 8, 0, None, 0, 0
-    head = bytearray()
+def bgzf_members(path):
+    """Generator over a file's BGZF members, hopping from header to header: (file offset, member bytes, XLEN, ISIZE).  Raises
+    IndexBuildError where no whole member with a BC subfield stands."""
+    size = os.path.getsize(path)
     with open(path, "rb") as f:
-        while True:
+        at = 0
+        while at < size:
             f.seek(at)
-            fixed = f.read(18)
-            if len(fixed) < 18 or fixed[:4] != b"\x1f\x8b\x08\x04":
-                raise IndexBuildError("%s: no BGZF block at file offset %d (the BAM header is cut)" % (path, at))
+            fixed = f.read(12)
+            if len(fixed) < 12 or fixed[:4] != b"\x1f\x8b\x08\x04":
+                raise IndexBuildError("no BGZF block at file offset %d" % at)
             xlen = struct.unpack_from("<H", fixed, 10)[0]
-            f.seek(at + 12)
             extra = f.read(xlen)
             bsize, q = None, 0
             while q + 4 <= len(extra):
                 slen = struct.unpack_from("<H", extra, q + 2)[0]
-                if extra[q:q + 2] == b"BC" and slen == 2:
+                if extra[q:q + 2] == b"BC" and slen == 2 and q + 6 <= len(extra):
                     bsize = struct.unpack_from("<H", extra, q + 4)[0] + 1
                 q += 4 + slen
-            if bsize is None:
-                raise IndexBuildError("%s: the gzip member at file offset %d is no BGZF block" % (path, at))
-            payload = f.read(bsize - 12 - xlen - 8)
+            if bsize is None or bsize < 12 + xlen + 8 or at + bsize > size:
+                raise IndexBuildError("no whole BGZF block at file offset %d" % at)
+            f.seek(at + bsize - 4)
+            yield at, bsize, xlen, struct.unpack("<I", f.read(4))[0]
+            at += bsize
+
+
+HeaderPlace = collections.namedtuple("HeaderPlace", "block_at entry n_ref head isize")
+
+
+def header_place(path, members=None, limit=1 << 30):
+    """Host: the BAM header through zlib, block by block -> HeaderPlace(file offset of the BGZF block the first record starts in, the
+    record's offset in that block's inflated bytes, number of references, the inflated bytes in front of the first record, the sum of
+    the ISIZE fields of the members taken).  ``members``: a :func:`bgzf_members` of the file at its start; it is left behind the last
+    member the header needed, so a caller that wants every member's ISIZE goes on where this stopped."""
+    need, have, n_ref, step, isize_sum = 8, 0, None, 0, 0
+    head = bytearray()
+    with open(path, "rb") as f:
+        for at, bsize, xlen, isize in (bgzf_members(path) if members is None else members):
+            f.seek(at + 12 + xlen)
             try:
-                data = zlib.decompress(payload, -15)
+                data = zlib.decompress(f.read(bsize - 12 - xlen - 8), -15)
             except zlib.error as exc:
                 raise IndexBuildError("%s: the block at file offset %d does not inflate (%s)" % (path, at, exc)) from None
             block_at, block_base = at, have
             head += data
             have += len(data)
-            at += bsize
+            isize_sum += isize
             # the header's fields, as far as they are in hand: magic, l_text, text, n_ref, then per reference l_name, name, l_ref
             while have >= need:
                 if step == 0:
@@ -102,9 +120,17 @@ def first_record(path, limit=1 << 30):
                 break
             if have > limit:
                 raise IndexBuildError("%s: a BAM header of more than %d bytes" % (path, limit))
+        else:
+            raise IndexBuildError("%s: no BGZF block at file offset %d (the BAM header is cut)" % (path, os.path.getsize(path)))
     if need == have:                                            # the header fills its block: the first record opens the next one
-        return at, 0, n_ref
-    return block_at, need - block_base, n_ref
+        return HeaderPlace(at + bsize, 0, n_ref, bytes(head), isize_sum)
+    return HeaderPlace(block_at, need - block_base, n_ref, bytes(head[:need]), isize_sum)
+
+
+def first_record(path, limit=1 << 30):
+    """-> (file offset of the BGZF block the first record starts in, the record's offset in that block's inflated bytes, number of
+    references): :func:`header_place` without the bytes."""
+    return tuple(header_place(path, limit=limit)[:3])
 
 
 class _Clock:
@@ -119,6 +145,46 @@ class _Clock:
         now = time.perf_counter()
         self.times[stage] += now - self.t
         self.t = now
+
+
+def on_device(needs, device, stages=STAGES):
+    """What every device routine here starts with -> (torch, libsvx, the device with its index, a :class:`_Clock` over ``stages``).
+    No GPU: SvxError, ``needs`` being the caller's sentence of what it wants one for."""
+    import torch
+    if not torch.cuda.is_available():
+        raise _lib.SvxError("%s; there is no CPU fallback" % needs)
+    dev = torch.device(device)
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    return torch, _lib.load(), dev, _Clock(torch, dev, stages)
+
+
+def temp_beside(path):
+    """A temporary file in the directory of ``path``, so that a rename puts it in place -> (the open file, its name)."""
+    fd, tmp = tempfile.mkstemp(prefix=os.path.basename(path) + ".", suffix=".tmp", dir=os.path.dirname(os.path.abspath(path)))
+    return os.fdopen(fd, "wb"), tmp
+
+
+def into_place(tmp, path):
+    """The closed temporary file becomes ``path``, with the mode the umask gives a new file."""
+    os.chmod(tmp, 0o666 & ~_umask())
+    os.replace(tmp, path)
+
+
+def discard(tmp):
+    if tmp is not None and os.path.exists(tmp):
+        os.unlink(tmp)
+
+
+def write_into_place(path, data):
+    """``data`` written under a temporary name beside ``path`` and renamed; a failure leaves no file."""
+    f, tmp = temp_beside(path)
+    try:
+        with f:
+            f.write(data)
+        into_place(tmp, path)
+    finally:
+        discard(tmp)
 
 
 def _as_i64(t_np):
@@ -211,9 +277,9 @@ def _walk_range(lib, torch, kernels, dev, rng, with_seq, clock, extract=True):
         clock.lap("walk")
         return
     d_base = torch.from_numpy(base).to(dev)
+    rng.d_starts, rng.n_starts, rng.d_base = d_starts, n_starts, d_base
+    rng.n_rec, rng.words, rng.name_bytes = n_rec, words, name_bytes
     if not extract:
-        rng.d_starts, rng.n_starts, rng.d_base = d_starts, n_starts, d_base
-        rng.n_rec, rng.words, rng.name_bytes = n_rec, words, name_bytes
         clock.lap("walk")
         return
     d_tid, d_pos, d_l_seq = (torch.empty(n_rec, dtype=torch.int32, device=dev) for _ in range(3))
@@ -237,14 +303,12 @@ def _walk_range(lib, torch, kernels, dev, rng, with_seq, clock, extract=True):
         _lib.check(lib.svx_bam_walk_extract(d_raw.data_ptr(), d_starts.data_ptr(), n_starts, d_base.data_ptr(), d_tid.data_ptr(), d_pos.data_ptr(),
                                             d_flag.data_ptr(), d_mapq.data_ptr(), d_l_seq.data_ptr(), d_cig_off.data_ptr(), d_cigar.data_ptr(),
                                             d_name_off.data_ptr(), d_names.data_ptr(), n_rec, st), "svx_bam_walk_extract")
-    rng.d_starts, rng.n_starts, rng.d_base = d_starts, n_starts, d_base
-    rng.n_rec, rng.words, rng.name_bytes = n_rec, words, name_bytes
     rng.d_tid, rng.d_pos, rng.d_flag, rng.d_mapq, rng.d_l_seq = d_tid, d_pos, d_flag, d_mapq, d_l_seq
     rng.d_cig_off, rng.d_cigar, rng.d_name_off, rng.d_names = d_cig_off, d_cigar, d_name_off, d_names
     clock.lap("walk")
 
 
-def record_ranges(bam_path, head, dev, clock, range_bytes=None, with_seq=False, places=None, extract=True):
+def record_ranges(bam_path, head, dev, clock, range_bytes=None, with_seq=False, places=None, extract=True, first=None):
     """Generator: the whole file in ranges of about ``range_bytes`` compressed bytes (default: the device decoder's group size), each
     read, inflated, CRC-checked and walked on the device -> one :class:`RecordRange` a range, whose records are those that complete
     in it; a record the range's end cuts opens the next range, a range in which none completes is read again, twice as large.  The
@@ -254,12 +318,13 @@ def record_ranges(bam_path, head, dev, clock, range_bytes=None, with_seq=False, 
     Every range carries its ``place`` (file offset, compressed bytes asked for, entry offset).  ``places``: a list of such places of
     an earlier pass over the same file -- those ranges again and no others, in the list's order (svision_amd/sort.py reads the ranges
     a span of its output needs); a place that no longer gives a range raises IndexBuildError.  ``extract=False``: the walk stops at its
-    counts (:func:`_walk_range`): ``n_rec`` and what svx_bam_walk_offsets takes, no fields, CIGAR words or names."""
+    counts (:func:`_walk_range`): ``n_rec`` and what svx_bam_walk_offsets takes, no fields, CIGAR words or names.  ``first``: what
+    :func:`first_record` gives for the file, where the caller has it already."""
     import torch
     from . import ingest, ingest_gpu, kernels
     lib = _lib.load()
     base_bytes = int(range_bytes or ingest_gpu.LARGE_GROUP_BYTES)
-    file_at, entry, n_ref = first_record(bam_path)
+    file_at, entry, n_ref = first or first_record(bam_path)
     if n_ref != len(head.references):
         raise IndexBuildError("%s: the header names %d references, its dictionary %d" % (bam_path, len(head.references), n_ref))
     size = os.path.getsize(bam_path)
@@ -318,13 +383,22 @@ def record_ranges(bam_path, head, dev, clock, range_bytes=None, with_seq=False, 
             file_at, entry = int(blocks.coff[b]), exit_off - int(rng.dst[b])
 
 
+def walk_offsets(lib, torch, kernels, dev, rng, closed=False):
+    """svx_bam_walk_offsets: the byte offset of every record of the range in its inflated stream, on the device [n_rec]; ``closed``:
+    [n_rec + 1], the chain's ``exit_off`` behind them -- CSR offsets of the records' bytes."""
+    d_off = torch.empty(rng.n_rec + (1 if closed else 0), dtype=torch.int64, device=dev)
+    _lib.check(lib.svx_bam_walk_offsets(rng.d_raw.data_ptr(), rng.d_starts.data_ptr(), rng.n_starts, rng.d_base.data_ptr(), d_off.data_ptr(),
+                                        kernels._stream_ptr(dev)), "svx_bam_walk_offsets")
+    if closed:
+        d_off[rng.n_rec] = int(rng.exit_off)
+    return d_off
+
+
 def _index_fields(lib, torch, kernels, dev, rng, clock):
     """What the index wants of a range's records -> host arrays tid, pos, flag, reference span, byte offset in the range's stream."""
     if rng.n_rec == 0:
         return np.empty(0, np.int32), np.empty(0, np.int32), np.empty(0, np.uint16), np.empty(0, np.int32), np.empty(0, np.uint64)
-    d_rec_off = torch.empty(rng.n_rec, dtype=torch.int64, device=dev)
-    _lib.check(lib.svx_bam_walk_offsets(rng.d_raw.data_ptr(), rng.d_starts.data_ptr(), rng.n_starts, rng.d_base.data_ptr(), d_rec_off.data_ptr(),
-                                        kernels._stream_ptr(dev)), "svx_bam_walk_offsets")
+    d_rec_off = walk_offsets(lib, torch, kernels, dev, rng)
     clock.lap("walk")
     # the reference span of every record: the scan's statistics (a CG-tag record: of its real CIGAR); no gap is long enough to be listed
     scan = kernels.cigar_scan(rng.d_cigar, rng.d_cig_off, rng.d_pos, 0x7FFFFFFF, n_words=rng.words)
@@ -339,17 +413,10 @@ def build_index(bam_path, out_path=None, device="cuda", range_bytes=None, stats=
     """Write the ``.bai`` of ``bam_path`` to ``out_path`` (default ``bam_path + ".bai"``) and return that path.  ``range_bytes``:
     compressed bytes a range (default: the device decoder's group size; tests).  ``stats``: a dict that receives the number of
     ranges, blocks and records and the seconds per stage -- in total ("seconds") and per range ("per_range")."""
-    import torch
     from . import kernels
     from .io.bam import read_bam_header
-    if not torch.cuda.is_available():
-        raise _lib.SvxError("build_index needs the GPU (svx_bam_find_starts); there is no CPU fallback")
-    lib = _lib.load()
-    dev = torch.device(device)
-    if dev.index is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
+    torch, lib, dev, clock = on_device("build_index needs the GPU (svx_bam_find_starts)", device)
     out_path = out_path or bam_path + ".bai"
-    clock = _Clock(torch, dev)
     head = read_bam_header(bam_path)
     n_ref = len(head.references)
     parts, per_range, n_blocks, end_voff = [], [], 0, None
@@ -370,16 +437,7 @@ def build_index(bam_path, out_path=None, device="cuda", range_bytes=None, stats=
         data = bai.bai_bytes(n_ref, tid, pos64, pos64 + np.maximum(span.astype(np.int64), 1), flag, voff, voff_end)
     except ValueError as exc:
         raise IndexBuildError("%s: %s" % (bam_path, exc)) from None
-    fd, tmp = tempfile.mkstemp(prefix=os.path.basename(out_path) + ".", suffix=".tmp", dir=os.path.dirname(os.path.abspath(out_path)))
-    try:
-        with os.fdopen(fd, "wb") as f:
-            f.write(data)
-        os.chmod(tmp, 0o666 & ~_umask())
-        os.replace(tmp, out_path)
-    except BaseException:
-        if os.path.exists(tmp):
-            os.unlink(tmp)
-        raise
+    write_into_place(out_path, data)
     clock.lap("assembly", False)
     if stats is not None:
         stats.update(ranges=len(per_range), blocks=n_blocks, records=int(tid.size), seconds={k: round(v, 6) for k, v in clock.times.items()},

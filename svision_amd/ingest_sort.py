@@ -20,8 +20,6 @@ CRC mismatch, a malformed or cut chain or a device allocation that fails raises 
 """
 import numpy as np
 
-from . import _lib
-
 STAGES = ("read", "upload", "inflate", "crc", "find_starts", "walk", "concat", "sort", "gather", "read_back", "names", "scan")
 
 
@@ -75,17 +73,10 @@ def load_sample(bam_path, fasta, min_sv, device="cuda", with_seq=False, range_by
     """The :class:`svision_amd.sample.Sample` of a BAM whose records come in any order (see the head of the module).  ``with_seq``: the
     table carries the read bases (--hash / --graph).  ``range_bytes``: compressed bytes a range (default: the device decoder's group
     size; tests).  ``stats``: a dict that receives the number of ranges and records, the CIGAR words and the seconds per stage."""
-    import torch
     from . import index, kernels
     from .io.bam import AlignmentTable, read_bam_header
     from .sample import Sample
-    if not torch.cuda.is_available():
-        raise _lib.SvxError("load_sample needs the GPU (svx_record_sort); there is no CPU fallback")
-    lib = _lib.load()
-    dev = torch.device(device)
-    if dev.index is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
-    clock = index._Clock(torch, dev, STAGES)
+    torch, lib, dev, clock = index.on_device("load_sample needs the GPU (svx_record_sort)", device, STAGES)
     try:
         head = read_bam_header(bam_path)
     except ValueError as exc:                                   # (the host reader inflates in front of the header's end: a corrupt block shows here)

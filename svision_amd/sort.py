@@ -53,17 +53,23 @@ placed in pieces, the same two files byte for byte:
 
 A corrupt block, a CRC mismatch, a malformed or cut chain, a device allocation or a write that fails raises SortWriteError (a
 ValueError); no file and no temporary is left behind.
+
+:func:`sort_bam` is the list of its steps, each a function of this module over named values: ``_open`` (header, first record and
+``room`` from one pass over the file's members: index.bgzf_members, index.header_place) -> ``_key_pass`` -> ``_order`` -> the pieces,
+``_pieces_in_core`` or ``_pieces_spanned``: generators of (device buffer, first byte, bytes), a chunk each -> :class:`BgzfWriter`,
+which owns the temporary file and the ledger of members and is handed its encoder (:class:`DeviceEncode`; zlib in the CPU tests) ->
+``_bai`` -> :func:`commit_pair`.  Which records a chunk or a span takes is one rule, :func:`records_touching`; the 0xFF00 cut one
+function, :func:`block_cuts`.
 """
 import collections
 import os
 import struct
 import sys
-import tempfile
 import zlib
 
 import numpy as np
 
-from . import _lib
+from . import _lib, index
 
 BLOCK = 0xFF00                                                  # htslib's block size: inflated bytes a BGZF block of the output
 DEFAULT_CHUNK_BYTES = 1024 * BLOCK
@@ -90,49 +96,12 @@ def sorted_header_text(text):
     return "@HD\tVN:1.6\tSO:coordinate\n" + text
 
 
-def _members(path):
-    """Generator over the file's BGZF members, hopping from header to header: (file offset, member bytes, XLEN, ISIZE).  Raises
-    SortWriteError where no whole member with a BC subfield stands."""
-    size = os.path.getsize(path)
-    with open(path, "rb") as f:
-        at = 0
-        while at < size:
-            f.seek(at)
-            fixed = f.read(12)
-            if len(fixed) < 12 or fixed[:4] != b"\x1f\x8b\x08\x04":
-                raise SortWriteError("no BGZF block at file offset %d" % at)
-            xlen = struct.unpack_from("<H", fixed, 10)[0]
-            extra = f.read(xlen)
-            bsize, q = None, 0
-            while q + 4 <= len(extra):
-                slen = struct.unpack_from("<H", extra, q + 2)[0]
-                if extra[q:q + 2] == b"BC" and slen == 2 and q + 6 <= len(extra):
-                    bsize = struct.unpack_from("<H", extra, q + 4)[0] + 1
-                q += 4 + slen
-            if bsize is None or bsize < 12 + xlen + 8 or at + bsize > size:
-                raise SortWriteError("no whole BGZF block at file offset %d" % at)
-            f.seek(at + bsize - 4)
-            yield at, bsize, xlen, struct.unpack("<I", f.read(4))[0]
-            at += bsize
-
-
 def inflated_size(path):
     """The sum of the members' ISIZE fields: the file's inflated bytes, from its headers and footers alone."""
-    return sum(isize for _at, _bsize, _xlen, isize in _members(path))
-
-
-def _inflated_head(path, block_at, entry):
-    """The inflated bytes of the file up to the first record: the blocks in front of file offset ``block_at`` and ``entry`` bytes of the
-    block there."""
-    out = bytearray()
-    with open(path, "rb") as f:
-        for at, bsize, xlen, _isize in _members(path):
-            if at > block_at or (at == block_at and not entry):
-                break
-            f.seek(at + 12 + xlen)
-            data = zlib.decompress(f.read(bsize - 12 - xlen - 8), -15)      # (index.first_record has inflated these blocks already)
-            out += data[:entry] if at == block_at else data
-    return bytes(out)
+    try:
+        return sum(isize for _at, _bsize, _xlen, isize in index.bgzf_members(path))
+    except index.IndexBuildError as exc:
+        raise SortWriteError(str(exc)) from None
 
 
 def sorted_header_bytes(head):
@@ -150,11 +119,21 @@ def sorted_header_bytes(head):
 Span = collections.namedtuple("Span", "lo hi r_lo r_hi base size")
 
 
+def records_touching(off_out, lo, hi):
+    """The records that touch the stream bytes [lo, hi), ``off_out`` [n + 1] being the records' offsets in the stream -> (r_lo, r_hi,
+    base): the records [r_lo, r_hi) -- records of no byte between two others included, those at an edge left out: they have nothing
+    to place -- and ``base = off_out[r_lo]``, the stream offset of the first one's first byte.  Scalars or arrays of lo and hi: the one
+    rule of the chunks of a run in one piece and of the spans."""
+    r_lo = np.searchsorted(off_out, lo, "right") - 1
+    r_hi = np.searchsorted(off_out, hi, "left")
+    return r_lo, r_hi, off_out[r_lo]
+
+
 def plan_spans(off_out, memory_bytes):
     """The output's record stream [0, total), ``off_out`` [n + 1] being its records' offsets, cut into spans of
     ``max(memory_bytes // BLOCK, 1) * BLOCK`` bytes -- whole blocks, so the 0xFF00 cuts fall where they fall in one piece -> a list of
     Span(lo, hi, r_lo, r_hi, base, size): the stream bytes [lo, hi); the records [r_lo, r_hi) that touch them, by the rule of the
-    chunk loop (records of no byte between two others included, those at a span's edge left out: they have nothing to place);
+    chunks (:func:`records_touching`);
     ``base = off_out[r_lo]``, the stream offset of the span buffer's first byte, and the buffer's ``size``,
     off_out[r_hi] - base + 4: the records are placed whole, the first and the last may reach over the span's edges, so a buffer
     exceeds the span by less than two records (+ the 4 bytes of slack the encoder's aligned loads want).  No byte: no span."""
@@ -165,9 +144,7 @@ def plan_spans(off_out, memory_bytes):
         span_bytes = max(total, 1)
     lo = np.arange(0, total, span_bytes, dtype=np.int64)
     hi = np.minimum(lo + span_bytes, total)
-    r_lo = np.searchsorted(off_out, lo, "right") - 1
-    r_hi = np.searchsorted(off_out, hi, "left")
-    base = off_out[r_lo]
+    r_lo, r_hi, base = records_touching(off_out, lo, hi)
     size = off_out[r_hi] - base + 4
     return [Span(*(int(v) for v in s)) for s in zip(lo, hi, r_lo, r_hi, base, size)]
 
@@ -193,7 +170,105 @@ def parse_memory(text):
     return int(digits) * scale
 
 
+# ---- the BGZF writer (host: the encoder is handed in) ----
+def block_cuts(n_bytes, eof=False):
+    """The 0xFF00 cut: ``n_bytes`` bytes in blocks of BLOCK, the last one shorter -> the blocks' offsets [blocks + 1]; ``eof``: with
+    an empty block behind them."""
+    n = (n_bytes + BLOCK - 1) // BLOCK + bool(eof)
+    return np.minimum(np.arange(n + 1, dtype=np.int64) * BLOCK, n_bytes)
+
+
+def chunk_cuts(lo, hi, step):
+    """The stream bytes [lo, hi) in chunks of ``step`` -> (lo, hi) of each, in order."""
+    for at in range(lo, hi, step):
+        yield at, min(at + step, hi)
+
+
+Written = collections.namedtuple("Written", "coff dst blocks stored_blocks dynamic_blocks chunks compressed_bytes inflated_bytes")
+
+
+class BgzfWriter:
+    """The output file while it is written: a temporary file beside ``path``, and the ledger of what went into it -- every member's
+    length and every block's inflated bytes (what the index needs), the stored and the dynamic blocks, the chunks.
+
+    ``encode(buffer, block offsets [n + 1]) -> (the n members end to end: host uint8 array, their lengths [n], 1 where stored, 1 where
+    dynamic: host arrays)`` is all that knows how blocks are deflated and where ``buffer`` lives: :class:`DeviceEncode` in sort_bam,
+    zlib over a NumPy array in tests/test_sort_steps_cpu.py.  ``clock.lap("write", False)`` closes every write.  ``source`` names the
+    input in a refusal."""
+
+    def __init__(self, path, encode, clock, source=None):
+        self.encode, self.clock, self.source = encode, clock, source or path
+        self.member_lens, self.block_bytes, self.stored, self.dynamic, self.chunks, self.eof = [], [], 0, 0, 0, None
+        self.f, self.tmp = index.temp_beside(path)
+
+    def _append(self, buf, first, n_bytes, eof=False):
+        off = block_cuts(n_bytes, eof)
+        packed, m, stored, dynamic = self.encode(buf, off + first)
+        if (m < 26).any():
+            raise SortWriteError("%s: svx_bgzf_deflate refused a block" % self.source)
+        n = m.size - bool(eof)
+        end = int(m[:n].sum())
+        self.f.write(packed[:end].tobytes())
+        if eof:
+            self.eof = packed[end:].tobytes()
+        self.stored += int(stored[:n].sum())
+        self.dynamic += int(dynamic[:n].sum())
+        self.member_lens.append(m[:n])
+        self.block_bytes.append(np.diff(off[:n + 1]))
+        self.clock.lap("write", False)
+
+    def put_header(self, buf, n_bytes):
+        """The header's bytes buf[:n_bytes] in blocks of their own -- the first record opens a new block -- and, encoded with them,
+        an empty block: its member is the end-of-file marker, kept for :meth:`finish`."""
+        self._append(buf, 0, n_bytes, eof=True)
+
+    def put(self, buf, first, n_bytes):
+        """A chunk: the stream bytes buf[first : first + n_bytes], whole blocks but for the stream's last, encoded and appended."""
+        self._append(buf, first, n_bytes)
+        self.chunks += 1
+
+    def finish(self):
+        """The end-of-file marker closes the file -> Written: every member's file offset ``coff`` and where its block's bytes lie in the
+        inflated file, ``dst`` [blocks + 1], the end-of-file block included, and the counts."""
+        self.f.write(self.eof)
+        self.f.close()
+        self.clock.lap("write", False)
+        member_lens = np.concatenate(self.member_lens + [np.asarray([len(self.eof)], np.int64)])
+        block_bytes = np.concatenate(self.block_bytes + [np.zeros(1, np.int64)])
+        coff = np.zeros(member_lens.size, np.uint64)
+        coff[1:] = np.cumsum(member_lens[:-1])
+        dst = np.zeros(block_bytes.size + 1, np.uint64)
+        dst[1:] = np.cumsum(block_bytes)
+        return Written(coff, dst, int(member_lens.size), self.stored, self.dynamic, self.chunks, int(member_lens.sum()), int(dst[-1]))
+
+    def discard(self):
+        """The file closed and, unless it was renamed into place, removed."""
+        self.f.close()
+        index.discard(self.tmp)
+
+
+def commit_pair(tmp_bam, out_path, bai_data):
+    """The written temporary file becomes ``out_path`` and ``bai_data`` its ``.bai``: the pair or nothing -- a failure leaves neither
+    file nor temporary, a sorted file that was already in place is removed again when its index cannot follow."""
+    f, tmp_bai = index.temp_beside(out_path + ".bai")
+    try:
+        with f:
+            f.write(bai_data)
+        index.into_place(tmp_bam, out_path)
+        try:
+            index.into_place(tmp_bai, out_path + ".bai")
+        except OSError:
+            os.unlink(out_path)
+            raise
+    finally:
+        index.discard(tmp_bam)
+        index.discard(tmp_bai)
+
+
 # ---- the device steps ----
+_Dev = collections.namedtuple("_Dev", "torch lib kernels dev clock")
+
+
 def _encoder(kernels, tables):
     """-> deflate(d_in, d_in_off) -> (slots, member lengths, 1 where stored, 1 where dynamic: device tensors) of the chosen encoder."""
     if tables == "dynamic":
@@ -207,20 +282,197 @@ def _encoder(kernels, tables):
     return deflate
 
 
-def _deflate_blocks(torch, deflate, dev, d_bytes, first, n_bytes):
-    """The bytes d_bytes[first : first + n_bytes] (n_bytes > 0) cut every 0xFF00 and deflated -> (slots, member lengths, stored flags,
-    dynamic flags: device tensors, the number of blocks)."""
-    n = (n_bytes + BLOCK - 1) // BLOCK
-    off = np.minimum(np.arange(n + 1, dtype=np.int64) * BLOCK, n_bytes) + first
-    slots, member_len, stored, dynamic = deflate(d_bytes, torch.from_numpy(off).to(dev))
-    return slots, member_len, stored, dynamic, n
-
-
 def _download(torch, d, n_bytes):
     h = torch.empty(max(n_bytes, 1), dtype=torch.uint8, pin_memory=True)
     h[:n_bytes].copy_(d[:n_bytes], non_blocking=True)
     torch.cuda.current_stream(d.device).synchronize()
     return h[:n_bytes].numpy()
+
+
+class DeviceEncode:
+    """:class:`BgzfWriter`'s encoder on the device: the blocks of a device buffer deflated (``tables``), packed (svx_bgzf_pack) and
+    downloaded through pinned memory, the clock lapped behind each; slots and packed members go when the call returns."""
+
+    def __init__(self, dv, tables):
+        self.dv, self.deflate = dv, _encoder(dv.kernels, tables)
+
+    def __call__(self, d_bytes, off):
+        torch, kernels, clock = self.dv.torch, self.dv.kernels, self.dv.clock
+        slots, d_len, d_stored, d_dynamic = self.deflate(d_bytes, torch.from_numpy(off).to(self.dv.dev))
+        clock.lap("deflate")
+        d_packed, _d_file_off = kernels.bgzf_pack(slots, d_len, int(off[-1] - off[0]) + kernels.BGZF_MEMBER_EXTRA * (off.size - 1))
+        clock.lap("pack")
+        m = d_len.cpu().numpy().astype(np.int64)
+        stored, dynamic = d_stored.cpu().numpy(), d_dynamic.cpu().numpy()
+        packed = _download(torch, d_packed, int(m.sum()))
+        clock.lap("download")
+        return packed, m, stored, dynamic
+
+
+Opened = collections.namedtuple("Opened", "path head first header room")
+
+
+def _open(bam_path):
+    """open: -> Opened(the path, read_bam_header's table, first_record's (file offset, entry, references), the header's bytes as the
+    output takes them, ``room``: the records' inflated bytes by the members' ISIZE fields) -- one pass over the file's members."""
+    from .io.bam import read_bam_header
+    try:
+        head = read_bam_header(bam_path)
+        members = index.bgzf_members(bam_path)
+        place = index.header_place(bam_path, members)           # (takes the members the header lies in; the rest follow below)
+        header = sorted_header_bytes(place.head)
+        room = place.isize + sum(isize for _at, _bsize, _xlen, isize in members) - len(place.head)
+    except (ValueError, TypeError, OSError, zlib.error, struct.error) as exc:
+        raise SortWriteError("%s: %s" % (bam_path, exc)) from None
+    if room < 0:
+        raise SortWriteError("%s: its BGZF blocks hold fewer bytes than its header" % bam_path)
+    return Opened(bam_path, head, tuple(place[:3]), header, room)
+
+
+class KeyPass:
+    """What the pass over the file leaves, filled by :func:`_key_pass` as it goes (``seen`` is right in a failure's message too):
+    ``range_records`` and ``places`` per range; ``seen``: the inflated record bytes so far; behind the join the ``n`` records' host
+    fields ``tid pos flag span``, the device keys ``d_tid d_pos`` (until the sort has taken them), the records' offsets in the joined
+    stream ``off_in`` / ``d_off_in`` [n + 1], and ``d_stream``: the resident record stream, None in a spanned run."""
+
+    def __init__(self):
+        self.range_records, self.places, self.seen, self.n = [], [], 0, 0
+        self.tid = self.pos = self.flag = self.span = self.d_tid = self.d_pos = self.off_in = self.d_off_in = self.d_stream = None
+
+
+def _key_pass(dv, opened, spanned, range_bytes, kp):
+    """key pass: every range of the file (index.record_ranges) -> ``kp`` filled.  The record stream is allocated once, by the ISIZE sum
+    (4 readable bytes behind it: the gather's aligned loads), and every range's slice goes straight to its place in it; ``spanned``:
+    no byte is kept."""
+    torch, dev, clock, room = dv.torch, dv.dev, dv.clock, opened.room
+    kp.d_stream = None if spanned else torch.empty(room + 4, dtype=torch.uint8, device=dev)
+    host, d_keys, lens = [], [], []
+    for rng in index.record_ranges(opened.path, opened.head, dev, clock, range_bytes, first=opened.first):
+        kp.range_records.append(int(rng.n_rec))
+        kp.places.append(rng.place)
+        if rng.n_rec:
+            tid, pos, flag, span, rec_off = index._index_fields(dv.lib, torch, dv.kernels, dev, rng, clock)
+            first, last = int(rec_off[0]), int(rng.exit_off)
+            if kp.seen + last - first > room:
+                raise SortWriteError("%s: more record bytes than its BGZF blocks' ISIZE fields add up to (%d)" % (opened.path, room))
+            host.append((tid, pos, flag, span))
+            lens.append(np.diff(np.append(rec_off, np.uint64(last)).astype(np.int64)))
+            d_keys.append((rng.d_tid, rng.d_pos))
+            if not spanned:
+                kp.d_stream[kp.seen:kp.seen + last - first].copy_(rng.d_raw[first:last])      # the records that complete in the range: contiguous there
+            kp.seen += last - first
+        rng.d_raw = rng.d_starts = rng.d_base = rng.d_cigar = rng.d_cig_off = rng.d_names = rng.d_name_off = None
+        del rng
+        clock.lap("keep")
+    n = kp.n = int(sum(l.size for l in lens))
+    if n > 0xFFFFFFFF:
+        raise SortWriteError("%s: %d records -- svx_record_sort takes up to 2^32 - 1" % (opened.path, n))
+    # ---- join: CSR offsets and the keys of the one record stream
+    if not spanned:
+        kp.d_stream[kp.seen:] = 0
+    kp.off_in = np.zeros(n + 1, np.int64)
+    if n:
+        kp.off_in[1:] = np.cumsum(np.concatenate(lens))
+    kp.d_off_in = torch.from_numpy(kp.off_in).to(dev)
+    if n:
+        kp.d_tid, kp.d_pos = torch.cat([k[0] for k in d_keys]), torch.cat([k[1] for k in d_keys])
+        kp.tid, kp.pos, kp.flag, kp.span = (np.concatenate([h[i] for h in host]) for i in range(4))
+    else:
+        kp.d_tid = kp.d_pos = torch.empty(0, dtype=torch.int32, device=dev)
+        kp.tid = kp.pos = kp.span = np.empty(0, np.int32)
+        kp.flag = np.empty(0, np.uint16)
+    del d_keys, host, lens
+    clock.lap("join")
+    return kp
+
+
+Ordered = collections.namedtuple("Ordered", "order off_out d_order d_off_out pos_bits rank d_rank plan spans stream_bytes")
+
+
+def _order(dv, opened, kp, spanned, budget):
+    """order: ONE svx_record_sort over the keys (they go with it) -> Ordered(the records in output order, ``order`` / ``d_order`` [n];
+    their offsets in the output stream, ``off_out`` / ``d_off_out`` [n + 1]; ``pos_bits``; for a spanned run every input record's
+    ``rank`` / ``d_rank`` and the ``plan`` of :func:`plan_spans`, else None; the number of ``spans``, 1 in one piece; ``stream_bytes``:
+    the largest record buffer of the run)."""
+    from . import ingest_sort
+    torch, kernels, dev, n = dv.torch, dv.kernels, dv.dev, kp.n
+    pos_bits = ingest_sort.pos_bits_for(opened.head.lengths, int(kp.pos.max()) if n else -1)
+    if n:
+        d_order = kernels.record_sort(kp.d_tid, kp.d_pos, len(opened.head.references), pos_bits)
+        d_off_out = kernels.record_gather_offsets(kp.d_off_in, d_order)
+    else:                                                       # a header and no record: header blocks + the end-of-file marker
+        d_order, d_off_out = torch.empty(0, dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.int64, device=dev)
+    order = d_order.cpu().numpy().view(np.uint32).astype(np.int64)
+    off_out = d_off_out.cpu().numpy()
+    kp.d_tid = kp.d_pos = None
+    dv.clock.lap("sort")
+    if not spanned:
+        return Ordered(order, off_out, d_order, d_off_out, pos_bits, None, None, None, 1, int(kp.d_stream.numel()))
+    d_rank = kernels.record_invert(d_order)
+    rank = np.empty(n, np.int64)
+    rank[order] = np.arange(n, dtype=np.int64)
+    plan = plan_spans(off_out, budget)
+    dv.clock.lap("sort")
+    return Ordered(order, off_out, d_order, d_off_out, pos_bits, rank, d_rank, plan, len(plan), max((sp.size for sp in plan), default=0))
+
+
+def _pieces_in_core(dv, opened, kp, od, chunk_blocks, counts):
+    """pieces of a run in one piece: per chunk the records that touch it gathered from the resident stream -> (device buffer, the
+    chunk's first byte in it, its bytes).  The buffer goes before the next one is allocated: the caller drops its piece first."""
+    torch, lib, dev = dv.torch, dv.lib, dv.dev
+    st = dv.kernels._stream_ptr(dev)
+    for lo, hi in chunk_cuts(0, int(od.off_out[-1]), chunk_blocks * BLOCK):
+        r_lo, r_hi, base = (int(v) for v in records_touching(od.off_out, lo, hi))
+        d_rebased = od.d_off_out[r_lo:r_hi + 1] - base
+        d_rows = od.d_order[r_lo:r_hi].contiguous()
+        d_chunk = torch.empty(int(od.off_out[r_hi]) - base + 4, dtype=torch.uint8, device=dev)
+        _lib.check(lib.svx_record_gather_segments(kp.d_stream.data_ptr(), kp.d_off_in.data_ptr(), d_rows.data_ptr(), d_rebased.data_ptr(),
+                                                  d_chunk.data_ptr(), r_hi - r_lo, 1, st), "svx_record_gather_segments")
+        dv.clock.lap("gather")
+        yield d_chunk, lo - base, hi - lo
+        del d_chunk
+
+
+def _pieces_spanned(dv, opened, kp, od, chunk_blocks, counts):
+    """pieces of a run in spans: the record stream in pieces of the budget, each filled by a pass over the ranges that own its records
+    (``counts["span_range_reads"]`` of them in all) and then given chunk by chunk -> as :func:`_pieces_in_core`."""
+    torch, lib, kernels, dev, clock = dv
+    rec_base = np.concatenate([[0], np.cumsum(np.asarray(kp.range_records, np.int64))])
+    for sp in od.plan:
+        d_span = torch.empty(sp.size, dtype=torch.uint8, device=dev)
+        d_status = torch.zeros(1, dtype=torch.int32, device=dev)
+        need = span_ranges(od.rank, kp.range_records, sp.r_lo, sp.r_hi)
+        clock.lap("scatter")
+        for k, rng in zip(need, index.record_ranges(opened.path, opened.head, dev, clock, places=[kp.places[k] for k in need], extract=False,
+                                                    first=opened.first)):
+            counts["span_range_reads"] += 1
+            if rng.n_rec != kp.range_records[k]:
+                raise SortWriteError("%s changed while it was sorted: %d records complete in the range at file offset %d, %d did in the "
+                                     "first pass" % (opened.path, rng.n_rec, kp.places[k][0], kp.range_records[k]))
+            d_src_off = index.walk_offsets(lib, torch, kernels, dev, rng, closed=True)
+            clock.lap("walk")
+            kernels.record_scatter_segments(rng.d_raw, d_src_off, od.d_rank[int(rec_base[k]):int(rec_base[k + 1])], sp.r_lo, sp.r_hi,
+                                            od.d_off_out, sp.base, d_span, d_status)
+            clock.lap("scatter")
+            rng.d_raw = rng.d_starts = rng.d_base = None
+            del rng, d_src_off
+        if int(d_status.item()):
+            raise SortWriteError("%s changed while it was sorted: a record's length is not the one the first pass saw" % opened.path)
+        for lo, hi in chunk_cuts(sp.lo, sp.hi, chunk_blocks * BLOCK):
+            yield d_span, lo - sp.base, hi - lo
+        del d_span
+
+
+def _bai(opened, kp, od, written):
+    """index: the ``.bai`` of the written file, from the sorted fields and the writer's ledger -> its bytes."""
+    from .io import bai
+    voff = bai.virtual_offsets(written.dst, written.coff, (od.off_out + len(opened.header)).astype(np.uint64))
+    order = od.order
+    tid, pos, flag, span = kp.tid[order], kp.pos[order].astype(np.int64), kp.flag[order], kp.span[order].astype(np.int64)
+    try:
+        return bai.bai_bytes(len(opened.head.references), tid, pos, pos + np.maximum(span, 1), flag, voff[:-1], voff[1:])
+    except ValueError as exc:
+        raise SortWriteError("%s: %s" % (opened.path, exc)) from None
 
 
 def sort_bam(bam_path, out_path, device="cuda", range_bytes=None, chunk_bytes=None, stats=None, tables="fixed", memory_bytes=None):
@@ -234,243 +486,51 @@ def sort_bam(bam_path, out_path, device="cuda", range_bytes=None, chunk_bytes=No
     ranges, records, blocks, stored_blocks, dynamic_blocks, compressed_bytes, inflated_bytes, chunks, spans (1: in one piece),
     span_range_reads (ranges read again over all spans; 0 in one piece), range_records (the records every range of the pass
     completed), stream_bytes (the largest record buffer allocated) and the seconds per stage."""
-    import torch
-    from . import index, ingest_sort, kernels
-    from .io import bai
-    from .io.bam import read_bam_header
-    if not torch.cuda.is_available():
-        raise _lib.SvxError("sort_bam needs the GPU (svx_record_sort, svx_bgzf_deflate); there is no CPU fallback")
+    from . import ingest_sort, kernels
+    torch, lib, dev, clock = index.on_device("sort_bam needs the GPU (svx_record_sort, svx_bgzf_deflate)", device, STAGES)
     if tables not in TABLES:
         raise ValueError("tables: %r is none of %s" % (tables, ", ".join(TABLES)))
-    lib = _lib.load()
-    deflate = _encoder(kernels, tables)
-    dev = torch.device(device)
-    if dev.index is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
+    dv = _Dev(torch, lib, kernels, dev, clock)
     chunk_blocks = max(int(chunk_bytes or DEFAULT_CHUNK_BYTES) // BLOCK, 1)
-    clock = index._Clock(torch, dev, STAGES)
-    out_dir = os.path.dirname(os.path.abspath(out_path))
-    tmp_bam = tmp_bai = None
-    seen = room = 0                                             # inflated record bytes kept so far, and in all
     budget = None if memory_bytes is None else max(int(memory_bytes), 1)
+    opened, kp, writer, counts = None, KeyPass(), None, {"span_range_reads": 0}
     try:
-        try:
-            head = read_bam_header(bam_path)
-            block_at, entry, _n_ref = index.first_record(bam_path)
-            raw_head = _inflated_head(bam_path, block_at, entry)
-            header = sorted_header_bytes(raw_head)
-            room = inflated_size(bam_path) - len(raw_head)      # the records' bytes, by the members' ISIZE fields
-        except (ValueError, TypeError, OSError, zlib.error, struct.error) as exc:
-            raise SortWriteError("%s: %s" % (bam_path, exc)) from None
-        if room < 0:
-            raise SortWriteError("%s: its BGZF blocks hold fewer bytes than its header" % bam_path)
-        n_ref = len(head.references)
+        opened = _open(bam_path)
         with torch.cuda.device(dev):
             if budget is None:                                  # half of what is free: the rest is for a range, its inflate workspace, keys and chunks
                 budget = max(int(torch.cuda.mem_get_info(dev)[0]) // 2, 1)
-            spanned = room > budget                             # the records do not fit: no byte is kept in the pass, the output is filled in spans
-            # ---- pass: the record stream is allocated once, by the ISIZE sum (4 readable bytes behind it: the gather's aligned
-            #      loads), and every range's slice goes straight to its place in it
-            d_stream = None if spanned else torch.empty(room + 4, dtype=torch.uint8, device=dev)
-            stream_bytes = 0 if spanned else int(d_stream.numel())
-            host, d_keys, lens, ranges, range_records, places = [], [], [], 0, [], []
-            for rng in index.record_ranges(bam_path, head, dev, clock, range_bytes):
-                ranges += 1
-                range_records.append(int(rng.n_rec))
-                places.append(rng.place)
-                if rng.n_rec:
-                    tid, pos, flag, span, rec_off = index._index_fields(lib, torch, kernels, dev, rng, clock)
-                    first, last = int(rec_off[0]), int(rng.exit_off)
-                    if seen + last - first > room:
-                        raise SortWriteError("%s: more record bytes than its BGZF blocks' ISIZE fields add up to (%d)" % (bam_path, room))
-                    host.append((tid, pos, flag, span))
-                    lens.append(np.diff(np.append(rec_off, np.uint64(last)).astype(np.int64)))
-                    d_keys.append((rng.d_tid, rng.d_pos))
-                    if not spanned:
-                        d_stream[seen:seen + last - first].copy_(rng.d_raw[first:last])      # the records that complete in the range: contiguous there
-                    seen += last - first
-                rng.d_raw = rng.d_starts = rng.d_base = rng.d_cigar = rng.d_cig_off = rng.d_names = rng.d_name_off = None
-                del rng
-                clock.lap("keep")
-            n = int(sum(l.size for l in lens))
-            if n > 0xFFFFFFFF:
-                raise SortWriteError("%s: %d records -- svx_record_sort takes up to 2^32 - 1" % (bam_path, n))
-            # ---- join: CSR offsets and the keys of the one record stream
-            if not spanned:
-                d_stream[seen:] = 0
-            off_in = np.zeros(n + 1, np.int64)
-            if n:
-                off_in[1:] = np.cumsum(np.concatenate(lens))
-            d_off_in = torch.from_numpy(off_in).to(dev)
-            if n:
-                d_tid, d_pos = torch.cat([k[0] for k in d_keys]), torch.cat([k[1] for k in d_keys])
-                tid, pos, flag, span = (np.concatenate([h[i] for h in host]) for i in range(4))
-            else:
-                d_tid = d_pos = torch.empty(0, dtype=torch.int32, device=dev)
-                tid = pos = span = np.empty(0, np.int32)
-                flag = np.empty(0, np.uint16)
-            del d_keys, host, lens
-            clock.lap("join")
-            # ---- sort
-            pos_bits = ingest_sort.pos_bits_for(head.lengths, int(pos.max()) if n else -1)
-            if n:
-                d_order = kernels.record_sort(d_tid, d_pos, n_ref, pos_bits)
-                d_off_out = kernels.record_gather_offsets(d_off_in, d_order)
-            else:                                                   # a header and no record: header blocks + the end-of-file marker
-                d_order, d_off_out = torch.empty(0, dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.int64, device=dev)
-            order = d_order.cpu().numpy().view(np.uint32).astype(np.int64)
-            off_out = d_off_out.cpu().numpy()
-            del d_tid, d_pos
-            clock.lap("sort")
-            # ---- output
-            fd, tmp_bam = tempfile.mkstemp(prefix=os.path.basename(out_path) + ".", suffix=".tmp", dir=out_dir)
-            member_lens, block_bytes, n_stored, n_dynamic, chunks, span_range_reads = [], [], 0, 0, 0, 0
-            with os.fdopen(fd, "wb") as f:
-                # the header's blocks and, behind them, an empty block: the end-of-file marker, kept for the end
-                d_head = torch.from_numpy(np.frombuffer(header, np.uint8).copy()).to(dev)
-                n_head = (len(header) + BLOCK - 1) // BLOCK
-                h_off = np.minimum(np.arange(n_head + 2, dtype=np.int64) * BLOCK, len(header))
-                h_off[n_head + 1] = len(header)
-                slots, d_len, d_stored, d_dynamic = deflate(d_head, torch.from_numpy(h_off).to(dev))
-                clock.lap("deflate")
-                d_packed, d_file_off = kernels.bgzf_pack(slots, d_len, len(header) + kernels.BGZF_MEMBER_EXTRA * (n_head + 1))
-                clock.lap("pack")
-                m = d_len.cpu().numpy().astype(np.int64)
-                packed = _download(torch, d_packed, int(m.sum()))
-                eof = packed[int(m[:n_head].sum()):].tobytes()
-                n_stored += int(d_stored[:n_head].sum())
-                n_dynamic += int(d_dynamic[:n_head].sum())
-                clock.lap("download")
-                f.write(packed[:int(m[:n_head].sum())].tobytes())
-                member_lens.append(m[:n_head])
-                block_bytes.append(np.diff(h_off[:n_head + 1]))
-                clock.lap("write", False)
-                del slots, d_packed, d_head
-                total = int(off_out[n])
-                st = kernels._stream_ptr(dev)
-
-                def put(d_bytes, first, n_bytes):
-                    """The stream bytes d_bytes[first : first + n_bytes], whole blocks but for the stream's last: deflated, packed,
-                    downloaded and appended to the file."""
-                    nonlocal n_stored, n_dynamic
-                    slots, d_len, d_stored, d_dynamic, nb = _deflate_blocks(torch, deflate, dev, d_bytes, first, n_bytes)
-                    clock.lap("deflate")
-                    d_packed, d_file_off = kernels.bgzf_pack(slots, d_len, n_bytes + kernels.BGZF_MEMBER_EXTRA * nb)
-                    clock.lap("pack")
-                    m = d_len.cpu().numpy().astype(np.int64)
-                    if (m < 26).any():
-                        raise SortWriteError("%s: svx_bgzf_deflate refused a block" % bam_path)
-                    n_stored += int(d_stored.sum())
-                    n_dynamic += int(d_dynamic.sum())
-                    packed = _download(torch, d_packed, int(m.sum()))
-                    clock.lap("download")
-                    f.write(packed.tobytes())
-                    member_lens.append(m)
-                    block_bytes.append(np.diff(np.minimum(np.arange(nb + 1, dtype=np.int64) * BLOCK, n_bytes)))
-                    clock.lap("write", False)
-
-                if not spanned:
-                    for lo in range(0, total, chunk_blocks * BLOCK):
-                        hi = min(lo + chunk_blocks * BLOCK, total)
-                        chunks += 1
-                        # the records that touch stream bytes [lo, hi)
-                        r_lo = int(np.searchsorted(off_out, lo, "right")) - 1
-                        r_hi = int(np.searchsorted(off_out, hi, "left"))
-                        base = int(off_out[r_lo])
-                        d_rebased = d_off_out[r_lo:r_hi + 1] - base
-                        d_rows = d_order[r_lo:r_hi].contiguous()
-                        d_chunk = torch.empty(int(off_out[r_hi]) - base + 4, dtype=torch.uint8, device=dev)
-                        _lib.check(lib.svx_record_gather_segments(d_stream.data_ptr(), d_off_in.data_ptr(), d_rows.data_ptr(), d_rebased.data_ptr(),
-                                                                  d_chunk.data_ptr(), r_hi - r_lo, 1, st), "svx_record_gather_segments")
-                        clock.lap("gather")
-                        put(d_chunk, lo - base, hi - lo)
-                        del d_chunk
-                else:
-                    # ---- spans: the record stream in pieces of the budget, each filled by a pass over the ranges that own its records
-                    d_rank = kernels.record_invert(d_order)
-                    rank = np.empty(n, np.int64)
-                    rank[order] = np.arange(n, dtype=np.int64)
-                    rec_base = np.concatenate([[0], np.cumsum(np.asarray(range_records, np.int64))])
-                    plan = plan_spans(off_out, budget)
-                    clock.lap("sort")
-                    for sp in plan:
-                        d_span = torch.empty(sp.size, dtype=torch.uint8, device=dev)
-                        stream_bytes = max(stream_bytes, int(d_span.numel()))
-                        d_status = torch.zeros(1, dtype=torch.int32, device=dev)
-                        need = span_ranges(rank, range_records, sp.r_lo, sp.r_hi)
-                        clock.lap("scatter")
-                        for k, rng in zip(need, index.record_ranges(bam_path, head, dev, clock, places=[places[k] for k in need], extract=False)):
-                            span_range_reads += 1
-                            if rng.n_rec != range_records[k]:
-                                raise SortWriteError("%s changed while it was sorted: %d records complete in the range at file offset %d, %d did in the "
-                                                     "first pass" % (bam_path, rng.n_rec, places[k][0], range_records[k]))
-                            d_src_off = torch.empty(rng.n_rec + 1, dtype=torch.int64, device=dev)
-                            _lib.check(lib.svx_bam_walk_offsets(rng.d_raw.data_ptr(), rng.d_starts.data_ptr(), rng.n_starts, rng.d_base.data_ptr(),
-                                                                d_src_off.data_ptr(), st), "svx_bam_walk_offsets")
-                            d_src_off[rng.n_rec] = int(rng.exit_off)
-                            clock.lap("walk")
-                            kernels.record_scatter_segments(rng.d_raw, d_src_off, d_rank[int(rec_base[k]):int(rec_base[k + 1])], sp.r_lo, sp.r_hi,
-                                                            d_off_out, sp.base, d_span, d_status)
-                            clock.lap("scatter")
-                            rng.d_raw = rng.d_starts = rng.d_base = None
-                            del rng, d_src_off
-                        if int(d_status.item()):
-                            raise SortWriteError("%s changed while it was sorted: a record's length is not the one the first pass saw" % bam_path)
-                        step = min(chunk_blocks * BLOCK, sp.hi - sp.lo)
-                        for lo in range(sp.lo, sp.hi, step):
-                            hi = min(lo + step, sp.hi)
-                            chunks += 1
-                            put(d_span, lo - sp.base, hi - lo)
-                        del d_span
-                f.write(eof)
-            clock.lap("write", False)
-            # ---- index: every block's file offset and where its bytes lie in the inflated file, the end-of-file block included
-            member_lens = np.concatenate(member_lens + [np.asarray([len(eof)], np.int64)])
-            block_bytes = np.concatenate(block_bytes + [np.zeros(1, np.int64)])
-            coff = np.zeros(member_lens.size, np.uint64)
-            coff[1:] = np.cumsum(member_lens[:-1])
-            dst = np.zeros(block_bytes.size + 1, np.uint64)
-            dst[1:] = np.cumsum(block_bytes)
-            voff = bai.virtual_offsets(dst, coff, (off_out + len(header)).astype(np.uint64))
-            tid, pos, flag, span = tid[order], pos[order].astype(np.int64), flag[order], span[order].astype(np.int64)
-            try:
-                data = bai.bai_bytes(n_ref, tid, pos, pos + np.maximum(span, 1), flag, voff[:-1], voff[1:])
-            except ValueError as exc:
-                raise SortWriteError("%s: %s" % (bam_path, exc)) from None
-            fd, tmp_bai = tempfile.mkstemp(prefix=os.path.basename(out_path) + ".bai.", suffix=".tmp", dir=out_dir)
-            with os.fdopen(fd, "wb") as f:
-                f.write(data)
-            for t in (tmp_bam, tmp_bai):
-                os.chmod(t, 0o666 & ~index._umask())
-            os.replace(tmp_bam, out_path)
-            tmp_bam = None
-            try:
-                os.replace(tmp_bai, out_path + ".bai")
-            except OSError:                                         # the pair or nothing: no sorted file without its index
-                os.unlink(out_path)
-                raise
-            tmp_bai = None
+            spanned = opened.room > budget                      # the records do not fit: no byte is kept in the pass, the output is filled in spans
+            _key_pass(dv, opened, spanned, range_bytes, kp)
+            od = _order(dv, opened, kp, spanned, budget)
+            pieces = _pieces_spanned if spanned else _pieces_in_core
+            writer = BgzfWriter(out_path, DeviceEncode(dv, tables), clock, bam_path)
+            writer.put_header(torch.from_numpy(np.frombuffer(opened.header, np.uint8).copy()).to(dev), len(opened.header))
+            for piece in pieces(dv, opened, kp, od, chunk_blocks, counts):
+                writer.put(*piece)
+                del piece                                       # (the chunk's buffer goes before the generator allocates the next)
+            written = writer.finish()
+            commit_pair(writer.tmp, out_path, _bai(opened, kp, od, written))
             clock.lap("index", False)
     except index.IndexBuildError as exc:
         raise SortWriteError("%s: %s" % (bam_path, exc)) from None
     except torch.cuda.OutOfMemoryError as exc:
         raise SortWriteError("%s: the device has no room for the file's records -- %d inflated record bytes in all, %d seen so far, a budget of "
                              "%s bytes for them; a smaller one (--memory, SVX_SORT_MEMORY; sort_bam's memory_bytes) writes the file in more "
-                             "spans (%s)" % (bam_path, room, seen, budget, str(exc).split("\n")[0])) from None
+                             "spans (%s)" % (bam_path, opened.room, kp.seen, budget, str(exc).split("\n")[0])) from None
     except _lib.SvxError as exc:
         raise SortWriteError("%s: %s" % (bam_path, exc)) from None
     except OSError as exc:
         raise SortWriteError("%s: writing %s failed (%s)" % (bam_path, out_path, exc)) from None
     finally:
-        for t in (tmp_bam, tmp_bai):
-            if t is not None and os.path.exists(t):
-                os.unlink(t)
+        if writer is not None:
+            writer.discard()
     if stats is not None:
-        stats.update(ranges=ranges, records=n, blocks=int(member_lens.size), stored_blocks=n_stored, dynamic_blocks=n_dynamic, chunks=chunks,
-                     spans=len(plan) if spanned else 1, span_range_reads=span_range_reads, range_records=range_records, stream_bytes=stream_bytes,
-                     memory_bytes=budget,
-                     compressed_bytes=int(member_lens.sum()), inflated_bytes=int(dst[-1]), pos_bits=pos_bits,
-                     passes=len(ingest_sort.digit_plan(n_ref, pos_bits)), seconds={k: round(v, 6) for k, v in clock.times.items()})
+        stats.update(ranges=len(kp.range_records), records=kp.n, blocks=written.blocks, stored_blocks=written.stored_blocks,
+                     dynamic_blocks=written.dynamic_blocks, chunks=written.chunks, spans=od.spans, span_range_reads=counts["span_range_reads"],
+                     range_records=kp.range_records, stream_bytes=od.stream_bytes, memory_bytes=budget,
+                     compressed_bytes=written.compressed_bytes, inflated_bytes=written.inflated_bytes, pos_bits=od.pos_bits,
+                     passes=len(ingest_sort.digit_plan(len(opened.head.references), od.pos_bits)),
+                     seconds={k: round(v, 6) for k, v in clock.times.items()})
     return out_path
 
 

@@ -99,13 +99,13 @@ def test_the_record_stream_is_sized_from_the_isize_fields(tmp_path):
     """sort_bam allocates the record stream once, before the pass: the members' ISIZE sum is the file's inflated bytes, and the bytes
     in front of the first record are the header's."""
     import os
-    from svision_amd import sort
+    from svision_amd import index, sort
     from tests import baicases, helpers
     path = os.path.join(helpers.GOLDEN, "collect_small.bam")
     w = baicases.walk(path)
     assert sort.inflated_size(path) == len(w.stream)
     raw = open(path, "rb").read()
-    assert [(at, n) for at, n, _x, _i in sort._members(path)][-1] == (len(raw) - 28, 28)      # the end-of-file marker: 28 bytes, ISIZE 0
+    assert [(at, n) for at, n, _x, _i in index.bgzf_members(path)][-1] == (len(raw) - 28, 28)      # the end-of-file marker: 28 bytes, ISIZE 0
     for cut in (len(raw) - 29, len(raw) - 5, 7):                 # a member without its end, a footer cut, not even a header
         p = str(tmp_path / ("cut%d.bam" % cut))
         with open(p, "wb") as f:
