@@ -261,6 +261,18 @@ int svx_fc_bias_act_live(const float* d_x, const float* d_w_packed, const float*
 int svx_fc8_softmax_live(const float* d_x, const float* d_w, const float* d_bias, float* d_out, uint32_t n,
                          const uint32_t* d_live, void* stream);
 
+/* (ABI 420, additive) The tail of the memo's chain in one launch.  svx_fc_partial_live is the split-K half of
+ * svx_fc_bias_act_live: it leaves the svx_fc_splits(m, n, k) partial sums in d_ws as [split][m][n] and adds nothing up.
+ * With m > 64 and a live count its wave tile follows *d_live (32 x 32 up to 64 live rows, the tile of m beyond); the split count and every element's order of summation stay those of m, so the rows are the same bit for bit.
+ * svx_fc8_tail_live takes fc7's partial sums [splits][m][4096]: per live row relu(d_bias7 + part[0] + part[1] + ...) in that
+ * order (what svx_fc_bias_act_live writes to d_out), svx_fc8_softmax on it, and the packed row written to d_out[i] of every
+ * record i < n with d_inv[i] == row (svx_gather_rows; records whose d_inv is not below the live count keep what they held). */
+uint32_t svx_fc_splits(uint32_t m, uint32_t n, uint32_t k);
+int svx_fc_partial_live(const float* d_x, const float* d_w_packed, float* d_ws, uint32_t m, uint32_t n, uint32_t k,
+                        const uint32_t* d_live, void* stream);
+int svx_fc8_tail_live(const float* d_part, uint32_t splits, const float* d_bias7, const float* d_w, const float* d_bias,
+                      const uint32_t* d_inv, float* d_out, uint32_t m, uint32_t n, const uint32_t* d_live, void* stream);
+
 /* Pairwise signature distances of the clustering step, all partitions of a window in one launch (fp64).
  * Replaces the Python-callback pdist inside linkage(data, method="average", metric=span_position_distance)
  * (reference src/collection/cluster_signatures.py:114 with the metric of :132-141):

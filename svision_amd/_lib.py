@@ -49,6 +49,9 @@ SYMBOLS = {
                                                    ctypes.c_float, ctypes.c_float, ctypes.c_float, _vp, _vp, _vp, _vp]),
     "svx_fc_bias_act_live": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, ctypes.c_int, _vp, _vp]),
     "svx_fc8_softmax_live": (ctypes.c_int, [_vp, _vp, _vp, _vp, _u32, _vp, _vp]),
+    "svx_fc_splits": (_u32, [_u32, _u32, _u32]),                         # (ABI 420, additive: the fused tail of the memo's chain)
+    "svx_fc_partial_live": (ctypes.c_int, [_vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp]),
+    "svx_fc8_tail_live": (ctypes.c_int, [_vp, _u32, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp]),
     "svx_span_position_distance":(ctypes.c_int, [_vp, _vp, _vp, _u32, _vp, _u64, ctypes.c_double, _vp, _vp]),
     "svx_hash_seeds": (ctypes.c_int, [_vp, _vp, _u32, _vp, _vp, _vp, _u32, _u32, _u32, _vp]),
     "svx_hash_pack_hits": (ctypes.c_int, [_vp, _u32, _vp, _vp, _vp, _vp, _u64, _vp]),

@@ -476,14 +476,10 @@ namespace {
 // tf.nn.softmax and tf.argmax (first maximal index) as fetched at src/network/predict.py:209.  One
 // workgroup per image, one wave per class; packed row = [softmax x5, class, logits x5, pad].
 constexpr int FC8_IN = 4096, FC8_OUT = 5;
-__global__ __launch_bounds__(64 * FC8_OUT)
-void fc8_softmax_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
-                        float* __restrict__ out, const uint32_t* __restrict__ live)
+// the packed row of one image from its fc7 activations xv (global memory or LDS) to o; logit: FC8_OUT floats of LDS
+__device__ __forceinline__ void fc8_row(const float4* xv, const float* __restrict__ w, const float* __restrict__ bias, float* logit, float* o)
 {
-    __shared__ float logit[FC8_OUT];
-    const int img = blockIdx.x, cls = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (live && (uint32_t)img >= *live) return;              // a row behind the launch's distinct images
-    const float4* xv = reinterpret_cast<const float4*>(x + (size_t)img * FC8_IN);
+    const int cls = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const float4* wv = reinterpret_cast<const float4*>(w + (size_t)cls * FC8_IN);
     float acc = 0.0f;
 #pragma unroll 4
@@ -492,7 +488,7 @@ void fc8_softmax_kernel(const float* __restrict__ x, const float* __restrict__ w
         acc = fmaf(a.x, b.x, acc); acc = fmaf(a.y, b.y, acc); acc = fmaf(a.z, b.z, acc); acc = fmaf(a.w, b.w, acc);
     }
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    for (int d = 32; d > 0; d >>= 1) acc += __shfl_xor(acc, d, 64);
     if (lane == 0) logit[cls] = acc + bias[cls];
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -501,13 +497,63 @@ void fc8_softmax_kernel(const float* __restrict__ x, const float* __restrict__ w
         for (int j = 1; j < FC8_OUT; ++j) if (logit[j] > m) { m = logit[j]; best = j; }
         float e[FC8_OUT], s = 0.0f;
         for (int j = 0; j < FC8_OUT; ++j) { e[j] = expf(logit[j] - m); s += e[j]; }
-        float* o = out + (size_t)img * 12;
         for (int j = 0; j < FC8_OUT; ++j) { o[j] = e[j] / s; o[6 + j] = logit[j]; }
         o[5] = (float)best;
         o[11] = 0.0f;
     }
 }
+
+__global__ __launch_bounds__(64 * FC8_OUT)
+void fc8_softmax_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
+                        float* __restrict__ out, const uint32_t* __restrict__ live)
+{
+    __shared__ float logit[FC8_OUT];
+    const int img = blockIdx.x;
+    if (live && (uint32_t)img >= *live) return;              // a row behind the launch's distinct images
+    fc8_row(reinterpret_cast<const float4*>(x + (size_t)img * FC8_IN), w, bias, logit, out + (size_t)img * 12);
+}
+
+// The tail of the memo's chain in one launch: fc7's ordered reduce (relu(bias7 + part[0] + part[1] + ...), the sums of
+// fc_reduce_kernel in its order) into LDS while the row is loaded, fc8 + softmax on it, and the packed row written to every
+// record of the launch whose image it is (svx_gather_rows).  A workgroup per distinct image.
+__global__ __launch_bounds__(64 * FC8_OUT)
+void fc8_tail_kernel(const float* __restrict__ part, const float* __restrict__ bias7, const float* __restrict__ w, const float* __restrict__ bias,
+                     const uint32_t* __restrict__ inv, float* __restrict__ out, uint32_t m, uint32_t n, int splits, const uint32_t* __restrict__ live)
+{
+    __shared__ float4 xs[FC8_IN / 4];
+    __shared__ float logit[FC8_OUT];
+    __shared__ float packed[12];
+    const uint32_t img = blockIdx.x;
+    if (live && img >= *live) return;
+    const size_t mn4 = (size_t)m * (FC8_IN / 4);
+    const float4* p = reinterpret_cast<const float4*>(part) + (size_t)img * (FC8_IN / 4);
+    for (int i = threadIdx.x; i < FC8_IN / 4; i += 64 * FC8_OUT) {
+        float4 v = reinterpret_cast<const float4*>(bias7)[i];
+        for (int s = 0; s < splits; ++s) { const float4 q = p[(size_t)s * mn4 + i]; v.x += q.x; v.y += q.y; v.z += q.z; v.w += q.w; }
+        v.x = fmaxf(v.x, 0.0f); v.y = fmaxf(v.y, 0.0f); v.z = fmaxf(v.z, 0.0f); v.w = fmaxf(v.w, 0.0f);
+        xs[i] = v;
+    }
+    __syncthreads();
+    fc8_row(xs, w, bias, logit, packed);
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < n; i += 64 * FC8_OUT)
+        if (inv[i] == img) {
+#pragma unroll
+            for (int e = 0; e < 12; ++e) out[(size_t)i * 12 + e] = packed[e];
+        }
+}
 }  // namespace
+
+extern "C" int svx_fc8_tail_live(const float* d_part, uint32_t splits, const float* d_bias7, const float* d_w, const float* d_bias,
+                                 const uint32_t* d_inv, float* d_out, uint32_t m, uint32_t n, const uint32_t* d_live, void* stream)
+{
+    if (m == 0 || n == 0) return SVX_OK;
+    if (!d_part || !d_bias7 || !d_w || !d_bias || !d_inv || !d_out || splits == 0) return SVX_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(d_part) | reinterpret_cast<uintptr_t>(d_bias7) | reinterpret_cast<uintptr_t>(d_w)) & 15u) return SVX_EINVAL;
+    hipLaunchKernelGGL(fc8_tail_kernel, dim3(m), dim3(64 * FC8_OUT), 0, static_cast<hipStream_t>(stream), d_part, d_bias7, d_w, d_bias, d_inv, d_out,
+                       m, n, (int)splits, d_live);
+    return hipGetLastError() == hipSuccess ? SVX_OK : SVX_ELAUNCH;
+}
 
 extern "C" int svx_fc8_softmax_live(const float* d_x, const float* d_w, const float* d_bias, float* d_out, uint32_t n,
                                     const uint32_t* d_live, void* stream)

@@ -12,6 +12,8 @@
 //                   order: the first equal key is the record's first occurrence.
 //   compact_kernel: one workgroup; an ordered prefix sum over the first-occurrence flags (1024 records per step) gives
 //                   every distinct image its compact row, then every record the compact row of its first occurrence.
+//   dedup_small_kernel: both steps in one workgroup of the launch's size for up to 1,024 records -- every launch of the
+//                   pipeline (64 .. 256 records: 1 .. 4 waves, which find room on a CU that a workgroup of 16 waits for).
 // No atomics: the output is the same in every run.
 #include "svx_raster_common.hpp"
 
@@ -44,7 +46,8 @@ void first_kernel(const int32_t* __restrict__ records, uint32_t n, uint32_t* __r
     if (i < n) first[i] = f;
 }
 
-// first[] comes in as the first occurrence of every record and leaves as its compact row (d_inv)
+// first[] comes in as the first occurrence of every record and leaves as its compact row (d_inv).  The block is the launch
+// rounded up to whole waves (at most COMPACT_BLOCK threads): a workgroup of 16 waves waits for a CU with room for all of them.
 __global__ __launch_bounds__(COMPACT_BLOCK)
 void compact_kernel(const int32_t* __restrict__ records, uint32_t n, uint32_t* __restrict__ inv, uint32_t* __restrict__ row,
                     int32_t* __restrict__ unique, uint32_t* __restrict__ live)
@@ -52,9 +55,10 @@ void compact_kernel(const int32_t* __restrict__ records, uint32_t n, uint32_t* _
     __shared__ uint32_t wave_sum[COMPACT_BLOCK / WAVE];
     __shared__ uint32_t s_base;
     const int t = threadIdx.x, lane = t & (WAVE - 1), wv = t / WAVE;
+    const uint32_t block = blockDim.x;
     if (t == 0) s_base = 0;
     __syncthreads();
-    for (uint32_t c0 = 0; c0 < n; c0 += COMPACT_BLOCK) {
+    for (uint32_t c0 = 0; c0 < n; c0 += block) {
         const uint32_t i = c0 + t;
         const bool is_first = i < n && inv[i] == i;
         const unsigned long long ball = __ballot(is_first);
@@ -70,14 +74,58 @@ void compact_kernel(const int32_t* __restrict__ records, uint32_t n, uint32_t* _
             for (int e = 0; e < 12; ++e) unique[(size_t)c * 12 + e] = records[(size_t)i * 12 + e];
         }
         __syncthreads();                                     // every lane has read s_base and wave_sum
-        if (t == 0) { uint32_t s = s_base; for (int w = 0; w < COMPACT_BLOCK / WAVE; ++w) s += wave_sum[w]; s_base = s; }
+        if (t == 0) { uint32_t s = s_base; for (uint32_t w = 0; w < block / WAVE; ++w) s += wave_sum[w]; s_base = s; }
         __syncthreads();
     }
     const uint32_t n_live = s_base;
     // rows behind the distinct images repeat the first record: a consumer without the live count computes a valid image there
-    for (uint32_t e = n_live * 12 + t; e < n * 12; e += COMPACT_BLOCK) unique[e] = records[e % 12];
-    for (uint32_t i = t; i < n; i += COMPACT_BLOCK) inv[i] = row[inv[i]];
+    for (uint32_t e = n_live * 12 + t; e < n * 12; e += block) unique[e] = records[e % 12];
+    for (uint32_t i = t; i < n; i += block) inv[i] = row[inv[i]];
     if (t == 0) *live = n_live;
+}
+
+// Both steps in one workgroup for a launch of at most COMPACT_BLOCK records (every launch of the pipeline): a lane per record
+// keys it, walks the keys in front of it in ascending order, and the ordered prefix sum over the first-occurrence flags gives
+// the compact rows -- the same outputs as first_kernel + compact_kernel, without the second launch and its scratch.
+__global__ __launch_bounds__(COMPACT_BLOCK)
+void dedup_small_kernel(const int32_t* __restrict__ records, uint32_t n, uint32_t* __restrict__ inv, int32_t* __restrict__ unique,
+                        uint32_t* __restrict__ live, uint4* __restrict__ keys)
+{
+    constexpr uint32_t SCAN = 8;                             // divides the block: a turn never reads behind it
+    __shared__ uint4 tile[COMPACT_BLOCK];
+    __shared__ uint32_t row[COMPACT_BLOCK];
+    __shared__ uint32_t wave_sum[COMPACT_BLOCK / WAVE];
+    const uint32_t i = threadIdx.x, lane = i & (WAVE - 1), wv = i / WAVE, block = blockDim.x;
+    const uint4 mine = i < n ? svx_raster::image_key(records + (size_t)i * 12) : uint4{0, 0, 0, 0};
+    if (keys && i < n) keys[i] = mine;
+    tile[i] = mine;
+    __syncthreads();
+    uint32_t f = i;
+    if (i < n)
+        for (uint32_t j0 = 0; j0 < i && f == i; j0 += SCAN) {  // SCAN keys per turn, their loads in flight together: the first equal one
+            uint32_t hit = 0;
+#pragma unroll
+            for (uint32_t u = 0; u < SCAN; ++u)
+                if (key_eq(tile[j0 + u], mine) && j0 + u < i) hit |= 1u << u;
+            if (hit) f = j0 + __ffs(hit) - 1;
+        }
+    const bool is_first = i < n && f == i;
+    const unsigned long long ball = __ballot(is_first);
+    const uint32_t below = __popcll(ball & ((1ull << lane) - 1ull));
+    if (lane == 0) wave_sum[wv] = __popcll(ball);
+    __syncthreads();
+    uint32_t before = 0, n_live = 0;
+    for (uint32_t w = 0; w < block / WAVE; ++w) { if (w == wv) before = n_live; n_live += wave_sum[w]; }
+    if (is_first) {
+        const uint32_t c = before + below;
+        row[i] = c;
+#pragma unroll
+        for (int e = 0; e < 12; ++e) unique[(size_t)c * 12 + e] = records[(size_t)i * 12 + e];
+    }
+    __syncthreads();
+    if (i < n) inv[i] = row[f];
+    for (uint32_t e = n_live * 12 + i; e < n * 12; e += block) unique[e] = records[e % 12];
+    if (i == 0) *live = n_live;
 }
 
 __global__ __launch_bounds__(256)
@@ -99,9 +147,14 @@ extern "C" int svx_image_dedup(const int32_t* d_records, uint32_t n, int32_t* d_
     if (n == 0) return hipMemsetAsync(d_live, 0, sizeof(uint32_t), st) == hipSuccess ? SVX_OK : SVX_ELAUNCH;
     if (!d_records || !d_unique || !d_inv || !d_ws || n > (1u << 26)) return SVX_EINVAL;
     if (reinterpret_cast<uintptr_t>(d_keys) & 15u) return SVX_EINVAL;
+    const uint32_t block = n >= COMPACT_BLOCK ? COMPACT_BLOCK : (n + WAVE - 1) / WAVE * WAVE;
+    if (n <= COMPACT_BLOCK) {
+        hipLaunchKernelGGL(dedup_small_kernel, dim3(1), dim3(block), 0, st, d_records, n, d_inv, d_unique, d_live, reinterpret_cast<uint4*>(d_keys));
+        return hipGetLastError() == hipSuccess ? SVX_OK : SVX_ELAUNCH;
+    }
     hipLaunchKernelGGL(first_kernel, dim3((n + KEY_BLOCK - 1) / KEY_BLOCK), dim3(KEY_BLOCK), 0, st, d_records, n, d_inv,
                        reinterpret_cast<uint4*>(d_keys));
-    hipLaunchKernelGGL(compact_kernel, dim3(1), dim3(COMPACT_BLOCK), 0, st, d_records, n, d_inv, d_ws, d_unique, d_live);
+    hipLaunchKernelGGL(compact_kernel, dim3(1), dim3(block), 0, st, d_records, n, d_inv, d_ws, d_unique, d_live);
     return hipGetLastError() == hipSuccess ? SVX_OK : SVX_ELAUNCH;
 }
 

@@ -32,6 +32,9 @@ __device__ __forceinline__ v4f buf_load4(__amdgpu_buffer_rsrc_t rsrc, unsigned v
 #ifndef SVX_FC_RING_A
 #define SVX_FC_RING_A 6
 #endif
+#ifndef SVX_FC_RING_NARROW                 // the weight ring of the narrow tiles of fc_splitk_live_kernel: 12 (the registers the smaller
+#define SVX_FC_RING_NARROW 6               // accumulators free) measured the same as 6 (profiles/fc_live.txt): the tiles are bound by MFMA issue
+#endif
 
 template <int U> struct StageIndex { static constexpr int value = U; };
 
@@ -54,19 +57,11 @@ __device__ __forceinline__ void svx_tail_stages(F& f, int left)
 // live: NULL, or the number of leading rows to compute (device); the tiling and the split count stay those of M
 struct FcArgs { const float* x; const float* w; float* part; int M, N, K, splits; const uint32_t* live; };
 
-template <int NA, int NB>
-__global__ __launch_bounds__(THREADS, 2)
-void fc_splitk_kernel(const FcArgs a)
+// One wave tile: 32 NA neurons (tile nt) x 32 NB images (tile mt) over the k range of split s, RA octets of weights in flight.
+// Every output element is one MFMA chain over its split's octets in ascending order whatever NA, NB and RA.
+template <int NA, int NB, int RA>
+__device__ __forceinline__ void fc_tile(const FcArgs& a, int nt, int s, int mt, int m_live)
 {
-    SVX_SHADOW_ROOM();
-    const int n_tiles = a.N / (32 * NA), m_tiles = (a.M + 32 * NB - 1) / (32 * NB);
-    const int total = m_tiles * a.splits * n_tiles;                 // neuron tile fastest: neighbours share the x slice
-    const int wt = blockIdx.x * WAVES + (threadIdx.x >> 6);
-    if (wt >= total) return;
-    const int nt = wt % n_tiles, rest = wt / n_tiles;
-    const int s = rest % a.splits, mt = rest / a.splits;
-    const int m_live = a.live ? min((int)*a.live, a.M) : a.M;
-    if (mt * 32 * NB >= m_live) return;                              // a tile behind the launch's distinct images
     const int lane = threadIdx.x & 63, hi = lane >> 5, lo = lane & 31;
     const int KQ = a.K / 8;
     const int q0 = (int)((long long)KQ * s / a.splits), q1 = (int)((long long)KQ * (s + 1) / a.splits);
@@ -88,7 +83,7 @@ void fc_splitk_kernel(const FcArgs a)
     // flight; at the two octets of the activations' ring ~1000 waves held 2 MB in flight and the stream ran at 3 TB/s),
     // the activations come out of L2 (RB - 1 = 2 octets ahead, as in svx_conv.hip).  RA is a multiple of RB: the body is
     // unrolled RA stages so that every ring slot is a compile-time register.
-    constexpr int RA = SVX_FC_RING_A, RB = 3, MF = 4 * NA * NB, L = NA + NB;
+    constexpr int RB = 3, MF = 4 * NA * NB, L = NA + NB;
     static_assert(RA % RB == 0, "weight ring must be a multiple of the activation ring");
     v4f ra[RA][NA], rb[RB][NB];
     unsigned soff_a = 0, soff_b = 0;                      // of the NEXT octet each ring loads
@@ -144,6 +139,55 @@ void fc_splitk_kernel(const FcArgs a)
         }
 }
 
+template <int NA, int NB>
+__global__ __launch_bounds__(THREADS, 2)
+void fc_splitk_kernel(const FcArgs a)
+{
+    SVX_SHADOW_ROOM();
+    const int n_tiles = a.N / (32 * NA), m_tiles = (a.M + 32 * NB - 1) / (32 * NB);
+    const int total = m_tiles * a.splits * n_tiles;                 // neuron tile fastest: neighbours share the x slice
+    const int wt = blockIdx.x * WAVES + (threadIdx.x >> 6);
+    if (wt >= total) return;
+    const int nt = wt % n_tiles, rest = wt / n_tiles;
+    const int s = rest % a.splits, mt = rest / a.splits;
+    const int m_live = a.live ? min((int)*a.live, a.M) : a.M;
+    if (mt * 32 * NB >= m_live) return;                              // a tile behind the launch's distinct images
+    fc_tile<NA, NB, SVX_FC_RING_A>(a, nt, s, mt, m_live);
+}
+
+// A launch of more than 64 rows with a live count (the image memo: ~40 distinct images in a launch of 256).  The wide tile above
+// leaves such a launch one M tile of waves, a quarter of the SIMDs, each bound by the MFMAs of a tile that is mostly dead rows.
+// Here the tile follows *live (wave-uniform): 32 x 32 in the narrow regimes -- a quarter of the wide tile's MFMAs per weight byte --
+// and the wide tile beyond 64 live rows.  Up to 32 live rows a (neuron tile, split) item is one wave, item = block + wave * blocks:
+// the live waves are dealt over all workgroups (CUs) before a workgroup gets a second one.  From 33 to 64 an item is two waves of
+// one workgroup, a half of the rows each: the second reads the weights behind the first out of the cache, and every SIMD has a
+// wave (one 32 x 64 wave per item measured 110 us for fc6 + fc7 at M = 256, the pair 88: profiles/fc_live.txt).  The split count
+// and part[s][m][n] stay those of M.
+template <int NA>
+__global__ __launch_bounds__(THREADS, 2)
+void fc_splitk_live_kernel(const FcArgs a)
+{
+    SVX_SHADOW_ROOM();
+    const int m_live = min((int)*a.live, a.M);
+    const int wv = threadIdx.x >> 6;
+    if (m_live > 64) {
+        const int n_tiles = a.N / (32 * NA), m_tiles = (a.M + 63) / 64;
+        const int wt = blockIdx.x * WAVES + wv;
+        if (wt >= m_tiles * a.splits * n_tiles) return;
+        const int nt = wt % n_tiles, rest = wt / n_tiles;
+        const int s = rest % a.splits, mt = rest / a.splits;
+        if (mt * 64 >= m_live) return;
+        fc_tile<NA, 2, SVX_FC_RING_A>(a, nt, s, mt, m_live);
+        return;
+    }
+    if (m_live == 0) return;
+    const int n_tiles = a.N / 32;
+    const int pair = m_live > 32 ? 1 : 0;
+    const int item = (int)(blockIdx.x + (wv >> pair) * gridDim.x);
+    if (item >= n_tiles * a.splits) return;
+    fc_tile<1, 1, SVX_FC_RING_NARROW>(a, item % n_tiles, item / n_tiles, pair ? (wv & 1) : 0, m_live);
+}
+
 // out[m][n] = act(bias[n] + part[0][m][n] + part[1][m][n] + ...): fixed order, one float4 per lane
 __global__ __launch_bounds__(THREADS)
 void fc_reduce_kernel(const float* __restrict__ part, const float* __restrict__ bias, float* __restrict__ out, int MN4, int N4, int splits, int relu,
@@ -190,12 +234,17 @@ extern "C" size_t svx_fc_ws_bytes(uint32_t m, uint32_t n, uint32_t k)
     return (size_t)fc_splits(m, n, k) * m * n * sizeof(float);
 }
 
-extern "C" int svx_fc_bias_act_live(const float* d_x, const float* d_w_packed, const float* d_bias, float* d_out, float* d_ws,
-                                    uint32_t m, uint32_t n, uint32_t k, int relu, const uint32_t* d_live, void* stream)
+extern "C" uint32_t svx_fc_splits(uint32_t m, uint32_t n, uint32_t k)
+{
+    return (uint32_t)fc_splits(m, n, k);
+}
+
+extern "C" int svx_fc_partial_live(const float* d_x, const float* d_w_packed, float* d_ws, uint32_t m, uint32_t n, uint32_t k,
+                                   const uint32_t* d_live, void* stream)
 {
     if (m == 0) return SVX_OK;
-    if (!d_x || !d_w_packed || !d_bias || !d_out || !d_ws || n % 32 || k % 8 || k < 24 * 8) return SVX_EINVAL;
-    for (const void* p : {(const void*)d_x, (const void*)d_w_packed, (const void*)d_bias, (const void*)d_out, (const void*)d_ws})
+    if (!d_x || !d_w_packed || !d_ws || n % 32 || k % 8 || k < 24 * 8) return SVX_EINVAL;
+    for (const void* p : {(const void*)d_x, (const void*)d_w_packed, (const void*)d_ws})
         if (reinterpret_cast<uintptr_t>(p) & 15u) return SVX_EINVAL;
     if ((uint64_t)n * k * 4 > 0x7fffffffull || (uint64_t)m * k * 4 > 0x7fffffffull) return SVX_EINVAL;
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -203,12 +252,31 @@ extern "C" int svx_fc_bias_act_live(const float* d_x, const float* d_w_packed, c
     const int m_tiles = (int)((m + 63) / 64);
     const int na = fc_na(m, n);
     const int waves = m_tiles * a.splits * (int)(n / (32 * na));
+    if (d_live && m > 64) {
+        // the tile is chosen on the device from *d_live: the grid holds the wide regime's waves and, two waves each, the narrow items
+        const int items = a.splits * (int)(n / 32);
+        const dim3 grid((unsigned)(((waves > 2 * items ? waves : 2 * items) + WAVES - 1) / WAVES));
+        if (na == 2) hipLaunchKernelGGL((fc_splitk_live_kernel<2>), grid, dim3(THREADS), 0, st, a);
+        else         hipLaunchKernelGGL((fc_splitk_live_kernel<1>), grid, dim3(THREADS), 0, st, a);
+        return hipGetLastError() == hipSuccess ? SVX_OK : SVX_ELAUNCH;
+    }
     const dim3 grid((unsigned)((waves + WAVES - 1) / WAVES));
     if (na == 2)      hipLaunchKernelGGL((fc_splitk_kernel<2, 2>), grid, dim3(THREADS), 0, st, a);
     else if (m <= 32) hipLaunchKernelGGL((fc_splitk_kernel<1, 1>), grid, dim3(THREADS), 0, st, a);
     else              hipLaunchKernelGGL((fc_splitk_kernel<1, 2>), grid, dim3(THREADS), 0, st, a);
+    return hipGetLastError() == hipSuccess ? SVX_OK : SVX_ELAUNCH;
+}
+
+extern "C" int svx_fc_bias_act_live(const float* d_x, const float* d_w_packed, const float* d_bias, float* d_out, float* d_ws,
+                                    uint32_t m, uint32_t n, uint32_t k, int relu, const uint32_t* d_live, void* stream)
+{
+    if (m == 0) return SVX_OK;
+    if (!d_bias || !d_out || (reinterpret_cast<uintptr_t>(d_bias) & 15u) || (reinterpret_cast<uintptr_t>(d_out) & 15u)) return SVX_EINVAL;
+    const int rc = svx_fc_partial_live(d_x, d_w_packed, d_ws, m, n, k, d_live, stream);
+    if (rc != SVX_OK) return rc;
     const int mn4 = (int)((uint64_t)m * n / 4);
-    hipLaunchKernelGGL(fc_reduce_kernel, dim3((mn4 + THREADS - 1) / THREADS), dim3(THREADS), 0, st, d_ws, d_bias, d_out, mn4, (int)(n / 4), a.splits, relu, d_live);
+    hipLaunchKernelGGL(fc_reduce_kernel, dim3((mn4 + THREADS - 1) / THREADS), dim3(THREADS), 0, static_cast<hipStream_t>(stream), d_ws, d_bias, d_out,
+                       mn4, (int)(n / 4), fc_splits(m, n, k), relu, d_live);
     return hipGetLastError() == hipSuccess ? SVX_OK : SVX_ELAUNCH;
 }
 

@@ -362,6 +362,44 @@ def fc8_softmax(x, w_out_in, bias, out=None, live=None):
     return out
 
 
+def fc_partial(x, w_packed, live=None):
+    """The split-K half of :func:`fc_bias_act`: x float32 [m,k], w_packed [n/32,k/8,32,8] -> the partial sums float32
+    [splits,m,n] (rows >= live are skipped), to be added up in order by :func:`fc8_tail`.  See include/svx.h svx_fc_partial_live."""
+    lib = _lib.load()
+    for t, nm in ((x, "x"), (w_packed, "w_packed")):
+        _require_cuda(t, nm)
+    if x.dtype != torch.float32 or x.dim() != 2 or w_packed.dim() != 4 or w_packed.shape[2:] != (32, 8) or w_packed.shape[1] * 8 != x.shape[1]:
+        raise _lib.SvxError("x must be float32 [m,k] and w packed [n/32,k/8,32,8]")
+    m, k = x.shape
+    n = w_packed.shape[0] * 32
+    part = torch.empty((lib.svx_fc_splits(m, n, k), m, n), dtype=torch.float32, device=x.device)
+    rc = lib.svx_fc_partial_live(x.data_ptr(), w_packed.data_ptr(), part.data_ptr(), m, n, k, _check_live(live), _stream_ptr(x.device))
+    _lib.check(rc, "svx_fc_partial")
+    return part
+
+
+def fc8_tail(part, bias7, w_out_in, bias, inv, out=None, live=None):
+    """part float32 [splits,m,4096] (fc7's partial sums, :func:`fc_partial`), bias7 [4096], w [5,4096], bias [5], inv int32 [n]
+    -> packed float32 [n,12]: relu(bias7 + the splits in order), fc8 + softmax per live row, and each row written to the
+    records whose image it is -- fc7's reduction, :func:`fc8_softmax` and :func:`gather_rows` in one launch.  See include/svx.h
+    svx_fc8_tail_live."""
+    lib = _lib.load()
+    for t, nm in ((part, "part"), (bias7, "bias7"), (w_out_in, "w"), (bias, "bias"), (inv, "inv")):
+        _require_cuda(t, nm)
+    if part.dtype != torch.float32 or part.dim() != 3 or part.shape[2] != 4096 or not part.is_contiguous() or bias7.numel() != 4096 \
+            or tuple(w_out_in.shape) != (5, 4096) or inv.dtype != torch.int32 or inv.dim() != 1:
+        raise _lib.SvxError("part must be a contiguous float32 [splits,m,4096], bias7 [4096], w float32 [5,4096] and inv int32 [n]")
+    splits, m, n = part.shape[0], part.shape[1], inv.shape[0]
+    if out is None:
+        out = torch.empty((n, 12), dtype=torch.float32, device=part.device)
+    elif tuple(out.shape) != (n, 12) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise _lib.SvxError("out must be a contiguous float32 [n,12] tensor")
+    rc = lib.svx_fc8_tail_live(part.data_ptr(), splits, bias7.data_ptr(), w_out_in.data_ptr(), bias.data_ptr(), inv.data_ptr(),
+                               out.data_ptr(), m, n, _check_live(live), _stream_ptr(part.device))
+    _lib.check(rc, "svx_fc8_tail")
+    return out
+
+
 def span_position_distance(starts, ends, part_off, normalizer=1000.0):
     """Condensed span_position_distance matrices of several partitions in one launch.
     starts / ends: float64 device tensors [N] (partitions concatenated); part_off: int sequence [P+1].

@@ -16,6 +16,7 @@ layer are one kernel.
     svx_fc_bias_act           fc6 / fc7 (+ bias + relu) as a weight stream feeding fp32 MFMAs, split-K, ordered reduce
     svx_fc8_softmax           fc8 + softmax + argmax + packing
     svx_gather_rows           the packed rows of the distinct images back to one row per record
+    svx_fc8_tail_live         with the memo: fc7's ordered reduce + fc8 + softmax + that gather in one launch (after svx_fc_partial_live)
 
 With the image memo (default; ``memo=False`` or SVX_IMAGE_MEMO=0 turns it off) every stage after svx_image_dedup is
 the *_live variant of its kernel: a launch keeps its size (a captured graph is fixed) and the rows behind the distinct
@@ -213,11 +214,12 @@ class AlexNet(torch.nn.Module):
         # fc6 / fc7 keep the split-K grouping of the launch size B (a function of m): every row sums in the order it
         # would without the memo
         x = kernels.fc_bias_act(x, self.fc6_w, self.fc6_b, relu=True, live=live)
-        x = kernels.fc_bias_act(x, self.fc7_w, self.fc7_b, relu=True, live=live)
         if live is None:
+            x = kernels.fc_bias_act(x, self.fc7_w, self.fc7_b, relu=True)
             return kernels.fc8_softmax(x, self.fc8_w, self.fc8_b, out=out)
-        packed = kernels.fc8_softmax(x, self.fc8_w, self.fc8_b, live=live)
-        return kernels.gather_rows(packed, inv, out=out)
+        # the memo's tail in one launch: fc7's ordered reduce, fc8 + softmax and the rows back to their records
+        part = kernels.fc_partial(x, self.fc7_w, live=live)
+        return kernels.fc8_tail(part, self.fc7_b, self.fc8_w, self.fc8_b, inv, out=out, live=live)
 
     @torch.no_grad()
     def predict_records(self, records):
