@@ -547,6 +547,50 @@ int            svx_bgzf_deflate_dyn(const uint8_t* d_in, const uint64_t* d_in_of
                                     uint32_t* d_btype, void* d_ws, uint64_t ws_bytes, void* stream);
 int            svx_bgzf_pack(const uint8_t* d_slots, const uint32_t* d_member_len, uint32_t n_blocks, uint64_t* d_file_off, uint8_t* d_out,
                              uint64_t out_bytes, void* stream);
+/* SAM text -> BAM records (svx_sam.hip over svx_sam_core.hpp; ABI 420, additive): the front end of svision_amd/sort.py for an
+ * aligner's text output.  The rules are listed in svision_amd/io/sam.py, which encodes the same bytes on the host.  d_text: a chunk of
+ * n_bytes of alignment lines that ends at a line boundary (the last line may lack its newline), with SVX_SAM_SLACK readable bytes
+ * behind it.
+ *   svx_sam_lines    d_line_off [n_lines + 1]: the offset of every line start and n_bytes behind them (line i = the bytes
+ *                    [d_line_off[i], d_line_off[i + 1]) without its newline), *d_n_lines = their number.  A count launch, a prefix of
+ *                    the tiles' counts in one workgroup, an emit launch; no atomics.  cap = the entries of d_line_off (>= 1): entries
+ *                    beyond it are dropped, *d_n_lines + 1 > cap tells.  d_ws: svx_sam_lines_ws_bytes(n_bytes) bytes, 8-byte aligned
+ *   svx_sam_measure  a wave a line: d_len [i] = the bytes of the line's BAM record including block_size, or a negative code;
+ *                    d_tid d_pos d_flag d_span [i] = the sort key and the index's fields (where d_len is an error code: unspecified).
+ *                    SVX_SAM_HOST: the line is valid as far as the kernel looked and is not taken by it -- more than 65,535 CIGAR
+ *                    operations, or an f / B:f value outside the exact fast path (at most 15 significant digits and a decimal
+ *                    exponent of magnitude <= 22: one IEEE double multiply or divide, then the cast), inf and nan among them.
+ *                    SVX_SAM_E_*: FIELDS fewer than 11 fields or an empty line, NUMBER a numeric field or array value that is no
+ *                    number or out of its range, NAME a read name of 0 or more than 254 bytes, RNAME a reference the table does not
+ *                    hold, CIGAR, QUAL another length than SEQ, TAG a malformed tag, RANGE an i tag outside [-2^31, 2^32), HEADER a
+ *                    line that starts with '@'.  The reference table: d_ref_hash [n_ref] the names' FNV-1a hashes ascending,
+ *                    d_ref_tid [n_ref] their tids in that order, d_ref_name_off [n_ref + 1] / d_ref_names the names' bytes by tid;
+ *                    the kernel compares the bytes
+ *   svx_sam_encode   a wave a line: the record of every line with d_len [i] >= 0 written to d_out + (d_off[i] - out_base), exactly
+ *                    d_len [i] bytes -- the resident stream (out_base 0) or a chunk-local buffer.  A line that no longer measures
+ *                    d_len [i] is not written: *d_status = 1 (a plain store; zero it before the call).  Lines with d_len [i] < 0 are
+ *                    skipped
+ * Every loop is bounded by the line table, reads stay inside the chunk and its slack, no kernel waits for another. */
+#define SVX_SAM_SLACK 64u
+#define SVX_SAM_HOST (-1)
+#define SVX_SAM_E_FIELDS (-2)
+#define SVX_SAM_E_NUMBER (-3)
+#define SVX_SAM_E_NAME (-4)
+#define SVX_SAM_E_RNAME (-5)
+#define SVX_SAM_E_CIGAR (-6)
+#define SVX_SAM_E_QUAL (-7)
+#define SVX_SAM_E_TAG (-8)
+#define SVX_SAM_E_RANGE (-9)
+#define SVX_SAM_E_HEADER (-10)
+size_t         svx_sam_lines_ws_bytes(uint64_t n_bytes);
+int            svx_sam_lines(const uint8_t* d_text, uint64_t n_bytes, int64_t* d_line_off, uint64_t cap, uint64_t* d_n_lines, void* d_ws,
+                             uint64_t ws_bytes, void* stream);
+int            svx_sam_measure(const uint8_t* d_text, const int64_t* d_line_off, uint32_t n_lines, const uint32_t* d_ref_hash,
+                               const int32_t* d_ref_tid, const uint32_t* d_ref_name_off, const uint8_t* d_ref_names, uint32_t n_ref,
+                               int32_t* d_len, int32_t* d_tid, int32_t* d_pos, int32_t* d_flag, int32_t* d_span, void* stream);
+int            svx_sam_encode(const uint8_t* d_text, const int64_t* d_line_off, uint32_t n_lines, const uint32_t* d_ref_hash,
+                              const int32_t* d_ref_tid, const uint32_t* d_ref_name_off, const uint8_t* d_ref_names, uint32_t n_ref,
+                              const int32_t* d_len, const int64_t* d_off, int64_t out_base, uint8_t* d_out, int32_t* d_status, void* stream);
 /* host helpers of the device-side ingestion: parallel positional read into caller memory; the whole BGZF blocks of a
  * buffer (payload offset / size, ISIZE, file offset; -> their number or -1, *used = bytes they cover); QNAME ids by
  * first occurrence (-> number of distinct names, written '\n'-separated to uniq) */

@@ -87,6 +87,10 @@ SYMBOLS = {
     "svx_bgzf_deflate_dyn_ws_bytes": (_sz, [_u32]),                      # (ABI 420, additive: dynamic Huffman tables)
     "svx_bgzf_deflate_dyn": (ctypes.c_int, [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _u64, _vp]),
     "svx_bgzf_pack": (ctypes.c_int, [_vp, _vp, _u32, _vp, _vp, _u64, _vp]),
+    "svx_sam_lines_ws_bytes": (_sz, [_u64]),                             # (ABI 420, additive: svx_sam.hip)
+    "svx_sam_lines": (ctypes.c_int, [_vp, _u64, _vp, _u64, _vp, _vp, _u64, _vp]),
+    "svx_sam_measure": (ctypes.c_int, [_vp, _vp, _u32] + [_vp] * 4 + [_u32] + [_vp] * 5 + [_vp]),
+    "svx_sam_encode": (ctypes.c_int, [_vp, _vp, _u32] + [_vp] * 4 + [_u32, _vp, _vp, ctypes.c_int64, _vp, _vp, _vp]),
     "svx_read_range": (ctypes.c_int, [ctypes.c_char_p, _u64, _u64, _vp, ctypes.c_int]),
     "svx_bgzf_index": (ctypes.c_int64, [_vp, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _vp]),
     "svx_name_ids": (ctypes.c_int64, [_vp, _vp, _u64, _vp, _vp, _vp]),

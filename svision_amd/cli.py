@@ -219,7 +219,7 @@ def _load_unsorted(options):
 
 
 def _write_sorted(options):
-    """SVX_DEVICE_SORT=write and a header that does not say ``SO:coordinate``: the coordinate-sorted BAM and its .bai written into the
+    """SVX_DEVICE_SORT=write and a header that does not say ``SO:coordinate``, or an aligner's SAM text: the coordinate-sorted BAM and its .bai written into the
     output directory (svision_amd/sort.py) -> the sorted file's path, which stays there.  The sort runs in a process of its own: this
     one has not touched the device when the helpers of ``-t N`` are forked.  It inherits the environment: ``SVX_SORT_TABLES=dynamic``
     there is ``--tables dynamic`` (Huffman codes built per block; default: the fixed code), ``SVX_SORT_MEMORY=BYTES`` (K, M or G) is
@@ -231,7 +231,7 @@ def _write_sorted(options):
     import time
     t0 = time.perf_counter()
     name = os.path.basename(options.bam_path)
-    out = os.path.join(options.out_path, (name[:-4] if name.endswith(".bam") else name) + ".sorted.bam")
+    out = os.path.join(options.out_path, (name[:-4] if name.endswith((".bam", ".sam")) else name) + ".sorted.bam")
     stats_path = out + ".stats.json"
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, PYTHONPATH=os.pathsep.join([root] + [p for p in os.environ.get("PYTHONPATH", "").split(os.pathsep) if p]))
@@ -248,8 +248,9 @@ def _write_sorted(options):
     finally:
         if os.path.exists(stats_path):
             os.unlink(stats_path)
-    logging.info("%s is not coordinate sorted: %d records sorted on the device in %.2f s (%d range(s), %d radix passes)", options.bam_path,
-                 stats["records"], time.perf_counter() - t0, stats["ranges"], stats["passes"])
+    logging.info("%s is %s: %d records sorted on the device in %.2f s (%d range(s), %d radix passes)", options.bam_path,
+                 "SAM text" if stats.get("input") == "sam" else "not coordinate sorted", stats["records"], time.perf_counter() - t0,
+                 stats["ranges"], stats["passes"])
     logging.info("sorted file: %s (+ .bai), %d BGZF blocks, %d -> %d bytes, written in %d span(s) under a budget of %d bytes for the records "
                  "(SVX_SORT_MEMORY)", out, stats["blocks"], stats["inflated_bytes"], stats["compressed_bytes"], stats["spans"], stats["memory_bytes"])
     return out
@@ -258,6 +259,15 @@ def _write_sorted(options):
 # What a run reads.  ``sample``: the resident Sample (handed in, or sorted on the device), None when the file is streamed chromosome by
 # chromosome; ``index`` / ``build_index``: the streamed file's .bai, or that it is to be built on the device (both unset for a Sample).
 RunInput = collections.namedtuple("RunInput", "sample fasta references lengths index build_index")
+
+
+def _is_sam_text(path):
+    from .io import sam
+    try:
+        with open(path, "rb") as f:
+            return sam.is_sam_text(f.read(1 << 20))
+    except OSError:
+        return False
 
 
 def _open_input(options, sample, ws, tick):
@@ -270,8 +280,9 @@ def _open_input(options, sample, ws, tick):
     from .io.bam import find_index, read_bam_header
     if sample is None:
         # file-driven run: header now, the records chromosome by chromosome while the pipeline runs (ingest.ChromosomeFeed)
-        head = read_bam_header(options.bam_path)
-        if head.sort_order == "coordinate":
+        # (SAM text under SVX_DEVICE_SORT=write takes the road of an unsorted BAM; every other setting reads it as a BAM and refuses it)
+        head = None if os.environ.get("SVX_DEVICE_SORT") == "write" and _is_sam_text(options.bam_path) else read_bam_header(options.bam_path)
+        if head is not None and head.sort_order == "coordinate":
             fasta = Fasta(options.genome)
             index = find_index(options.bam_path)
             build_index = index is None and os.environ.get("SVX_BUILD_INDEX") == "1"

@@ -1,0 +1,308 @@
+"""SAM text -> the BAM record bytes htslib writes for it (``sam_parse1`` + ``bam_write1``): the host statement of the rules the
+device parser (svision_amd/csrc/svx_sam_core.hpp) follows, the road of every line that parser hands back (``SVX_SAM_HOST``), and the
+yardstick of its CPU model (tools/hostwave/sam_main.cpp).  Pure Python + ``struct``.
+
+The header.  The ``@`` lines in front of the first record are the BAM header's text, byte for byte; the reference dictionary is
+the ``@SQ`` lines' ``SN`` / ``LN`` in order.  No ``@SQ`` line: SamError.  An ``@`` line behind a record: SamError.
+
+A record line.  Lines end at ``\\n``, the last one may lack it; a ``\\r`` belongs to the last field.  Eleven tab-separated fields
+and any number of tags:
+
+  QNAME   l_read_name = its bytes + one NUL, no padding; empty or more than 254 bytes: error
+  FLAG    decimal, 0 .. 65535
+  RNAME   ``*`` -> -1; else the @SQ line's index; a name no @SQ line has: error (htslib warns and unmaps)
+  POS     decimal 0 .. 2^31 - 1, stored minus 1
+  MAPQ    decimal, 0 .. 255
+  CIGAR   ``*`` -> no operation; else <length><one of MIDNSHP=X> repeated, a length of 1 to 9 digits below 2^28.  More than 65,535
+          operations: the record carries ``<l_seq>S<span>N`` and the real words go behind the line's own tags as CG:B,I (SAMv1 4.2.2)
+  RNEXT   ``=`` -> the record's own tid, ``*`` -> -1, else as RNAME
+  PNEXT   as POS
+  TLEN    decimal with an optional ``-``, within +-(2^31 - 1)
+  SEQ     ``*`` -> l_seq 0; else 4 bits a base by the table ``=ACMGRSVTWYHKDBN``, either case, any other byte N, the first base in the
+          high nibble, an odd length leaves a zero low nibble
+  QUAL    ``*`` -> 0xFF x l_seq; else every byte minus 33, as many as l_seq or: error
+  bin     reg2bin(pos, pos + max(reference span, 1)) (the span: the lengths of M D N = X), 4680 where tid is -1; 16 bits
+  tags    ``XX:T:value``.  A: one byte.  Z and H: the bytes + NUL.  i: the narrowest type, htslib's choice -- negative: c, s, i;
+          else C, S, I; outside [-2^31, 2^32): error.  f: float32(double(text)), the decimal -> double conversion correctly rounded
+          (``strtod``, Python's ``float``).  B: ``B:<cCsSiIf>`` and a value behind every comma (none: an empty array); integers
+          within the subtype's range, floats as ``f``
+
+Errors raise :class:`SamError` (a ValueError) whose message names the 1-based line number and whose ``code`` is the device
+parser's code for the same line (include/svx.h, SVX_SAM_E_*)."""
+import collections
+import re
+import struct
+
+HOST = -1                                                       # SVX_SAM_HOST: valid as far as seen, not taken by the kernels
+E_FIELDS, E_NUMBER, E_NAME, E_RNAME, E_CIGAR, E_QUAL, E_TAG, E_RANGE, E_HEADER = -2, -3, -4, -5, -6, -7, -8, -9, -10
+CIGAR_OPS = b"MIDNSHP=X"
+MAX_CIGAR_OPS = 65535
+
+_BASE = bytearray([15] * 256)
+for _i, _c in enumerate(b"=ACMGRSVTWYHKDBN"):
+    _BASE[_c] = _i
+    _BASE[ord(chr(_c).lower())] = _i
+_HI = bytes(b << 4 for b in _BASE)
+_LO = bytes(_BASE)
+_QUAL = bytes((b - 33) & 255 for b in range(256))
+_OP = {c: i for i, c in enumerate(CIGAR_OPS)}
+_REF_OPS = frozenset(b"MDN=X")
+_CIGAR_RE = re.compile(rb"(\d{1,9})([MIDNSHP=X])")
+_FLOAT_RE = re.compile(rb"[+-]?(?:(?:\d+\.?\d*|\.\d+)(?:[eE][+-]?\d+)?|inf|infinity|nan)\Z", re.I)
+_INT_RE = re.compile(rb"-?\d{1,11}\Z")
+_B_TYPES = {ord("c"): ("b", -128, 127), ord("C"): ("B", 0, 255), ord("s"): ("h", -32768, 32767), ord("S"): ("H", 0, 65535),
+            ord("i"): ("i", -(1 << 31), (1 << 31) - 1), ord("I"): ("I", 0, (1 << 32) - 1)}
+
+SamHead = collections.namedtuple("SamHead", "references lengths text sort_order")
+
+
+class SamError(ValueError):
+    def __init__(self, message, code, line=None):
+        ValueError.__init__(self, message if line is None else "line %d: %s" % (line, message))
+        self.what, self.code, self.line = message, code, line
+
+    def at(self, line):
+        return SamError(self.what, self.code, line)
+
+
+def reg2bin(beg, end):
+    end -= 1
+    for shift, first in ((14, 4681), (17, 585), (20, 73), (23, 9), (26, 1)):
+        if beg >> shift == end >> shift:
+            return first + (beg >> shift)
+    return 0
+
+
+def _int(text, lo, hi, what, range_code=E_NUMBER):
+    if not _INT_RE.match(text):
+        raise SamError("%s is not a number: %r" % (what, text[:20]), E_NUMBER)
+    v = int(text)
+    if not lo <= v <= hi:
+        raise SamError("%s %d lies outside [%d, %d]" % (what, v, lo, hi), range_code)
+    return v
+
+
+def _float(text):
+    if not _FLOAT_RE.match(text):
+        raise SamError("not a floating-point value: %r" % text[:20], E_NUMBER)
+    return float(text)
+
+
+def _ref(name, tid_of):
+    if name == b"*":
+        return -1
+    tid = tid_of.get(name)
+    if tid is None:
+        raise SamError("the reference %r is in no @SQ line" % name[:40].decode("latin-1"), E_RNAME)
+    return tid
+
+
+def encode_tag(field):
+    """One tag field ``XX:T:value`` -> its BAM bytes."""
+    if len(field) < 5 or field[2] != 58 or field[4] != 58:
+        raise SamError("a malformed tag: %r" % field[:20], E_TAG)
+    name, typ, value = field[:2], field[3:4], field[5:]
+    if typ == b"A":
+        if len(value) != 1:
+            raise SamError("an A tag of %d bytes" % len(value), E_TAG)
+        return name + b"A" + value
+    if typ in (b"Z", b"H"):
+        return name + typ + value + b"\0"
+    if typ == b"i":
+        v = _int(value, -(1 << 31), (1 << 32) - 1, "an integer tag", E_RANGE)
+        if v < 0:
+            t = "cb" if v >= -128 else "sh" if v >= -32768 else "ii"
+        else:
+            t = "CB" if v <= 255 else "SH" if v <= 65535 else "II"
+        return name + t[:1].encode() + struct.pack("<" + t[1], v)
+    if typ == b"f":
+        return name + b"f" + struct.pack("<f", _float(value))
+    if typ == b"B":
+        if not value or (len(value) > 1 and value[1] != 44):
+            raise SamError("a malformed B tag: %r" % field[:20], E_TAG)
+        sub = value[0]
+        items = value[2:].split(b",") if len(value) > 1 else []
+        if sub == ord("f"):
+            return name + b"Bf" + struct.pack("<i%df" % len(items), len(items), *[_float(x) for x in items])
+        if sub not in _B_TYPES:
+            raise SamError("a B tag of subtype %r" % chr(sub), E_TAG)
+        fmt, lo, hi = _B_TYPES[sub]
+        return name + b"B" + value[:1] + struct.pack("<i%d%s" % (len(items), fmt), len(items), *[_int(x, lo, hi, "an array value") for x in items])
+    raise SamError("a tag of type %r" % typ.decode("latin-1"), E_TAG)
+
+
+def cigar_words(text):
+    """CIGAR text (not ``*``) -> (the BAM words, the reference span)."""
+    words, span, at = [], 0, 0
+    for m in _CIGAR_RE.finditer(text):
+        if m.start() != at:
+            break
+        at = m.end()
+        n = int(m.group(1))
+        if n >= 1 << 28:
+            raise SamError("a CIGAR length of %d" % n, E_CIGAR)
+        op = m.group(2)[0]
+        words.append(n << 4 | _OP[op])
+        if op in _REF_OPS:
+            span += n
+    if at != len(text) or not words:
+        raise SamError("a malformed CIGAR near %r" % text[at:at + 12], E_CIGAR)
+    return words, span
+
+
+def fields_of(line, tid_of):
+    """One alignment line -> (tid, pos, flag, reference span): the sort key and the index's fields.  Checks the core fields only."""
+    f = line.split(b"\t", 6)
+    if len(f) < 7:
+        raise SamError("fewer than 11 fields", E_FIELDS)
+    return (_ref(f[2], tid_of), _int(f[3], 0, (1 << 31) - 1, "POS") - 1, _int(f[1], 0, 65535, "FLAG"),
+            0 if f[5] == b"*" else cigar_words(f[5])[1])
+
+
+def encode_line(line, tid_of):
+    """One alignment line (no ``\\n``) and {reference name (bytes): tid} -> the line's BAM record including its ``block_size``."""
+    if line[:1] == b"@":
+        raise SamError("a header line behind the first record", E_HEADER)
+    f = line.split(b"\t")
+    if len(f) < 11:
+        raise SamError("an empty line" if not line else "%d fields, an alignment has at least 11" % len(f), E_FIELDS)
+    qname, flag, rname, pos, mapq, cigar, rnext, pnext, tlen, seq, qual = f[:11]
+    if not qname or len(qname) > 254:
+        raise SamError("a read name of %d bytes" % len(qname), E_NAME)
+    flag = _int(flag, 0, 65535, "FLAG")
+    tid = _ref(rname, tid_of)
+    pos = _int(pos, 0, (1 << 31) - 1, "POS") - 1
+    mapq = _int(mapq, 0, 255, "MAPQ")
+    words, span = ([], 0) if cigar == b"*" else cigar_words(cigar)
+    next_tid = tid if rnext == b"=" else _ref(rnext, tid_of)
+    next_pos = _int(pnext, 0, (1 << 31) - 1, "PNEXT") - 1
+    tlen = _int(tlen, -(1 << 31) + 1, (1 << 31) - 1, "TLEN")
+    if seq == b"*":
+        l_seq, packed = 0, b""
+    else:
+        l_seq = len(seq)
+        hi, lo = seq[0::2].translate(_HI), seq[1::2].translate(_LO).ljust((l_seq + 1) // 2, b"\0")
+        packed = (int.from_bytes(hi, "little") | int.from_bytes(lo, "little")).to_bytes(len(hi), "little")      # (a bytewise OR)
+    if qual == b"*":
+        q = b"\xff" * l_seq
+    elif len(qual) != l_seq:
+        raise SamError("%d quality values for %d bases" % (len(qual), l_seq), E_QUAL)
+    else:
+        q = qual.translate(_QUAL)
+    tags = b"".join(encode_tag(t) for t in f[11:])
+    if len(words) > MAX_CIGAR_OPS:
+        tags += b"CGBI" + struct.pack("<i%dI" % len(words), len(words), *words)
+        words = [l_seq << 4 | 4, span << 4 | 3]
+    bin_ = reg2bin(pos, pos + max(span, 1)) & 0xFFFF if tid >= 0 else 4680
+    body = struct.pack("<iiBBHHHiiii", tid, pos, len(qname) + 1, mapq, bin_, len(words), flag, l_seq, next_tid, next_pos, tlen) \
+        + qname + b"\0" + struct.pack("<%dI" % len(words), *words) + packed + q + tags
+    return struct.pack("<i", len(body)) + body
+
+
+# ---- the header ----
+def parse_header(text):
+    """The ``@`` lines (bytes, every line closed by ``\\n``) -> SamHead(references, lengths, the text as str, the @HD line's SO)."""
+    references, lengths, order = [], [], None
+    for no, line in enumerate(text.split(b"\n"), 1):
+        if line.startswith(b"@SQ\t"):
+            kv = dict(p.split(b":", 1) for p in line.split(b"\t")[1:] if b":" in p)
+            if b"SN" not in kv or not kv.get(b"LN", b"").isdigit():
+                raise SamError("an @SQ line without SN or LN", E_HEADER, no)
+            references.append(kv[b"SN"].decode("latin-1"))
+            lengths.append(int(kv[b"LN"]))
+        elif no == 1 and line.startswith(b"@HD"):
+            order = next((p[3:].decode("latin-1") for p in line.split(b"\t")[1:] if p.startswith(b"SO:")), None)
+    if not references:
+        raise SamError("no @SQ line: a BAM needs its reference dictionary", E_HEADER)
+    return SamHead(references, lengths, text.decode("latin-1"), order)
+
+
+def header_end(path, limit=1 << 30):
+    """-> the ``@`` lines' bytes at the start of the file (they end where the first line without ``@`` begins)."""
+    out = []
+    with open(path, "rb") as f:
+        for line in f:
+            if line[:1] != b"@":
+                break
+            out.append(line if line.endswith(b"\n") else line + b"\n")
+            limit -= len(line)
+            if limit < 0:
+                raise SamError("a header of more than 2^30 bytes", E_HEADER)
+    return b"".join(out)
+
+
+def read_sam(path):
+    """The whole file on the host -> (SamHead, [every alignment line's BAM record]).  The slow road: tests, and the statement of what
+    a file means; errors name their line."""
+    header = header_end(path)
+    head = parse_header(header)
+    tid_of = tid_table(head.references)
+    records = []
+    with open(path, "rb") as f:
+        f.seek(len(header))
+        for no, line in enumerate(f, header.count(b"\n") + 1):
+            try:
+                records.append(encode_line(line[:-1] if line.endswith(b"\n") else line, tid_of))
+            except SamError as exc:
+                raise exc.at(no) from None
+    return head, records
+
+
+def chunk_places(path, start, chunk_bytes, block=1 << 20):
+    """The alignment lines of the file, from byte ``start``, in chunks of at most ``chunk_bytes`` that end behind a newline or with the
+    file -> [(file offset, bytes)].  A line longer than ``chunk_bytes`` grows its chunk to the line's end."""
+    chunk_bytes = max(int(chunk_bytes), 1)
+    places = []
+    with open(path, "rb") as f:
+        size = f.seek(0, 2)
+        at = start
+        while at < size:
+            want = min(at + chunk_bytes, size)
+            end = want
+            if want < size:
+                f.seek(at)
+                end = at + f.read(want - at).rfind(b"\n") + 1     # behind the chunk's last newline; none: at
+                while end == at:                                # one line that is longer than the chunk: to its end
+                    f.seek(want)
+                    more = f.read(block)
+                    cut = more.find(b"\n")
+                    if cut >= 0:
+                        end = want + cut + 1
+                    elif not more:
+                        end = size
+                    want += len(more)
+            places.append((at, end - at))
+            at = end
+    return places
+
+
+def bam_header_bytes(head):
+    """SamHead -> the bytes in front of a BAM's first record: magic, text, reference dictionary."""
+    text = head.text.encode("latin-1")
+    out = [b"BAM\x01", struct.pack("<i", len(text)), text, struct.pack("<i", len(head.references))]
+    for name, length in zip(head.references, head.lengths):
+        n = name.encode("latin-1") + b"\0"
+        out += [struct.pack("<i", len(n)), n, struct.pack("<i", length)]
+    return b"".join(out)
+
+
+def tid_table(references):
+    return {name.encode("latin-1"): i for i, name in enumerate(references)}
+
+
+def name_hash(name):
+    """FNV-1a, 32 bits: the hash of the device's reference table."""
+    h = 0x811C9DC5
+    for b in name:
+        h = ((h ^ b) * 0x01000193) & 0xFFFFFFFF
+    return h
+
+
+def is_sam_text(start):
+    """The first bytes of a file (up to its first line and beyond) -> whether it is SAM text: a first byte ``@``, or a first line of at
+    least 11 tab-separated fields."""
+    if start[:1] == b"@":
+        return True
+    if start[:2] == b"\x1f\x8b" or start[:4] == b"BAM\x01" or not start:
+        return False
+    return start.split(b"\n", 1)[0].count(b"\t") >= 10

@@ -3,6 +3,7 @@ buffers to the C ABI of libsvx.so on the current HIP stream.
 
 PyTorch is used here only for device memory and streams.
 """
+import collections
 import ctypes
 
 import numpy as np
@@ -969,3 +970,97 @@ def bgzf_pack(slots, member_len, out_bytes):
     _lib.check(lib.svx_bgzf_pack(slots.data_ptr(), member_len.data_ptr(), n, file_off.data_ptr(), out.data_ptr(), int(out_bytes), _stream_ptr(dev)),
                "svx_bgzf_pack")
     return out, file_off
+
+
+# ---- SAM text -> BAM records (svx_sam.hip; the rules: svision_amd/io/sam.py; the caller: svision_amd/sort.py) ----
+SAM_SLACK = 64                       # SVX_SAM_SLACK: readable bytes behind a chunk of text
+SAM_HOST = -1                        # SVX_SAM_HOST: a valid line the kernels leave to svision_amd.io.sam.encode_line
+
+SamRefTable = collections.namedtuple("SamRefTable", "hash tid name_off names n")
+
+
+def sam_ref_table(references, device):
+    """The @SQ names (str, in tid order) -> the device table the SAM kernels look RNAME and RNEXT up in: the names' FNV-1a hashes
+    ascending, their tids in that order, and the names' bytes by tid (the kernels compare them)."""
+    from .io.sam import name_hash
+    names = [r.encode("latin-1") for r in references]
+    hashes = np.fromiter((name_hash(n) for n in names), np.uint32, len(names))
+    by_hash = np.argsort(hashes, kind="stable").astype(np.int32)
+    name_off = np.zeros(len(names) + 1, np.uint32)
+    name_off[1:] = np.cumsum([len(n) for n in names], dtype=np.int64)
+    flat = np.frombuffer(b"".join(names) or b"\0", np.uint8)
+    to = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.int32 if a.dtype == np.uint32 else a.dtype).copy()).to(device)
+    return SamRefTable(to(hashes[by_hash]), to(by_hash), to(name_off), to(flat), len(names))
+
+
+def _require_text(d_text, n_bytes):
+    _require_cuda(d_text, "d_text")
+    if d_text.dtype != torch.uint8 or d_text.numel() < int(n_bytes) + SAM_SLACK:
+        raise _lib.SvxError("d_text must be uint8 with %d readable bytes behind the chunk's %d" % (SAM_SLACK, n_bytes))
+
+
+class SamLinesOverflow(_lib.SvxError):
+    def __init__(self, n_lines, cap):
+        _lib.SvxError.__init__(self, "svx_sam_lines: %d lines, the table holds %d" % (n_lines, cap - 1))
+        self.n_lines = n_lines
+
+
+def sam_lines(d_text, n_bytes, cap=None):
+    """The chunk d_text[:n_bytes] of alignment lines (SAM_SLACK readable bytes behind it) -> (int64 [cap] device tensor whose first
+    n_lines + 1 entries are the line starts and n_bytes, n_lines).  ``cap``: at least the chunk's lines + 1; None: a call that only
+    counts comes first.  See include/svx.h svx_sam_lines."""
+    lib = _lib.load()
+    _require_text(d_text, n_bytes)
+    if cap is None:
+        try:
+            return sam_lines(d_text, n_bytes, 1)
+        except SamLinesOverflow as exc:
+            return sam_lines(d_text, n_bytes, exc.n_lines + 1)
+    dev, cap = d_text.device, max(int(cap), 1)
+    line_off = torch.empty(cap, dtype=torch.int64, device=dev)
+    n_lines = torch.zeros(1, dtype=torch.int64, device=dev)
+    ws_bytes = int(lib.svx_sam_lines_ws_bytes(int(n_bytes)))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    _lib.check(lib.svx_sam_lines(d_text.data_ptr(), int(n_bytes), line_off.data_ptr(), cap, n_lines.data_ptr(), ws.data_ptr(), ws_bytes,
+                                 _stream_ptr(dev)), "svx_sam_lines")
+    n = int(n_lines.item())
+    if n + 1 > cap:
+        raise SamLinesOverflow(n, cap)
+    return line_off, n
+
+
+def sam_measure(d_text, n_bytes, line_off, n_lines, table):
+    """A wave a line -> int32 [n_lines] device tensors (len, tid, pos, flag, span): the bytes of the line's BAM record or a negative
+    code (SAM_HOST, or an error: svision_amd.io.sam.E_*), and the sort key and index fields.  See include/svx.h svx_sam_measure."""
+    lib = _lib.load()
+    _require_text(d_text, n_bytes)
+    dev = d_text.device
+    if line_off.dtype != torch.int64 or line_off.numel() < n_lines + 1 or n_lines > 0xFFFFFFFF:
+        raise _lib.SvxError("line_off must be int64 [n_lines + 1]")
+    out = [torch.empty(n_lines, dtype=torch.int32, device=dev) for _ in range(5)]
+    _lib.check(lib.svx_sam_measure(d_text.data_ptr(), line_off.data_ptr(), n_lines, table.hash.data_ptr(), table.tid.data_ptr(),
+                                   table.name_off.data_ptr(), table.names.data_ptr(), table.n, *[t.data_ptr() for t in out], _stream_ptr(dev)),
+               "svx_sam_measure")
+    return tuple(out)
+
+
+def sam_encode(d_text, n_bytes, line_off, n_lines, table, d_len, d_off, out_base, out, status):
+    """A wave a line: the record of every line with ``d_len[i] >= 0`` (int32 [n_lines]) to ``out`` (uint8) at byte d_off[i] - out_base
+    (int64 [n_lines]), exactly d_len[i] bytes; ``out`` must hold them all, which is checked here.  ``status``: int32 [1], set to 1 where a line no longer measures d_len[i] --
+    that record is not written.  See include/svx.h svx_sam_encode."""
+    lib = _lib.load()
+    _require_text(d_text, n_bytes)
+    for t, name in ((d_len, "d_len"), (d_off, "d_off"), (out, "out"), (status, "status")):
+        _require_cuda(t, name)
+    if d_len.dtype != torch.int32 or d_off.dtype != torch.int64 or out.dtype != torch.uint8 or status.dtype != torch.int32 \
+            or d_len.numel() < n_lines or d_off.numel() < n_lines or line_off.numel() < n_lines + 1:
+        raise _lib.SvxError("d_len must be int32 [n_lines], d_off int64 [n_lines], out uint8, status int32 [1]")
+    if n_lines:
+        ends = (d_off[:n_lines] + d_len[:n_lines].clamp(min=0)) - int(out_base)
+        taken = d_len[:n_lines] >= 0
+        if bool(taken.any()) and (int(ends[taken].max()) > out.numel() or int((d_off[:n_lines][taken] - int(out_base)).min()) < 0):
+            raise _lib.SvxError("svx_sam_encode: a record lies outside the %d bytes of out" % out.numel())
+    _lib.check(lib.svx_sam_encode(d_text.data_ptr(), line_off.data_ptr(), n_lines, table.hash.data_ptr(), table.tid.data_ptr(),
+                                  table.name_off.data_ptr(), table.names.data_ptr(), table.n, d_len.data_ptr(), d_off.data_ptr(), int(out_base),
+                                  out.data_ptr(), status.data_ptr(), _stream_ptr(d_text.device)), "svx_sam_encode")
+    return out

@@ -1,4 +1,4 @@
-"""Write the coordinate-sorted BAM of an unsorted one, and its ``.bai``, on the device: ``python -m svision_amd.sort in.bam -o out.bam``.
+"""Write the coordinate-sorted BAM of an unsorted one -- or of SAM text --, and its ``.bai``, on the device: ``python -m svision_amd.sort in.bam -o out.bam``.
 
 ``SVX_DEVICE_SORT=1`` (svision_amd/ingest_sort.py) computes the order of an aligner's output and throws it away with the process.
 Here the order becomes a file -- a standard BAM with a standard index that the default path, any number of ranks, a second caller
@@ -51,11 +51,30 @@ placed in pieces, the same two files byte for byte:
             SortWriteError
   output    the span's buffer through the chunk loop without the gather, ``chunk_bytes`` capped at the span
 
+SAM text.  An aligner's output that was never converted (minimap2, winnowmap, ngmlr, pbmm2 without --sort) is taken as it is: a file
+whose first byte is ``@``, or whose first line has at least 11 tab-separated fields.  Only the front end differs -- how the records'
+bytes, keys and fields come about -- and the two files are those of the same records stored as an unsorted BAM, byte for byte:
+
+  open      the ``@`` lines are the header's text, the reference dictionary comes from @SQ SN / LN (io/sam.py); ``room`` is not known yet
+  key pass  the text in chunks of ``range_bytes`` (DEFAULT_SAM_CHUNK_BYTES, 64 MB: of 16, 64 and 256 MB the fastest, profiles/sort_sam.txt)
+            cut at line ends, a longer line growing its chunk: read (svx_read_range into pinned memory), upload, svx_sam_lines,
+            svx_sam_measure -- a wave a line: the record's bytes or a code, tid pos flag span --, read back.  An error code raises with
+            the file's line number, worded by io/sam.py.  A line the kernels leave to the host (SVX_SAM_HOST: more than 65,535 CIGAR
+            operations, an ``f`` value outside the exact fast path) is encoded by io.sam.encode_line at once, its bytes kept on the host
+            and its length, key and fields patched in.  Behind the pass ``room`` is exact and ``spanned`` is decided
+  in one piece  the text is read a second time -- from the page cache for any file that fits the device -- and svx_sam_encode writes
+            every chunk's records straight into the resident stream; the host's encodings are copied to their offsets
+  in spans  the places of :func:`span_ranges` are chunks of text: each is encoded into a chunk-local buffer and goes through
+            svx_record_scatter_segments like a BAM's range.  A chunk with another number of lines, or a line whose record has another
+            length than in the key pass, means the file changed: SortWriteError
+Compressed SAM (gzip, BGZF) and stdin are not taken: the text is read twice.
+
 A corrupt block, a CRC mismatch, a malformed or cut chain, a device allocation or a write that fails raises SortWriteError (a
 ValueError); no file and no temporary is left behind.
 
 :func:`sort_bam` is the list of its steps, each a function of this module over named values: ``_open`` (header, first record and
-``room`` from one pass over the file's members: index.bgzf_members, index.header_place) -> ``_key_pass`` -> ``_order`` -> the pieces,
+``room`` from one pass over the file's members: index.bgzf_members, index.header_place; it also chooses the :class:`Source`, BAM or
+SAM text: the key pass and the reading-again of a span's ranges) -> ``_key_pass`` -> ``_order`` -> the pieces,
 ``_pieces_in_core`` or ``_pieces_spanned``: generators of (device buffer, first byte, bytes), a chunk each -> :class:`BgzfWriter`,
 which owns the temporary file and the ledger of members and is handed its encoder (:class:`DeviceEncode`; zlib in the CPU tests) ->
 ``_bai`` -> :func:`commit_pair`.  Which records a chunk or a span takes is one rule, :func:`records_touching`; the 0xFF00 cut one
@@ -75,7 +94,9 @@ BLOCK = 0xFF00                                                  # htslib's block
 DEFAULT_CHUNK_BYTES = 1024 * BLOCK
 TABLES = ("fixed", "dynamic")                                   # the encoder: svx_bgzf_deflate / svx_bgzf_deflate_dyn
 STAGES = ("read", "upload", "inflate", "crc", "find_starts", "walk", "scan", "read_back", "keep", "join", "sort", "gather", "scatter", "deflate",
-          "pack", "download", "write", "index")
+          "pack", "download", "write", "index", "lines", "measure", "encode", "host_lines")
+SAM_READ_THREADS = 8                                            # svx_read_range's threads for a chunk of text
+DEFAULT_SAM_CHUNK_BYTES = 64 << 20                              # text bytes a chunk of a SAM input (``range_bytes``); see profiles/sort_sam.txt
 
 
 class SortWriteError(ValueError):
@@ -309,13 +330,34 @@ class DeviceEncode:
         return packed, m, stored, dynamic
 
 
-Opened = collections.namedtuple("Opened", "path head first header room")
+Opened = collections.namedtuple("Opened", "path head first header room source", defaults=(None,))
+# The input's kind, chosen at open: ``key_pass(dv, opened, budget, range_bytes, kp) -> (opened with its room known, spanned)`` and
+# ``again(dv, opened, kp, need) -> per range of ``need`` (k, records completed, device bytes, the records' offsets in them [n + 1])``,
+# the ranges of the key pass read once more for a span.
+Source = collections.namedtuple("Source", "name key_pass again")
 
 
 def _open(bam_path):
     """open: -> Opened(the path, read_bam_header's table, first_record's (file offset, entry, references), the header's bytes as the
-    output takes them, ``room``: the records' inflated bytes by the members' ISIZE fields) -- one pass over the file's members."""
+    output takes them, ``room``: the records' inflated bytes by the members' ISIZE fields) -- one pass over the file's members.  SAM
+    text (a first byte ``@``, or a first line of 11 tab-separated fields): :func:`_open_sam`."""
+    from .io import sam
     from .io.bam import read_bam_header
+    try:
+        with open(bam_path, "rb") as f:
+            start = f.read(1 << 20)
+    except OSError as exc:
+        raise SortWriteError("%s: %s" % (bam_path, exc)) from None
+    if sam.is_sam_text(start):
+        return _open_sam(bam_path)
+    if start[:2] == b"\x1f\x8b":
+        try:
+            magic = zlib.decompressobj(31).decompress(start, 4)
+        except zlib.error:
+            magic = b"BAM\x01"                                   # (not for this check to report: the BAM road names what is broken)
+        if magic[:4] != b"BAM\x01":
+            raise SortWriteError("%s: gzip- or BGZF-compressed data that is no BAM -- compressed SAM is not taken: decompress it, or "
+                                 "convert it with `samtools view -b`" % bam_path)
     try:
         head = read_bam_header(bam_path)
         members = index.bgzf_members(bam_path)
@@ -326,17 +368,33 @@ def _open(bam_path):
         raise SortWriteError("%s: %s" % (bam_path, exc)) from None
     if room < 0:
         raise SortWriteError("%s: its BGZF blocks hold fewer bytes than its header" % bam_path)
-    return Opened(bam_path, head, tuple(place[:3]), header, room)
+    return Opened(bam_path, head, tuple(place[:3]), header, room, BAM_SOURCE)
+
+
+def _open_sam(path):
+    """open, SAM text: -> Opened(the path, the header's references and lengths (io.sam.SamHead), the file offset of the first alignment
+    line, the output's header bytes, ``room`` None: the records' bytes are known behind the key pass)."""
+    from .io import sam
+    try:
+        text = sam.header_end(path)
+        head = sam.parse_header(text)
+        header = sorted_header_bytes(sam.bam_header_bytes(head))
+    except (sam.SamError, OSError) as exc:
+        raise SortWriteError("%s: %s" % (path, exc)) from None
+    return Opened(path, head, (len(text), text.count(b"\n")), header, None, SAM_SOURCE)
 
 
 class KeyPass:
     """What the pass over the file leaves, filled by :func:`_key_pass` as it goes (``seen`` is right in a failure's message too):
     ``range_records`` and ``places`` per range; ``seen``: the inflated record bytes so far; behind the join the ``n`` records' host
     fields ``tid pos flag span``, the device keys ``d_tid d_pos`` (until the sort has taken them), the records' offsets in the joined
-    stream ``off_in`` / ``d_off_in`` [n + 1], and ``d_stream``: the resident record stream, None in a spanned run."""
+    stream ``off_in`` / ``d_off_in`` [n + 1], and ``d_stream``: the resident record stream, None in a spanned run.  SAM text besides:
+    ``host_lens`` per chunk the lines' lengths as svx_sam_encode takes them (negative: the host's line), ``host_records`` {record
+    number: the bytes io.sam encoded}, ``sam_table``: the device's reference names, ``pinned``: the host buffer a chunk is read into."""
 
     def __init__(self):
         self.range_records, self.places, self.seen, self.n = [], [], 0, 0
+        self.host_lens, self.host_records, self.sam_table, self.pinned = [], {}, None, None
         self.tid = self.pos = self.flag = self.span = self.d_tid = self.d_pos = self.off_in = self.d_off_in = self.d_stream = None
 
 
@@ -364,11 +422,18 @@ def _key_pass(dv, opened, spanned, range_bytes, kp):
         rng.d_raw = rng.d_starts = rng.d_base = rng.d_cigar = rng.d_cig_off = rng.d_names = rng.d_name_off = None
         del rng
         clock.lap("keep")
+    return _join(dv, opened, kp, host, d_keys, lens)
+
+
+def _join(dv, opened, kp, host, d_keys, lens):
+    """join: what the ranges left -- per range the host fields, the device keys and the records' lengths -> ``kp``'s arrays of the one
+    record stream."""
+    torch, dev, clock = dv.torch, dv.dev, dv.clock
     n = kp.n = int(sum(l.size for l in lens))
     if n > 0xFFFFFFFF:
         raise SortWriteError("%s: %d records -- svx_record_sort takes up to 2^32 - 1" % (opened.path, n))
     # ---- join: CSR offsets and the keys of the one record stream
-    if not spanned:
+    if kp.d_stream is not None:
         kp.d_stream[kp.seen:] = 0
     kp.off_in = np.zeros(n + 1, np.int64)
     if n:
@@ -435,7 +500,8 @@ def _pieces_in_core(dv, opened, kp, od, chunk_blocks, counts):
 
 def _pieces_spanned(dv, opened, kp, od, chunk_blocks, counts):
     """pieces of a run in spans: the record stream in pieces of the budget, each filled by a pass over the ranges that own its records
-    (``counts["span_range_reads"]`` of them in all) and then given chunk by chunk -> as :func:`_pieces_in_core`."""
+    (``counts["span_range_reads"]`` of them in all; the source reads them again: :func:`_bam_again`, :func:`_sam_again`) and then
+    given chunk by chunk -> as :func:`_pieces_in_core`."""
     torch, lib, kernels, dev, clock = dv
     rec_base = np.concatenate([[0], np.cumsum(np.asarray(kp.range_records, np.int64))])
     for sp in od.plan:
@@ -443,24 +509,191 @@ def _pieces_spanned(dv, opened, kp, od, chunk_blocks, counts):
         d_status = torch.zeros(1, dtype=torch.int32, device=dev)
         need = span_ranges(od.rank, kp.range_records, sp.r_lo, sp.r_hi)
         clock.lap("scatter")
-        for k, rng in zip(need, index.record_ranges(opened.path, opened.head, dev, clock, places=[kp.places[k] for k in need], extract=False,
-                                                    first=opened.first)):
+        for k, n_rec, d_raw, d_src_off in opened.source.again(dv, opened, kp, need):
             counts["span_range_reads"] += 1
-            if rng.n_rec != kp.range_records[k]:
+            if n_rec != kp.range_records[k]:
                 raise SortWriteError("%s changed while it was sorted: %d records complete in the range at file offset %d, %d did in the "
-                                     "first pass" % (opened.path, rng.n_rec, kp.places[k][0], kp.range_records[k]))
-            d_src_off = index.walk_offsets(lib, torch, kernels, dev, rng, closed=True)
-            clock.lap("walk")
-            kernels.record_scatter_segments(rng.d_raw, d_src_off, od.d_rank[int(rec_base[k]):int(rec_base[k + 1])], sp.r_lo, sp.r_hi,
+                                     "first pass" % (opened.path, n_rec, kp.places[k][0], kp.range_records[k]))
+            kernels.record_scatter_segments(d_raw, d_src_off, od.d_rank[int(rec_base[k]):int(rec_base[k + 1])], sp.r_lo, sp.r_hi,
                                             od.d_off_out, sp.base, d_span, d_status)
             clock.lap("scatter")
-            rng.d_raw = rng.d_starts = rng.d_base = None
-            del rng, d_src_off
+            del d_raw, d_src_off
         if int(d_status.item()):
             raise SortWriteError("%s changed while it was sorted: a record's length is not the one the first pass saw" % opened.path)
         for lo, hi in chunk_cuts(sp.lo, sp.hi, chunk_blocks * BLOCK):
             yield d_span, lo - sp.base, hi - lo
         del d_span
+
+
+# ---- the sources: a BAM's ranges, a SAM's chunks of text ----
+def _bam_key_pass(dv, opened, budget, range_bytes, kp):
+    """key pass of a BAM: ``room`` is known from the members' ISIZE fields, so the records are kept as the pass goes wherever they fit."""
+    spanned = opened.room > budget                              # the records do not fit: no byte is kept in the pass, the output is filled in spans
+    _key_pass(dv, opened, spanned, range_bytes, kp)
+    return opened, spanned
+
+
+def _bam_again(dv, opened, kp, need):
+    """The ranges ``need`` of a BAM read again: read, inflate, CRC, find_starts, the walk's counts and offsets; nothing is extracted."""
+    for k, rng in zip(need, index.record_ranges(opened.path, opened.head, dv.dev, dv.clock, places=[kp.places[k] for k in need], extract=False,
+                                                first=opened.first)):
+        if rng.n_rec != kp.range_records[k]:
+            yield k, rng.n_rec, None, None                      # (the caller refuses it; no offsets are taken of a range that changed)
+            return
+        d_src_off = index.walk_offsets(dv.lib, dv.torch, dv.kernels, dv.dev, rng, closed=True)
+        dv.clock.lap("walk")
+        yield k, rng.n_rec, rng.d_raw, d_src_off
+        rng.d_raw = rng.d_starts = rng.d_base = None
+        del rng, d_src_off
+
+
+def _sam_chunk(dv, opened, kp, place, again=False):
+    """A chunk of the text: read into pinned memory (svx_read_range), uploaded with the kernels' slack behind it, its line table ->
+    (the bytes on the host: a NumPy view that the next chunk overwrites, d_text, d_line_off, the number of lines)."""
+    torch, kernels, dev, clock = dv.torch, dv.kernels, dv.dev, dv.clock
+    n = place[1]
+    if kp.pinned is None or kp.pinned.numel() < n:
+        kp.pinned = torch.empty(n, dtype=torch.uint8, pin_memory=True)
+    if dv.lib.svx_read_range(opened.path.encode(), place[0], n, kp.pinned.data_ptr(), SAM_READ_THREADS) != 0:
+        raise SortWriteError(("%s changed while it was sorted: %s" if again else "%s: %s") % (opened.path, dv.lib.svx_bam_error().decode()))
+    clock.lap("read", False)
+    d_text = torch.empty(n + kernels.SAM_SLACK, dtype=torch.uint8, device=dev)
+    d_text[:n].copy_(kp.pinned[:n], non_blocking=True)
+    d_text[n:] = 0
+    clock.lap("upload")
+    d_line_off, n_lines = kernels.sam_lines(d_text, n)
+    clock.lap("lines")
+    return kp.pinned[:n].numpy(), d_text, d_line_off, n_lines
+
+
+def _sam_refuse(opened, tid_of, data, line_off, i, line_no, code):
+    """The error of line i of a chunk, worded by the host statement of the rules."""
+    from .io import sam
+    line = data[int(line_off[i]):int(line_off[i + 1])].tobytes()
+    try:
+        sam.encode_line(line[:-1] if line.endswith(b"\n") else line, tid_of)
+    except sam.SamError as exc:
+        return SortWriteError("%s: %s" % (opened.path, exc.at(line_no)))
+    return SortWriteError("%s: line %d: not an alignment line (svx_sam_measure: %d)" % (opened.path, line_no, code))
+
+
+def _sam_key_pass(dv, opened, budget, range_bytes, kp):
+    """key pass of SAM text: one pass over the chunks (io.sam.chunk_places: ``range_bytes`` of text, cut at line ends): svx_sam_lines,
+    svx_sam_measure, the lengths and fields read back.  An error code raises with the file's line number; a line the kernels leave to the
+    host (SVX_SAM_HOST) is encoded by io.sam at once -- its bytes kept in ``kp.host_records`` by record number, its length, key and
+    fields patched in.  ``room`` is exact behind the pass: -> (opened with it, spanned).  A run in one piece then reads the text once
+    more (:func:`_sam_fill`)."""
+    from .io import sam
+    torch, kernels, dev, clock = dv.torch, dv.kernels, dv.dev, dv.clock
+    tid_of, kp.sam_table = sam.tid_table(opened.head.references), kernels.sam_ref_table(opened.head.references, dev)
+    host, d_keys, lens = [], [], []
+    line_no, seen = opened.first[1], 0
+    for place in sam.chunk_places(opened.path, opened.first[0], range_bytes or DEFAULT_SAM_CHUNK_BYTES):
+        data, d_text, d_line_off, n_lines = _sam_chunk(dv, opened, kp, place)
+        d_len, d_tid, d_pos, d_flag, d_span = kernels.sam_measure(d_text, len(data), d_line_off, n_lines, kp.sam_table)
+        clock.lap("measure")
+        length, tid, pos, flag, span = (t.cpu().numpy() for t in (d_len, d_tid, d_pos, d_flag, d_span))
+        line_off = d_line_off[:n_lines + 1].cpu().numpy()
+        clock.lap("read_back")
+        bad = np.flatnonzero(length < kernels.SAM_HOST)
+        if bad.size:
+            raise _sam_refuse(opened, tid_of, data, line_off, int(bad[0]), line_no + int(bad[0]) + 1, int(length[bad[0]]))
+        kernel_len = length.copy()
+        left = np.flatnonzero(length == kernels.SAM_HOST)
+        for i in left:
+            line = data[int(line_off[i]):int(line_off[i + 1])].tobytes()
+            line = line[:-1] if line.endswith(b"\n") else line
+            try:
+                rec = sam.encode_line(line, tid_of)
+                tid[i], pos[i], flag[i], span[i] = sam.fields_of(line, tid_of)
+            except sam.SamError as exc:
+                raise SortWriteError("%s: %s" % (opened.path, exc.at(line_no + int(i) + 1))) from None
+            length[i] = len(rec)
+            kp.host_records[seen + int(i)] = rec
+        if left.size:
+            d_tid, d_pos = torch.from_numpy(tid).to(dev), torch.from_numpy(pos).to(dev)
+        clock.lap("host_lines", False)
+        kp.range_records.append(n_lines)
+        kp.places.append(place)
+        kp.host_lens.append(kernel_len)
+        if n_lines:
+            host.append((tid, pos, flag.astype(np.uint16), span))
+            lens.append(length.astype(np.int64))
+            d_keys.append((d_tid, d_pos))
+        kp.seen += int(length.sum())
+        seen += n_lines
+        line_no += n_lines
+        del d_text, d_line_off, d_len, d_flag, d_span
+        clock.lap("keep")
+    _join(dv, opened, kp, host, d_keys, lens)
+    opened = opened._replace(room=int(kp.off_in[-1]))
+    spanned = opened.room > budget
+    if not spanned:
+        _sam_fill(dv, opened, kp)
+    return opened, spanned
+
+
+def _sam_encode_chunk(dv, opened, kp, k, first, base, d_out, d_status):
+    """Chunk k of the key pass read again and its records written: svx_sam_lines -> svx_sam_encode to ``d_out``, record r of the stream
+    at byte off_in[r] - base; the host's encodings copied to their offsets.  ``first``: the number of the chunk's first record.
+    -> the lines the chunk has now (another number than in the key pass: nothing is written)."""
+    torch, kernels = dv.torch, dv.kernels
+    data, d_text, d_line_off, n_lines = _sam_chunk(dv, opened, kp, kp.places[k], again=True)
+    if n_lines != kp.range_records[k]:
+        return n_lines
+    d_len = torch.from_numpy(kp.host_lens[k]).to(dv.dev)
+    kernels.sam_encode(d_text, len(data), d_line_off, n_lines, kp.sam_table, d_len, kp.d_off_in[first:first + n_lines], base, d_out, d_status)
+    dv.clock.lap("encode")
+    for i in np.flatnonzero(kp.host_lens[k] < 0):
+        rec = kp.host_records[first + int(i)]
+        at = int(kp.off_in[first + int(i)]) - base
+        d_out[at:at + len(rec)].copy_(torch.frombuffer(bytearray(rec), dtype=torch.uint8))
+    dv.clock.lap("host_lines")
+    return n_lines
+
+
+def _sam_changed(opened, kp, k, n_lines):
+    return SortWriteError("%s changed while it was sorted: %d lines complete in the chunk at file offset %d, %d did in the first pass"
+                          % (opened.path, n_lines, kp.places[k][0], kp.range_records[k]))
+
+
+def _sam_fill(dv, opened, kp):
+    """in one piece, SAM text: the second read of the text -- in the page cache for a file that fits the device --, every chunk encoded
+    straight into the resident stream at its records' offsets."""
+    torch, dev = dv.torch, dv.dev
+    kp.d_stream = torch.empty(opened.room + 4, dtype=torch.uint8, device=dev)
+    kp.d_stream[opened.room:] = 0
+    d_status = torch.zeros(1, dtype=torch.int32, device=dev)
+    first = 0
+    for k, n_rec in enumerate(kp.range_records):
+        n_lines = _sam_encode_chunk(dv, opened, kp, k, first, 0, kp.d_stream, d_status)
+        if n_lines != n_rec:
+            raise _sam_changed(opened, kp, k, n_lines)
+        first += n_rec
+    if int(d_status.item()):
+        raise SortWriteError("%s changed while it was sorted: a line's record is not of the length the first pass saw" % opened.path)
+
+
+def _sam_again(dv, opened, kp, need):
+    """The chunks ``need`` of SAM text read again for a span: each encoded into a chunk-local buffer (+ the 4 readable bytes the
+    scatter's aligned loads want) whose record offsets are the key pass's."""
+    torch, dev = dv.torch, dv.dev
+    rec_base = np.concatenate([[0], np.cumsum(np.asarray(kp.range_records, np.int64))])
+    for k in need:
+        first, n_rec = int(rec_base[k]), int(kp.range_records[k])
+        base = int(kp.off_in[first])
+        d_local = torch.zeros(int(kp.off_in[first + n_rec]) - base + 4, dtype=torch.uint8, device=dev)
+        d_status = torch.zeros(1, dtype=torch.int32, device=dev)
+        d_src_off = kp.d_off_in[first:first + n_rec + 1] - base
+        n_lines = _sam_encode_chunk(dv, opened, kp, k, first, base, d_local, d_status)
+        if n_lines == n_rec and int(d_status.item()):
+            raise SortWriteError("%s changed while it was sorted: a line's record is not of the length the first pass saw" % opened.path)
+        yield k, n_lines, d_local, d_src_off
+        del d_local, d_src_off
+
+
+BAM_SOURCE = Source("bam", _bam_key_pass, _bam_again)
+SAM_SOURCE = Source("sam", _sam_key_pass, _sam_again)
 
 
 def _bai(opened, kp, od, written):
@@ -485,7 +718,8 @@ def sort_bam(bam_path, out_path, device="cuda", range_bytes=None, chunk_bytes=No
     spans, a pass over the input for each (see the head of the module) -- the same two files.  ``stats``: a dict that receives
     ranges, records, blocks, stored_blocks, dynamic_blocks, compressed_bytes, inflated_bytes, chunks, spans (1: in one piece),
     span_range_reads (ranges read again over all spans; 0 in one piece), range_records (the records every range of the pass
-    completed), stream_bytes (the largest record buffer allocated) and the seconds per stage."""
+    completed), stream_bytes (the largest record buffer allocated) and the seconds per stage.  ``bam_path`` may be SAM text: then
+    ``range_bytes`` is the text bytes of a chunk, and stats also has input="sam" and host_lines, the lines io/sam.py encoded."""
     from . import ingest_sort, kernels
     torch, lib, dev, clock = index.on_device("sort_bam needs the GPU (svx_record_sort, svx_bgzf_deflate)", device, STAGES)
     if tables not in TABLES:
@@ -499,8 +733,7 @@ def sort_bam(bam_path, out_path, device="cuda", range_bytes=None, chunk_bytes=No
         with torch.cuda.device(dev):
             if budget is None:                                  # half of what is free: the rest is for a range, its inflate workspace, keys and chunks
                 budget = max(int(torch.cuda.mem_get_info(dev)[0]) // 2, 1)
-            spanned = opened.room > budget                      # the records do not fit: no byte is kept in the pass, the output is filled in spans
-            _key_pass(dv, opened, spanned, range_bytes, kp)
+            opened, spanned = opened.source.key_pass(dv, opened, budget, range_bytes, kp)
             od = _order(dv, opened, kp, spanned, budget)
             pieces = _pieces_spanned if spanned else _pieces_in_core
             writer = BgzfWriter(out_path, DeviceEncode(dv, tables), clock, bam_path)
@@ -516,7 +749,7 @@ def sort_bam(bam_path, out_path, device="cuda", range_bytes=None, chunk_bytes=No
     except torch.cuda.OutOfMemoryError as exc:
         raise SortWriteError("%s: the device has no room for the file's records -- %d inflated record bytes in all, %d seen so far, a budget of "
                              "%s bytes for them; a smaller one (--memory, SVX_SORT_MEMORY; sort_bam's memory_bytes) writes the file in more "
-                             "spans (%s)" % (bam_path, opened.room, kp.seen, budget, str(exc).split("\n")[0])) from None
+                             "spans (%s)" % (bam_path, kp.seen if opened.room is None else opened.room, kp.seen, budget, str(exc).split("\n")[0])) from None
     except _lib.SvxError as exc:
         raise SortWriteError("%s: %s" % (bam_path, exc)) from None
     except OSError as exc:
@@ -525,6 +758,8 @@ def sort_bam(bam_path, out_path, device="cuda", range_bytes=None, chunk_bytes=No
         if writer is not None:
             writer.discard()
     if stats is not None:
+        if opened.source.name == "sam":
+            stats.update(input="sam", host_lines=len(kp.host_records))
         stats.update(ranges=len(kp.range_records), records=kp.n, blocks=written.blocks, stored_blocks=written.stored_blocks,
                      dynamic_blocks=written.dynamic_blocks, chunks=written.chunks, spans=od.spans, span_range_reads=counts["span_range_reads"],
                      range_records=kp.range_records, stream_bytes=od.stream_bytes, memory_bytes=budget,
@@ -537,7 +772,7 @@ def sort_bam(bam_path, out_path, device="cuda", range_bytes=None, chunk_bytes=No
 def main(argv=None):
     import argparse
     import json
-    ap = argparse.ArgumentParser(prog="python -m svision_amd.sort", description="Write the coordinate-sorted BAM of an unsorted one, and its .bai, on the GPU.")
+    ap = argparse.ArgumentParser(prog="python -m svision_amd.sort", description="Write the coordinate-sorted BAM of an unsorted BAM or of SAM text, and its .bai, on the GPU.")
     ap.add_argument("bam")
     ap.add_argument("-o", "--output", required=True, help="the sorted BAM to write (its index: OUTPUT + .bai)")
     ap.add_argument("--device", default="cuda")
