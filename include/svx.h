@@ -489,6 +489,15 @@ int            svx_bam_walk_offsets(const uint8_t* d_raw, const uint64_t* d_star
  *                       is NOT copied and d_status[0] is set to 1 (a plain store of the one value from any number of waves;
  *                       the caller zeroes it); the other records are copied.  Segments of no byte and of more than 65,535
  *                       bytes are fine; n = 0 and an empty window launch nothing
+ *   svx_record_retid    the reference indices of n BAM records rewritten in place through a table (svision_amd/sort.py: several
+ *                       inputs merged into one file, d_map [n_in] = every reference index of one input in the merged dictionary).
+ *                       Record r starts at d_bytes + d_off[r], at its block_size field -- any byte offset, at least 36 bytes --;
+ *                       refID is the little-endian int32 at byte 4, next_refID the one at byte 24.  Each field: -1 stays -1,
+ *                       0 <= v < n_in becomes d_map[v]; a record with a field outside that keeps BOTH fields as they are and
+ *                       d_status[0] is set to 1 (a plain store of the one value; the caller zeroes it).  d_tid_key [n] (may be
+ *                       NULL): the records' sort keys, translated by the same rule.  A lane per record in a grid-stride loop,
+ *                       byte loads and stores: only bytes 4..7 and 24..27 of a record are touched, nothing is read behind
+ *                       d_off[n - 1] + 28.  n = 0 launches nothing; n_in = 0: every field other than -1 is reported
  * No atomics in any of them: the output is a pure function of the input.  n = 0 is fine everywhere (d_off_out[0] = 0). */
 #define SVX_RECORD_SORT_TILE 2048u
 size_t         svx_record_sort_ws_bytes(uint32_t n);
@@ -504,6 +513,8 @@ int            svx_record_invert(const uint32_t* d_order, uint32_t n, uint32_t* 
 int            svx_record_scatter_segments(const void* d_src, const int64_t* d_src_off, const uint32_t* d_rank, uint32_t rank_lo,
                                            uint32_t rank_hi, const int64_t* d_off_out, int64_t out_base, void* d_dst, uint32_t n,
                                            int32_t* d_status, void* stream);
+int            svx_record_retid(void* d_bytes, const int64_t* d_off, uint32_t n, const int32_t* d_map, int32_t n_in, int32_t* d_tid_key,
+                                int32_t* d_status, void* stream);
 /* BGZF members FROM inflated bytes (svx_deflate.hip; ABI 420, additive): the encoder of svision_amd/sort.py, which writes the
  * device-sorted BAM.
  *   svx_bgzf_deflate    block b = the bytes d_in[d_in_off[b] .. d_in_off[b + 1]) -- any offsets, no alignment, 0 .. 0xFF00 bytes a block --

@@ -224,18 +224,20 @@ def _write_sorted(options):
     one has not touched the device when the helpers of ``-t N`` are forked.  It inherits the environment: ``SVX_SORT_TABLES=dynamic``
     there is ``--tables dynamic`` (Huffman codes built per block; default: the fixed code), ``SVX_SORT_MEMORY=BYTES`` (K, M or G) is
     ``--memory``: the device memory for the records' inflated bytes, beyond which the file is written in spans, a pass over the input
-    for each (default: half of the free device memory)."""
+    for each (default: half of the free device memory).  ``-b a.bam,b.bam,c.sam`` (:func:`_input_list`): the inputs merged into the one sorted
+    file ``OUT/<first input's stem>.merged.sorted.bam``."""
     import json
     import subprocess
     import sys
     import time
     t0 = time.perf_counter()
-    name = os.path.basename(options.bam_path)
-    out = os.path.join(options.out_path, (name[:-4] if name.endswith((".bam", ".sam")) else name) + ".sorted.bam")
+    inputs = _input_list(options.bam_path) or [options.bam_path]       # several: merged into OUT/<first input's stem>.merged.sorted.bam
+    name = os.path.basename(inputs[0])
+    out = os.path.join(options.out_path, (name[:-4] if name.endswith((".bam", ".sam")) else name) + (".merged" if len(inputs) > 1 else "") + ".sorted.bam")
     stats_path = out + ".stats.json"
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, PYTHONPATH=os.pathsep.join([root] + [p for p in os.environ.get("PYTHONPATH", "").split(os.pathsep) if p]))
-    r = subprocess.run([sys.executable, "-m", "svision_amd.sort", options.bam_path, "-o", out, "--stats-json", stats_path,
+    r = subprocess.run([sys.executable, "-m", "svision_amd.sort"] + inputs + ["-o", out, "--stats-json", stats_path,
                         "--device", "cuda:%d" % int(os.environ.get("LOCAL_RANK", "0"))], capture_output=True, text=True, env=env)
     try:
         if r.stderr.strip():                                        # the child's whole stderr (a traceback with its context) for the log
@@ -249,7 +251,7 @@ def _write_sorted(options):
         if os.path.exists(stats_path):
             os.unlink(stats_path)
     logging.info("%s is %s: %d records sorted on the device in %.2f s (%d range(s), %d radix passes)", options.bam_path,
-                 "SAM text" if stats.get("input") == "sam" else "not coordinate sorted", stats["records"], time.perf_counter() - t0,
+                 "%d inputs to merge" % len(inputs) if len(inputs) > 1 else "SAM text" if stats.get("input") == "sam" else "not coordinate sorted", stats["records"], time.perf_counter() - t0,
                  stats["ranges"], stats["passes"])
     logging.info("sorted file: %s (+ .bai), %d BGZF blocks, %d -> %d bytes, written in %d span(s) under a budget of %d bytes for the records "
                  "(SVX_SORT_MEMORY)", out, stats["blocks"], stats["inflated_bytes"], stats["compressed_bytes"], stats["spans"], stats["memory_bytes"])
@@ -259,6 +261,14 @@ def _write_sorted(options):
 # What a run reads.  ``sample``: the resident Sample (handed in, or sorted on the device), None when the file is streamed chromosome by
 # chromosome; ``index`` / ``build_index``: the streamed file's .bai, or that it is to be built on the device (both unset for a Sample).
 RunInput = collections.namedtuple("RunInput", "sample fasta references lengths index build_index")
+
+
+def _input_list(bam_path):
+    """A ``-b`` value that names no existing file, but whose comma-separated parts all do -> those files (absolute paths); else None."""
+    if os.path.exists(bam_path) or "," not in bam_path:
+        return None
+    parts = [os.path.abspath(p) for p in bam_path.split(",")]
+    return parts if all(os.path.isfile(p) for p in parts) else None
 
 
 def _is_sam_text(path):
@@ -280,8 +290,13 @@ def _open_input(options, sample, ws, tick):
     from .io.bam import find_index, read_bam_header
     if sample is None:
         # file-driven run: header now, the records chromosome by chromosome while the pipeline runs (ingest.ChromosomeFeed)
+        several = _input_list(options.bam_path)
+        if several and os.environ.get("SVX_DEVICE_SORT") != "write":
+            logging.error("-b names %d files: SVX_DEVICE_SORT=write merges them into one sorted BAM on the device (one rank); every other setting "
+                          "takes one file -- merge them first with `python -m svision_amd.sort %s -o merged.bam`", len(several), " ".join(several))
+            raise SystemExit(1)
         # (SAM text under SVX_DEVICE_SORT=write takes the road of an unsorted BAM; every other setting reads it as a BAM and refuses it)
-        head = None if os.environ.get("SVX_DEVICE_SORT") == "write" and _is_sam_text(options.bam_path) else read_bam_header(options.bam_path)
+        head = None if several or os.environ.get("SVX_DEVICE_SORT") == "write" and _is_sam_text(options.bam_path) else read_bam_header(options.bam_path)
         if head is not None and head.sort_order == "coordinate":
             fasta = Fasta(options.genome)
             index = find_index(options.bam_path)
@@ -296,7 +311,7 @@ def _open_input(options, sample, ws, tick):
             if ws > 1:
                 # (every rank would write the same file; one sort in front of the launch serves them all)
                 logging.error("SVX_DEVICE_SORT=write sorts an unsorted BAM in a single-rank run only: write the sorted file first with "
-                              "`python -m svision_amd.sort %s -o sorted.bam` and start the %d ranks on it", options.bam_path, ws)
+                              "`python -m svision_amd.sort %s -o sorted.bam` and start the %d ranks on it", " ".join(several or [options.bam_path]), ws)
                 raise SystemExit(1)
             options.bam_path = _write_sorted(options)
             tick("unsorted BAM: sorted file written on the device")

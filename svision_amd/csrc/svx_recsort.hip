@@ -26,6 +26,8 @@
 //                               larger than the device): a WAVE per INPUT record; where the record's rank lies in the window
 //                               [rank_lo, rank_hi) its bytes go to off_out[rank] - out_base, by the copy routine of
 //                               svx_recsort_core.hpp (the gather's alignment rule); the other waves leave at once
+//   svx_record_retid            a LANE per record rewrites its refID and next_refID through a table (several inputs merged into one
+//                               file, svision_amd/sort.py: each input's indices into the merged dictionary), byte by byte in place
 // No atomics, no cross-workgroup dependency inside a launch: the output is a pure function of the input, identical in every run.
 // A counter in LDS is written by ONE lane a round (the leader of its digit, in the wave's own row) with a barrier behind it.
 #include <hip/hip_runtime.h>
@@ -43,6 +45,7 @@ static_assert(SORT_BLOCK == RADIX, "thread d sums digit d");
 constexpr int SCAN_BLOCK = 256, SCAN_ITEMS = 4, SCAN_WAVES = SCAN_BLOCK / WAVE;
 constexpr uint32_t SCAN_CHUNK = SCAN_BLOCK * SCAN_ITEMS;         // values a workgroup of the scan takes
 constexpr int SEG_WAVES = 4;                                    // gather_segments: four records a workgroup, a wave each
+constexpr uint64_t RETID_MAX_BLOCKS = 2048;                     // record_retid: workgroups of 256 lanes (256 CUs x 8); more records: the grid-stride loop
 
 __host__ __device__ inline uint64_t pad16(uint64_t v) { return (v + 15) / 16 * 16; }
 
@@ -328,6 +331,17 @@ void scatter_segments_kernel(const uint8_t* __restrict__ src, const int64_t* __r
     svx_recsort::scatter_record(src, src_off, rank, rank_lo, rank_hi, off_out, out_base, dst, i, threadIdx.x & 63u, status);
 }
 
+// A lane per record in a grid-stride loop: two fields of four bytes each, at whatever offset the record lies (svx_recsort_core.hpp).
+// Two cache lines a record and nothing to share between lanes: the launch is bound by the latency of those loads, not by bandwidth.
+__global__ __launch_bounds__(256)
+void record_retid_kernel(uint8_t* __restrict__ bytes, const int64_t* __restrict__ off, uint32_t n, const int32_t* __restrict__ map, int32_t n_in,
+                         int32_t* __restrict__ tid_key, int32_t* __restrict__ status)
+{
+    const uint64_t step = (uint64_t)gridDim.x * 256;
+    for (uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x; r < n; r += step)
+        svx_recsort::retid_record(bytes, off, map, n_in, tid_key, r, status);
+}
+
 struct SortWs {
     uint64_t* key[2];
     uint32_t* idx;
@@ -455,5 +469,17 @@ extern "C" int svx_record_scatter_segments(const void* d_src, const int64_t* d_s
     const dim3 grid((uint32_t)(((uint64_t)n + SEG_WAVES - 1) / SEG_WAVES));
     hipLaunchKernelGGL(scatter_segments_kernel, grid, dim3(WAVE * SEG_WAVES), 0, static_cast<hipStream_t>(stream),
                        static_cast<const uint8_t*>(d_src), d_src_off, d_rank, rank_lo, rank_hi, d_off_out, out_base, static_cast<uint8_t*>(d_dst), n, d_status);
+    return hipGetLastError() == hipSuccess ? SVX_OK : SVX_ELAUNCH;
+}
+
+extern "C" int svx_record_retid(void* d_bytes, const int64_t* d_off, uint32_t n, const int32_t* d_map, int32_t n_in, int32_t* d_tid_key,
+                                int32_t* d_status, void* stream)
+{
+    if (n_in < 0) return SVX_EINVAL;
+    if (n == 0) return SVX_OK;
+    if (!d_bytes || !d_off || !d_status || (n_in > 0 && !d_map)) return SVX_EINVAL;
+    const uint64_t blocks = ((uint64_t)n + 255) / 256;
+    hipLaunchKernelGGL(record_retid_kernel, dim3((uint32_t)(blocks < RETID_MAX_BLOCKS ? blocks : RETID_MAX_BLOCKS)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), static_cast<uint8_t*>(d_bytes), d_off, n, d_map, n_in, d_tid_key, d_status);
     return hipGetLastError() == hipSuccess ? SVX_OK : SVX_ELAUNCH;
 }

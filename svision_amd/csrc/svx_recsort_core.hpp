@@ -1,5 +1,6 @@
-// svx_recsort_core.hpp -- a lane's share of scatter_segments_kernel (svx_recsort.hip), host- and device-compilable: the host
-// program tools/hostwave/scatter_main.cpp runs this very code, lane by lane, under AddressSanitizer.
+// svx_recsort_core.hpp -- a lane's share of scatter_segments_kernel and of record_retid_kernel (svx_recsort.hip), host- and
+// device-compilable: the host programs tools/hostwave/scatter_main.cpp and retid_main.cpp run this very code, lane by lane, under
+// AddressSanitizer.
 //
 // A wave of 64 lanes copies one segment.  The DESTINATION decides the alignment, as in gather_segments_kernel: single bytes up to
 // its first dword boundary, whole dwords -- each assembled from the one or two aligned source dwords that hold its bytes --,
@@ -52,6 +53,50 @@ SVX_RS_HD void scatter_record(const uint8_t* src, const int64_t* src_off, const 
         return;
     }
     copy_segment(src + src_off[i], dst + (off_out[r] - out_base), (uint64_t)len, lane);
+}
+
+// ---- record_retid_kernel's share of one record (tools/hostwave/retid_main.cpp runs it under AddressSanitizer) ----
+// A BAM record's two reference indices are little-endian int32 at bytes 4 (refID) and 24 (next_refID) behind its block_size field.
+// Records start at any byte offset, so the fields are read and written byte by byte: no access leaves bytes 4..7 and 24..27.
+SVX_RS_HD int32_t load_le32(const uint8_t* p)
+{
+    return (int32_t)((uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24);
+}
+
+SVX_RS_HD void store_le32(uint8_t* p, int32_t value)
+{
+    const uint32_t v = (uint32_t)value;
+    p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); p[2] = (uint8_t)(v >> 16); p[3] = (uint8_t)(v >> 24);
+}
+
+// -1 stays -1, 0 <= v < n_in becomes map[v] -> true; anything else: false, *out untouched.
+SVX_RS_HD bool retid_value(int32_t v, const int32_t* map, int32_t n_in, int32_t* out)
+{
+    if (v == -1) { *out = -1; return true; }
+    if (v < 0 || v >= n_in) return false;
+    *out = map[v];
+    return true;
+}
+
+// The lane of record r: both fields through `map`, and tid_key[r] where it is given.  A field outside [-1, n_in) leaves BOTH
+// fields of the record as they are and sets *status (a plain store of the one value); a key outside likewise stays.
+SVX_RS_HD void retid_record(uint8_t* bytes, const int64_t* off, const int32_t* map, int32_t n_in, int32_t* tid_key, uint64_t r,
+                            int32_t* status)
+{
+    uint8_t* rec = bytes + off[r];
+    const int32_t tid = load_le32(rec + 4), next = load_le32(rec + 24);
+    int32_t new_tid, new_next;
+    if (retid_value(tid, map, n_in, &new_tid) && retid_value(next, map, n_in, &new_next)) {
+        if (new_tid != tid) store_le32(rec + 4, new_tid);
+        if (new_next != next) store_le32(rec + 24, new_next);
+    } else {
+        *status = 1;
+    }
+    if (tid_key) {
+        int32_t key;
+        if (retid_value(tid_key[r], map, n_in, &key)) tid_key[r] = key;
+        else *status = 1;
+    }
 }
 
 }  // namespace svx_recsort

@@ -198,7 +198,7 @@ class RecordRange:
     as the device arrays svx_bam_walk_extract(_seq) filled (None where ``n_rec`` is 0).  ``d_starts`` / ``n_starts`` / ``d_base``: what
     the walk kernels took.  ``before``: the clock's stage times when the range was begun."""
     d_tid = d_pos = d_flag = d_mapq = d_l_seq = d_cig_off = d_cigar = d_name_off = d_names = d_seq_off = d_seq = None
-    d_starts = d_base = None
+    d_starts = d_base = d_rec_off = None
     n_starts = n_rec = words = name_bytes = seq_bytes = 0
 
 
@@ -398,7 +398,7 @@ def _index_fields(lib, torch, kernels, dev, rng, clock):
     """What the index wants of a range's records -> host arrays tid, pos, flag, reference span, byte offset in the range's stream."""
     if rng.n_rec == 0:
         return np.empty(0, np.int32), np.empty(0, np.int32), np.empty(0, np.uint16), np.empty(0, np.int32), np.empty(0, np.uint64)
-    d_rec_off = walk_offsets(lib, torch, kernels, dev, rng)
+    d_rec_off = rng.d_rec_off = walk_offsets(lib, torch, kernels, dev, rng)       # (kept with the range: svision_amd/sort.py rewrites records at them)
     clock.lap("walk")
     # the reference span of every record: the scan's statistics (a CG-tag record: of its real CIGAR); no gap is long enough to be listed
     scan = kernels.cigar_scan(rng.d_cigar, rng.d_cig_off, rng.d_pos, 0x7FFFFFFF, n_words=rng.words)

@@ -905,6 +905,30 @@ def record_scatter_segments(src, src_off, rank, rank_lo, rank_hi, off_out, out_b
     return out
 
 
+def record_retid(d_bytes, d_off, d_map, d_tid_key, status):
+    """The n = len(d_off) BAM records that start at d_bytes[d_off[r]] (uint8; int64 [n], any byte offsets): refID (byte 4) and
+    next_refID (byte 24) rewritten in place through ``d_map`` (int32 [n_in]) -- -1 stays, 0 <= v < n_in becomes d_map[v] --, and
+    ``d_tid_key`` (int32 [n] or None) by the same rule.  ``status``: int32 [1], set to 1 where a field lies outside (that record keeps
+    both fields).  Every record needs its first 28 bytes inside ``d_bytes``.  See include/svx.h svx_record_retid."""
+    lib = _lib.load()
+    for t, name in ((d_bytes, "d_bytes"), (d_off, "d_off"), (d_map, "d_map"), (status, "status")):
+        _require_cuda(t, name)
+    n = int(d_off.shape[0])
+    if d_bytes.dtype != torch.uint8 or d_off.dtype != torch.int64 or d_off.dim() != 1 or d_map.dtype != torch.int32 or d_map.dim() != 1 \
+            or status.dtype != torch.int32 or status.numel() < 1:
+        raise _lib.SvxError("d_bytes must be uint8, d_off int64 [n], d_map int32 [n_in], status int32 [1]")
+    if d_tid_key is not None:
+        _require_cuda(d_tid_key, "d_tid_key")
+        if d_tid_key.dtype != torch.int32 or d_tid_key.dim() != 1 or d_tid_key.shape[0] != n:
+            raise _lib.SvxError("d_tid_key must be int32 [n]")
+    if n > 0xFFFFFFFF:
+        raise _lib.SvxError("svx_record_retid takes up to 2^32 - 1 records")
+    _lib.check(lib.svx_record_retid(d_bytes.data_ptr(), d_off.data_ptr(), n, d_map.data_ptr() if d_map.numel() else None, int(d_map.shape[0]),
+                                    None if d_tid_key is None else d_tid_key.data_ptr(), status.data_ptr(), _stream_ptr(d_bytes.device)),
+               "svx_record_retid")
+    return d_bytes
+
+
 # ---- BGZF members from inflated bytes (svx_deflate.hip; the writer: svision_amd/sort.py) ----
 BGZF_SLOT = 65536                    # SVX_BGZF_SLOT: bytes of a member's slot in svx_bgzf_deflate's output
 BGZF_BLOCK_MAX = 0xFF00              # SVX_BGZF_BLOCK_MAX: the largest block the encoder takes (htslib's block size)

@@ -69,12 +69,36 @@ bytes, keys and fields come about -- and the two files are those of the same rec
             length than in the key pass, means the file changed: SortWriteError
 Compressed SAM (gzip, BGZF) and stdin are not taken: the text is read twice.
 
+Several inputs.  ``sort_bam([a.bam, b.sam, c.bam], out)`` -- ``python -m svision_amd.sort a.bam b.sam c.bam -o out.bam`` -- writes ONE sorted
+BAM of all their records, what ``samtools merge`` in front of the sort would have given: one BAM per SMRT cell, one SAM per FASTQ batch.
+The two files are, byte for byte, those of ONE unsorted BAM that holds the merged header and the inputs' records one input after the
+other, every reference index in the merged numbering; ties of (reference, position) therefore come out in list order, then file order:
+the stability of the one svx_record_sort over the inputs' keys end to end.
+
+  open      every input as above; :func:`merge_headers` (host, its rules stand there) gives the output's text, its dictionary -- the
+            union of the inputs' by name, in order of first appearance -- and per input the table old refID -> merged refID
+  key pass  input by input in list order, each with its own header, first record and ranges: a BAM is walked against ITS OWN
+            dictionary (svx_bam_find_starts validates against it).  Where its table is not the identity, svx_record_retid -- a lane a
+            record -- rewrites refID and next_refID of the range's records where they lie, and the sort's key with them, before the
+            slice is kept; the host's tid goes through the table in NumPy.  Identical dictionaries, or one that opens the merged
+            one: no launch.  A reference index outside the file's dictionary: SortWriteError.  SAM text is measured and encoded
+            against the MERGED names, so it needs no table, and a part without any header is usable beside one that has it
+  join      ranges, keys and offsets of all inputs end to end: ``ranges`` and ``range_records`` of the statistics run over all of them
+  spans     a span's ranges are read again input by input (``Source.again``), a BAM's records translated again before the scatter
+  room      all inputs BAM: the sum of their ISIZE-derived rooms is known before the passes, the stream is allocated once, as for one
+            file.  With SAM text among them the records' bytes are known only behind the key passes; they keep no byte, and a run
+            that fits then fills the stream input by input -- the text encoded as for one SAM file, a BAM's ranges READ A SECOND TIME
+            (``Source.fill``: the path of the spans without the scatter, one copy a range).  That second read is the price of a
+            mixed run (profiles/sort_merge.txt); an all-BAM run does not pay it
+A failure names the input it came from; "changed while it was sorted" names the input that changed.
+
 A corrupt block, a CRC mismatch, a malformed or cut chain, a device allocation or a write that fails raises SortWriteError (a
 ValueError); no file and no temporary is left behind.
 
-:func:`sort_bam` is the list of its steps, each a function of this module over named values: ``_open`` (header, first record and
-``room`` from one pass over the file's members: index.bgzf_members, index.header_place; it also chooses the :class:`Source`, BAM or
-SAM text: the key pass and the reading-again of a span's ranges) -> ``_key_pass`` -> ``_order`` -> the pieces,
+:func:`sort_bam` is the list of its steps, each a function of this module over named values: ``_open_all`` (per input ``_open``: header,
+first record and ``room`` from one pass over the file's members: index.bgzf_members, index.header_place; it also chooses the
+:class:`Source`, BAM or SAM text: the key pass, the reading-again of a span's ranges and the filling of a stream whose size was not
+known; several inputs: :func:`merge_headers`) -> ``_key_passes`` (per input its source's key pass, then ``_join``) -> ``_order`` -> the pieces,
 ``_pieces_in_core`` or ``_pieces_spanned``: generators of (device buffer, first byte, bytes), a chunk each -> :class:`BgzfWriter`,
 which owns the temporary file and the ledger of members and is handed its encoder (:class:`DeviceEncode`; zlib in the CPU tests) ->
 ``_bai`` -> :func:`commit_pair`.  Which records a chunk or a span takes is one rule, :func:`records_touching`; the 0xFF00 cut one
@@ -94,7 +118,7 @@ BLOCK = 0xFF00                                                  # htslib's block
 DEFAULT_CHUNK_BYTES = 1024 * BLOCK
 TABLES = ("fixed", "dynamic")                                   # the encoder: svx_bgzf_deflate / svx_bgzf_deflate_dyn
 STAGES = ("read", "upload", "inflate", "crc", "find_starts", "walk", "scan", "read_back", "keep", "join", "sort", "gather", "scatter", "deflate",
-          "pack", "download", "write", "index", "lines", "measure", "encode", "host_lines")
+          "pack", "download", "write", "index", "lines", "measure", "encode", "host_lines", "retid")
 SAM_READ_THREADS = 8                                            # svx_read_range's threads for a chunk of text
 DEFAULT_SAM_CHUNK_BYTES = 64 << 20                              # text bytes a chunk of a SAM input (``range_bytes``); see profiles/sort_sam.txt
 
@@ -115,6 +139,121 @@ def sorted_header_text(text):
         lines[0] = "\t".join(["@HD", vn, "SO:coordinate"] + rest)
         return "\n".join(lines)
     return "@HD\tVN:1.6\tSO:coordinate\n" + text
+
+
+MergedHeader = collections.namedtuple("MergedHeader", "text references lengths maps")
+
+
+def _line_fields(line):
+    """A header line's TAG:VALUE fields -> {tag: value} (the first of a tag counts)."""
+    out = {}
+    for f in line.split("\t")[1:]:
+        if len(f) > 2 and f[2] == ":":
+            out.setdefault(f[:2], f[3:])
+    return out
+
+
+def _with_fields(line, new):
+    """The line with the value of every field in ``new`` {tag: value} replaced, everything else as it is."""
+    return "\t".join(f[:3] + new[f[:2]] if i and len(f) > 2 and f[2] == ":" and f[:2] in new else f for i, f in enumerate(line.split("\t")))
+
+
+def merge_headers(parts):
+    """The headers of several inputs -> MergedHeader(the merged text, through :func:`sorted_header_text`; the merged references and
+    lengths; per input an int32 table ``map[old refID] -> merged refID``).  ``parts``: per input (its name for messages, the header
+    text, its references, their lengths) -- the dictionary a BAM carries in binary, a SAM in its @SQ lines; a headerless SAM part has
+    neither.  One input: its text through sorted_header_text and nothing else.  The rules:
+
+      @HD   the first input's (sorted_header_text: SO:coordinate; none: one is prepended); a later input's is dropped
+      @SQ   the union by SN in order of first appearance, the inputs taken in list order; the first occurrence's whole line is kept
+            (a reference a BAM's text has no line for gets ``@SQ SN LN``); the same SN with another LN: SortWriteError
+      @RG   the union by ID, an identical line once; the same ID on another line: SortWriteError (the records' RG:Z tags would have
+            to be rewritten)
+      @PG   the union by ID, an identical line once; the same ID on another line: the later input's line is renamed ID-<1-based input
+            number>, and the PP fields of that input's other @PG lines follow.  The records' PG:Z tags are NOT rewritten
+      other lines (@CO, ...): in input order, a line that is already there once
+    A later input's new line goes behind the last line of its type so far (no such line: to the end), so the types stay together."""
+    parts = [(name, text, list(refs), [int(v) for v in lens]) for name, text, refs, lens in parts]
+    if len(parts) == 1:
+        _name, text, refs, lens = parts[0]
+        return MergedHeader(sorted_header_text(text), refs, lens, [np.arange(len(refs), dtype=np.int32)])
+    out, seen, sq_seen = [], set(), set()                       # the merged lines, the lines that are there, the SN that have a line
+    tid_of, owner, references, lengths, maps = {}, {}, [], [], []
+    rg, pg = {}, {}                                             # ID -> (line, input's name)
+
+    def add(line):
+        at = next((i + 1 for i in range(len(out) - 1, -1, -1) if out[i][:3] == line[:3]), len(out))
+        out.insert(at, line)
+        seen.add(line)
+
+    for k, (name, text, refs, lens) in enumerate(parts, 1):
+        lines = [l for l in text.split("\n") if l.strip("\0")]
+        # ---- the dictionary: the union by name, and this input's table
+        table = np.empty(len(refs), np.int32)
+        for i, (ref, n) in enumerate(zip(refs, lens)):
+            if ref not in tid_of:
+                tid_of[ref], owner[ref] = len(references), name
+                references.append(ref)
+                lengths.append(n)
+            elif lengths[tid_of[ref]] != n:
+                raise SortWriteError("%s and %s name the reference %s with different lengths: %d and %d -- they were not aligned to the "
+                                     "same reference" % (owner[ref], name, ref, lengths[tid_of[ref]], n))
+            table[i] = tid_of[ref]
+        maps.append(table)
+        # ---- @PG: which IDs of this input take the suffix (a rename changes the PP of other lines, which may rename those too)
+        renamed = {}
+        while k > 1:
+            before = len(renamed)
+            for l in lines:
+                f = _line_fields(l) if l.startswith("@PG\t") else {}
+                new = _with_fields(l, {"PP": renamed[f["PP"]]}) if f.get("PP") in renamed else l
+                if f.get("ID") in pg and pg[f["ID"]][0] != new:
+                    renamed[f["ID"]] = "%s-%d" % (f["ID"], k)
+            if len(renamed) == before:
+                break
+        # ---- the lines: the first input's as they are, a later input's where they are new -- its new references first, in the
+        # dictionary's order, then the rest in the text's
+        sq_line = {}
+        for l in lines:
+            if l.startswith("@SQ\t"):
+                sq_line.setdefault(_line_fields(l).get("SN"), l)
+
+        def add_sq():
+            for ref in refs:
+                if ref not in sq_seen:
+                    add(sq_line.get(ref) or "@SQ\tSN:%s\tLN:%d" % (ref, lengths[tid_of[ref]]))
+                    sq_seen.add(ref)
+        if k > 1:
+            add_sq()
+        for i, l in enumerate(lines):
+            kind, f = l[:3], _line_fields(l)
+            if kind == "@HD":
+                if k == 1 and i == 0:
+                    out.append(l)
+                continue
+            if kind == "@SQ":
+                if k > 1:
+                    continue
+                sq_seen.add(f.get("SN"))
+            if kind == "@RG" and "ID" in f:
+                if k > 1 and f["ID"] in rg and rg[f["ID"]][0] != l:
+                    raise SortWriteError("%s and %s both have a read group %s, on different @RG lines -- one of them would need its records' "
+                                         "RG:Z tags rewritten, which this tool does not do: give the read groups distinct IDs"
+                                         % (rg[f["ID"]][1], name, f["ID"]))
+                rg.setdefault(f["ID"], (l, name))
+            if kind == "@PG" and "ID" in f:
+                change = {t: renamed[f[t]] for t in ("ID", "PP") if f.get(t) in renamed}
+                l = _with_fields(l, change) if change else l
+                pg.setdefault(renamed.get(f["ID"], f["ID"]), (l, name))
+            if k == 1:
+                out.append(l)
+                seen.add(l)
+            elif l not in seen:
+                add(l)
+        add_sq()                                                # (the first input's dictionary entries that its text has no line for)
+    if not references:
+        raise SortWriteError("%s: no input has an @SQ line: a BAM needs its reference dictionary" % parts[0][0])
+    return MergedHeader(sorted_header_text("\n".join(out) + "\n"), references, lengths, maps)
 
 
 def inflated_size(path):
@@ -330,14 +469,54 @@ class DeviceEncode:
         return packed, m, stored, dynamic
 
 
-Opened = collections.namedtuple("Opened", "path head first header room source", defaults=(None,))
-# The input's kind, chosen at open: ``key_pass(dv, opened, budget, range_bytes, kp) -> (opened with its room known, spanned)`` and
-# ``again(dv, opened, kp, need) -> per range of ``need`` (k, records completed, device bytes, the records' offsets in them [n + 1])``,
-# the ranges of the key pass read once more for a span.
-Source = collections.namedtuple("Source", "name key_pass again")
+# ``remap``: None, or the int32 table of :func:`merge_headers` that takes the input's reference indices into the merged dictionary
+# (a BAM input of several whose table is not the identity: svx_record_retid).
+Opened = collections.namedtuple("Opened", "path head first header room source remap", defaults=(None, None))
+# The input's kind, chosen at open: ``key_pass(dv, opened, range_bytes, kp, d_stream)``: the input's ranges -> ``kp`` (the input's own
+# KeyPass) filled, the records' bytes kept in ``d_stream`` from byte ``kp.base`` on where it is given; ``again(dv, opened, kp, need) ->
+# per range of ``need`` (k, records completed, device bytes, the records' offsets in them [n + 1])``, the ranges of the key pass read
+# once more for a span; ``fill(dv, opened, kp)``: the input's records written into ``kp.d_stream`` behind the key passes (a run in one
+# piece whose ``room`` was not known before them).
+Source = collections.namedtuple("Source", "name key_pass again fill")
+# Every input opened, and the one file they make: ``merged`` is an Opened whose head (references, lengths), header bytes and room are
+# the output's -- of one input: that input's own --, ``label`` names the inputs in a message.
+Inputs = collections.namedtuple("Inputs", "opened merged label")
+MergedHead = collections.namedtuple("MergedHead", "references lengths")
 
 
-def _open(bam_path):
+def input_paths(bam_path):
+    """sort_bam's first argument -> the list of paths: a str is one input, a list or tuple several; none: ValueError."""
+    if isinstance(bam_path, (str, bytes, os.PathLike)):
+        return [os.fsdecode(bam_path)]
+    paths = [os.fsdecode(p) for p in bam_path]
+    if not paths:
+        raise ValueError("sort_bam: an empty list of inputs")
+    return paths
+
+
+def _open_all(paths):
+    """open, every input: -> Inputs.  One input: as it is opened.  Several: the headers merged (:func:`merge_headers`) -- a SAM part
+    takes the merged dictionary for its own, so its records are encoded in the merged numbering and a part without header is
+    usable; a BAM part whose table is not the identity carries it as ``remap`` --, ``room`` the sum where every part's is known."""
+    from .io import sam
+    if len(paths) == 1:
+        opened = _open(paths[0])
+        return Inputs([opened], opened, paths[0])
+    opened = [_open(p, alone=False) for p in paths]
+    merged = merge_headers([(o.path, o.head.text if o.source is SAM_SOURCE else o.head.header_text, o.head.references, o.head.lengths) for o in opened])
+    for i, o in enumerate(opened):
+        if o.source is SAM_SOURCE:
+            opened[i] = o._replace(head=sam.SamHead(merged.references, merged.lengths, o.head.text, o.head.sort_order))
+        elif not np.array_equal(merged.maps[i], np.arange(len(merged.maps[i]))):       # (a dictionary that opens the merged one: nothing to rewrite)
+            opened[i] = o._replace(remap=merged.maps[i])
+    header = sam.bam_header_bytes(sam.SamHead(merged.references, merged.lengths, merged.text, "coordinate"))
+    rooms = [o.room for o in opened]
+    label = "%s (+ %d more)" % (paths[0], len(paths) - 1)
+    return Inputs(opened, Opened(label, MergedHead(merged.references, merged.lengths), None, header,
+                                 None if None in rooms else sum(rooms), None), label)
+
+
+def _open(bam_path, alone=True):
     """open: -> Opened(the path, read_bam_header's table, first_record's (file offset, entry, references), the header's bytes as the
     output takes them, ``room``: the records' inflated bytes by the members' ISIZE fields) -- one pass over the file's members.  SAM
     text (a first byte ``@``, or a first line of 11 tab-separated fields): :func:`_open_sam`."""
@@ -349,7 +528,7 @@ def _open(bam_path):
     except OSError as exc:
         raise SortWriteError("%s: %s" % (bam_path, exc)) from None
     if sam.is_sam_text(start):
-        return _open_sam(bam_path)
+        return _open_sam(bam_path, alone)
     if start[:2] == b"\x1f\x8b":
         try:
             magic = zlib.decompressobj(31).decompress(start, 4)
@@ -371,12 +550,15 @@ def _open(bam_path):
     return Opened(bam_path, head, tuple(place[:3]), header, room, BAM_SOURCE)
 
 
-def _open_sam(path):
+def _open_sam(path, alone=True):
     """open, SAM text: -> Opened(the path, the header's references and lengths (io.sam.SamHead), the file offset of the first alignment
-    line, the output's header bytes, ``room`` None: the records' bytes are known behind the key pass)."""
+    line, the output's header bytes, ``room`` None: the records' bytes are known behind the key pass).  One of several inputs
+    (``alone`` unset) may have no @SQ line: the other parts' dictionary serves it."""
     from .io import sam
     try:
         text = sam.header_end(path)
+        if not alone and not any(l.startswith(b"@SQ\t") for l in text.split(b"\n")):
+            return Opened(path, sam.SamHead([], [], text.decode("latin-1"), None), (len(text), text.count(b"\n")), None, None, SAM_SOURCE)
         head = sam.parse_header(text)
         header = sorted_header_bytes(sam.bam_header_bytes(head))
     except (sam.SamError, OSError) as exc:
@@ -392,19 +574,37 @@ class KeyPass:
     ``host_lens`` per chunk the lines' lengths as svx_sam_encode takes them (negative: the host's line), ``host_records`` {record
     number: the bytes io.sam encoded}, ``sam_table``: the device's reference names, ``pinned``: the host buffer a chunk is read into."""
 
-    def __init__(self):
+    def __init__(self, base=0):
         self.range_records, self.places, self.seen, self.n = [], [], 0, 0
         self.host_lens, self.host_records, self.sam_table, self.pinned = [], {}, None, None
         self.tid = self.pos = self.flag = self.span = self.d_tid = self.d_pos = self.off_in = self.d_off_in = self.d_stream = None
+        # Several inputs: the run's KeyPass holds the joined arrays and, in ``parts``, per input (its Opened, its own KeyPass, the
+        # number of its first range and of its first record in the run); an input's own KeyPass has its ranges, what the join takes of
+        # them (``host``, ``d_keys``, ``lens``: per range the host fields, the device keys, the records' lengths), ``base``: the stream
+        # offset of its first record, and behind the join its slices of ``off_in`` / ``d_off_in`` -- offsets in the one stream.
+        # ``reading``: the input that is being read, for a failure's message.
+        self.parts, self.host, self.d_keys, self.lens, self.base, self.reading, self.d_map = [], [], [], [], base, None, None
 
 
-def _key_pass(dv, opened, spanned, range_bytes, kp):
-    """key pass: every range of the file (index.record_ranges) -> ``kp`` filled.  The record stream is allocated once, by the ISIZE sum
-    (4 readable bytes behind it: the gather's aligned loads), and every range's slice goes straight to its place in it; ``spanned``:
-    no byte is kept."""
+def _retid(dv, opened, kp, d_bytes, d_off, d_tid_key):
+    """The records at ``d_off`` in ``d_bytes`` of an input whose reference indices are not the merged dictionary's: refID and next_refID
+    -- and the sort's key -- through the input's table (svx_record_retid)."""
+    torch = dv.torch
+    if kp.d_map is None:
+        kp.d_map = torch.from_numpy(np.ascontiguousarray(opened.remap, np.int32)).to(dv.dev)
+    d_status = torch.zeros(1, dtype=torch.int32, device=dv.dev)
+    dv.kernels.record_retid(d_bytes, d_off, kp.d_map, d_tid_key, d_status)
+    bad = int(d_status.item())
+    dv.clock.lap("retid")
+    if bad:
+        raise SortWriteError("%s: a record's reference index is outside its file's dictionary (%d references)" % (opened.path, len(opened.remap)))
+
+
+def _key_pass(dv, opened, range_bytes, kp, d_stream):
+    """key pass of a BAM: every range of the file (index.record_ranges) -> ``kp`` filled.  ``d_stream``: the record stream, allocated
+    once by the ISIZE sum -- every range's slice goes straight to its place in it, from byte ``kp.base`` on --, or None: no byte is
+    kept.  An input with a ``remap``: the range's records and keys are translated where they lie (:func:`_retid`), the host's tid too."""
     torch, dev, clock, room = dv.torch, dv.dev, dv.clock, opened.room
-    kp.d_stream = None if spanned else torch.empty(room + 4, dtype=torch.uint8, device=dev)
-    host, d_keys, lens = [], [], []
     for rng in index.record_ranges(opened.path, opened.head, dev, clock, range_bytes, first=opened.first):
         kp.range_records.append(int(rng.n_rec))
         kp.places.append(rng.place)
@@ -413,22 +613,62 @@ def _key_pass(dv, opened, spanned, range_bytes, kp):
             first, last = int(rec_off[0]), int(rng.exit_off)
             if kp.seen + last - first > room:
                 raise SortWriteError("%s: more record bytes than its BGZF blocks' ISIZE fields add up to (%d)" % (opened.path, room))
-            host.append((tid, pos, flag, span))
-            lens.append(np.diff(np.append(rec_off, np.uint64(last)).astype(np.int64)))
-            d_keys.append((rng.d_tid, rng.d_pos))
-            if not spanned:
-                kp.d_stream[kp.seen:kp.seen + last - first].copy_(rng.d_raw[first:last])      # the records that complete in the range: contiguous there
+            if opened.remap is not None:
+                _retid(dv, opened, kp, rng.d_raw, rng.d_rec_off, rng.d_tid)
+                tid = np.where(tid >= 0, opened.remap[np.maximum(tid, 0)], tid).astype(np.int32)
+            kp.host.append((tid, pos, flag, span))
+            kp.lens.append(np.diff(np.append(rec_off, np.uint64(last)).astype(np.int64)))
+            kp.d_keys.append((rng.d_tid, rng.d_pos))
+            if d_stream is not None:
+                at = kp.base + kp.seen
+                d_stream[at:at + last - first].copy_(rng.d_raw[first:last])      # the records that complete in the range: contiguous there
             kp.seen += last - first
-        rng.d_raw = rng.d_starts = rng.d_base = rng.d_cigar = rng.d_cig_off = rng.d_names = rng.d_name_off = None
+        rng.d_raw = rng.d_starts = rng.d_base = rng.d_cigar = rng.d_cig_off = rng.d_names = rng.d_name_off = rng.d_rec_off = None
         del rng
         clock.lap("keep")
-    return _join(dv, opened, kp, host, d_keys, lens)
 
 
-def _join(dv, opened, kp, host, d_keys, lens):
-    """join: what the ranges left -- per range the host fields, the device keys and the records' lengths -> ``kp``'s arrays of the one
-    record stream."""
+def _key_passes(dv, ins, budget, range_bytes):
+    """key pass, every input in list order -> (the merged Opened with its ``room`` known, the run's KeyPass joined, ``spanned``).  Where
+    every input's ``room`` is known before (BAMs: the ISIZE sums), the records are kept as the passes go wherever they fit the budget.
+    With SAM text among the inputs ``room`` is exact only behind the passes: they keep no byte, and a run that fits then fills the
+    stream input by input (``Source.fill``: the text encoded, a BAM's ranges read a second time, one copy a range)."""
+    torch, dev = dv.torch, dv.dev
+    kp, merged = KeyPass(), ins.merged
+    known = merged.room is not None
+    spanned = known and merged.room > budget                    # the records do not fit: no byte is kept in the pass, the output is filled in spans
+    if known and not spanned:
+        kp.d_stream = torch.empty(merged.room + 4, dtype=torch.uint8, device=dev)      # (4 readable bytes behind it: the gather's aligned loads)
+    ranges = records = 0
+    for opened in ins.opened:
+        part = KeyPass(kp.seen)
+        kp.parts.append((opened, part, ranges, records))
+        kp.reading = opened.path
+        opened.source.key_pass(dv, opened, range_bytes, part, kp.d_stream)
+        kp.seen += part.seen
+        ranges, records = ranges + len(part.range_records), records + sum(part.range_records)
+    kp.reading = None
+    _join(dv, merged, kp)
+    if not known:
+        merged = merged._replace(room=int(kp.off_in[-1]))
+        spanned = merged.room > budget
+        if not spanned:
+            kp.d_stream = torch.empty(merged.room + 4, dtype=torch.uint8, device=dev)
+            kp.d_stream[merged.room:] = 0
+            for opened, part, _ranges, _records in kp.parts:
+                kp.reading, part.d_stream = opened.path, kp.d_stream
+                opened.source.fill(dv, opened, part)
+            kp.reading = None
+    return merged, kp, spanned
+
+
+def _join(dv, opened, kp):
+    """join: what the inputs' ranges left -- per range the host fields, the device keys and the records' lengths -> ``kp``'s arrays of
+    the one record stream, and every input's slices of the offsets."""
     torch, dev, clock = dv.torch, dv.dev, dv.clock
+    host, d_keys, lens = ([v for _o, part, _r, _n in kp.parts for v in getattr(part, name)] for name in ("host", "d_keys", "lens"))
+    kp.range_records = [v for _o, part, _r, _n in kp.parts for v in part.range_records]
+    kp.places = [v for _o, part, _r, _n in kp.parts for v in part.places]
     n = kp.n = int(sum(l.size for l in lens))
     if n > 0xFFFFFFFF:
         raise SortWriteError("%s: %d records -- svx_record_sort takes up to 2^32 - 1" % (opened.path, n))
@@ -447,6 +687,10 @@ def _join(dv, opened, kp, host, d_keys, lens):
         kp.tid = kp.pos = kp.span = np.empty(0, np.int32)
         kp.flag = np.empty(0, np.uint16)
     del d_keys, host, lens
+    for _o, part, _r, first in kp.parts:
+        part.n = int(sum(part.range_records))
+        part.off_in, part.d_off_in = kp.off_in[first:first + part.n + 1], kp.d_off_in[first:first + part.n + 1]
+        part.host, part.d_keys, part.lens = [], [], []
     clock.lap("join")
     return kp
 
@@ -506,35 +750,34 @@ def _pieces_spanned(dv, opened, kp, od, chunk_blocks, counts):
     rec_base = np.concatenate([[0], np.cumsum(np.asarray(kp.range_records, np.int64))])
     for sp in od.plan:
         d_span = torch.empty(sp.size, dtype=torch.uint8, device=dev)
-        d_status = torch.zeros(1, dtype=torch.int32, device=dev)
         need = span_ranges(od.rank, kp.range_records, sp.r_lo, sp.r_hi)
         clock.lap("scatter")
-        for k, n_rec, d_raw, d_src_off in opened.source.again(dv, opened, kp, need):
-            counts["span_range_reads"] += 1
-            if n_rec != kp.range_records[k]:
-                raise SortWriteError("%s changed while it was sorted: %d records complete in the range at file offset %d, %d did in the "
-                                     "first pass" % (opened.path, n_rec, kp.places[k][0], kp.range_records[k]))
-            kernels.record_scatter_segments(d_raw, d_src_off, od.d_rank[int(rec_base[k]):int(rec_base[k + 1])], sp.r_lo, sp.r_hi,
-                                            od.d_off_out, sp.base, d_span, d_status)
-            clock.lap("scatter")
-            del d_raw, d_src_off
-        if int(d_status.item()):
-            raise SortWriteError("%s changed while it was sorted: a record's length is not the one the first pass saw" % opened.path)
+        for part_of, part, first_range, _first_record in kp.parts:             # input by input: each reads its own ranges again
+            mine = need[(need >= first_range) & (need < first_range + len(part.range_records))] - first_range
+            d_status = torch.zeros(1, dtype=torch.int32, device=dev)
+            kp.reading = part_of.path
+            for k_own, n_rec, d_raw, d_src_off in part_of.source.again(dv, part_of, part, mine) if mine.size else ():
+                k = first_range + int(k_own)
+                counts["span_range_reads"] += 1
+                if n_rec != kp.range_records[k]:
+                    raise SortWriteError("%s changed while it was sorted: %d records complete in the range at file offset %d, %d did in the "
+                                         "first pass" % (part_of.path, n_rec, kp.places[k][0], kp.range_records[k]))
+                kernels.record_scatter_segments(d_raw, d_src_off, od.d_rank[int(rec_base[k]):int(rec_base[k + 1])], sp.r_lo, sp.r_hi,
+                                                od.d_off_out, sp.base, d_span, d_status)
+                clock.lap("scatter")
+                del d_raw, d_src_off
+            if mine.size and int(d_status.item()):
+                raise SortWriteError("%s changed while it was sorted: a record's length is not the one the first pass saw" % part_of.path)
+        kp.reading = None
         for lo, hi in chunk_cuts(sp.lo, sp.hi, chunk_blocks * BLOCK):
             yield d_span, lo - sp.base, hi - lo
         del d_span
 
 
 # ---- the sources: a BAM's ranges, a SAM's chunks of text ----
-def _bam_key_pass(dv, opened, budget, range_bytes, kp):
-    """key pass of a BAM: ``room`` is known from the members' ISIZE fields, so the records are kept as the pass goes wherever they fit."""
-    spanned = opened.room > budget                              # the records do not fit: no byte is kept in the pass, the output is filled in spans
-    _key_pass(dv, opened, spanned, range_bytes, kp)
-    return opened, spanned
-
-
 def _bam_again(dv, opened, kp, need):
-    """The ranges ``need`` of a BAM read again: read, inflate, CRC, find_starts, the walk's counts and offsets; nothing is extracted."""
+    """The ranges ``need`` of a BAM read again: read, inflate, CRC, find_starts, the walk's counts and offsets; nothing is extracted.
+    An input with a ``remap``: the range's records translated where they lie before they are handed on (:func:`_retid`)."""
     for k, rng in zip(need, index.record_ranges(opened.path, opened.head, dv.dev, dv.clock, places=[kp.places[k] for k in need], extract=False,
                                                 first=opened.first)):
         if rng.n_rec != kp.range_records[k]:
@@ -542,9 +785,27 @@ def _bam_again(dv, opened, kp, need):
             return
         d_src_off = index.walk_offsets(dv.lib, dv.torch, dv.kernels, dv.dev, rng, closed=True)
         dv.clock.lap("walk")
+        if opened.remap is not None:
+            _retid(dv, opened, kp, rng.d_raw, d_src_off[:rng.n_rec], None)
         yield k, rng.n_rec, rng.d_raw, d_src_off
         rng.d_raw = rng.d_starts = rng.d_base = None
         del rng, d_src_off
+
+
+def _bam_fill(dv, opened, kp):
+    """in one piece, a BAM beside SAM text (``room`` was not known before the key passes): the ranges that completed a record read a
+    second time, each range's records -- contiguous in the range and in the stream -- one copy."""
+    need = np.flatnonzero(np.asarray(kp.range_records, np.int64))
+    rec_base = np.concatenate([[0], np.cumsum(np.asarray(kp.range_records, np.int64))])
+    for k, n_rec, d_raw, d_src_off in _bam_again(dv, opened, kp, need) if need.size else ():
+        ends = [int(v) for v in d_src_off[[0, n_rec]].cpu()] if n_rec == kp.range_records[k] else None
+        at, end = int(kp.off_in[rec_base[k]]), int(kp.off_in[rec_base[k + 1]])
+        if ends is None or ends[1] - ends[0] != end - at:
+            raise SortWriteError("%s changed while it was sorted: the range at file offset %d does not complete the records it did in the "
+                                 "first pass" % (opened.path, kp.places[k][0]))
+        kp.d_stream[at:end].copy_(d_raw[ends[0]:ends[1]])
+        dv.clock.lap("keep")
+        del d_raw, d_src_off
 
 
 def _sam_chunk(dv, opened, kp, place, again=False):
@@ -577,16 +838,16 @@ def _sam_refuse(opened, tid_of, data, line_off, i, line_no, code):
     return SortWriteError("%s: line %d: not an alignment line (svx_sam_measure: %d)" % (opened.path, line_no, code))
 
 
-def _sam_key_pass(dv, opened, budget, range_bytes, kp):
+def _sam_key_pass(dv, opened, range_bytes, kp, d_stream=None):
     """key pass of SAM text: one pass over the chunks (io.sam.chunk_places: ``range_bytes`` of text, cut at line ends): svx_sam_lines,
     svx_sam_measure, the lengths and fields read back.  An error code raises with the file's line number; a line the kernels leave to the
     host (SVX_SAM_HOST) is encoded by io.sam at once -- its bytes kept in ``kp.host_records`` by record number, its length, key and
-    fields patched in.  ``room`` is exact behind the pass: -> (opened with it, spanned).  A run in one piece then reads the text once
-    more (:func:`_sam_fill`)."""
+    fields patched in.  No byte is kept: ``room`` is exact behind the pass, and a run in one piece then reads the text once more
+    (:func:`_sam_fill`)."""
     from .io import sam
     torch, kernels, dev, clock = dv.torch, dv.kernels, dv.dev, dv.clock
     tid_of, kp.sam_table = sam.tid_table(opened.head.references), kernels.sam_ref_table(opened.head.references, dev)
-    host, d_keys, lens = [], [], []
+    host, d_keys, lens = kp.host, kp.d_keys, kp.lens
     line_no, seen = opened.first[1], 0
     for place in sam.chunk_places(opened.path, opened.first[0], range_bytes or DEFAULT_SAM_CHUNK_BYTES):
         data, d_text, d_line_off, n_lines = _sam_chunk(dv, opened, kp, place)
@@ -625,12 +886,6 @@ def _sam_key_pass(dv, opened, budget, range_bytes, kp):
         line_no += n_lines
         del d_text, d_line_off, d_len, d_flag, d_span
         clock.lap("keep")
-    _join(dv, opened, kp, host, d_keys, lens)
-    opened = opened._replace(room=int(kp.off_in[-1]))
-    spanned = opened.room > budget
-    if not spanned:
-        _sam_fill(dv, opened, kp)
-    return opened, spanned
 
 
 def _sam_encode_chunk(dv, opened, kp, k, first, base, d_out, d_status):
@@ -659,10 +914,8 @@ def _sam_changed(opened, kp, k, n_lines):
 
 def _sam_fill(dv, opened, kp):
     """in one piece, SAM text: the second read of the text -- in the page cache for a file that fits the device --, every chunk encoded
-    straight into the resident stream at its records' offsets."""
+    straight into the resident stream (``kp.d_stream``) at its records' offsets."""
     torch, dev = dv.torch, dv.dev
-    kp.d_stream = torch.empty(opened.room + 4, dtype=torch.uint8, device=dev)
-    kp.d_stream[opened.room:] = 0
     d_status = torch.zeros(1, dtype=torch.int32, device=dev)
     first = 0
     for k, n_rec in enumerate(kp.range_records):
@@ -692,8 +945,8 @@ def _sam_again(dv, opened, kp, need):
         del d_local, d_src_off
 
 
-BAM_SOURCE = Source("bam", _bam_key_pass, _bam_again)
-SAM_SOURCE = Source("sam", _sam_key_pass, _sam_again)
+BAM_SOURCE = Source("bam", _key_pass, _bam_again, lambda dv, opened, kp: _bam_fill(dv, opened, kp))
+SAM_SOURCE = Source("sam", _sam_key_pass, _sam_again, lambda dv, opened, kp: _sam_fill(dv, opened, kp))     # (looked up at the call: tests replace it)
 
 
 def _bai(opened, kp, od, written):
@@ -718,22 +971,29 @@ def sort_bam(bam_path, out_path, device="cuda", range_bytes=None, chunk_bytes=No
     spans, a pass over the input for each (see the head of the module) -- the same two files.  ``stats``: a dict that receives
     ranges, records, blocks, stored_blocks, dynamic_blocks, compressed_bytes, inflated_bytes, chunks, spans (1: in one piece),
     span_range_reads (ranges read again over all spans; 0 in one piece), range_records (the records every range of the pass
-    completed), stream_bytes (the largest record buffer allocated) and the seconds per stage.  ``bam_path`` may be SAM text: then
-    ``range_bytes`` is the text bytes of a chunk, and stats also has input="sam" and host_lines, the lines io/sam.py encoded."""
+    completed), stream_bytes (the largest record buffer allocated), inputs, input_records (the records of every input), retid_inputs
+    (the inputs whose records were renumbered: svx_record_retid) and the seconds per stage.  ``bam_path`` may be SAM text: then
+    ``range_bytes`` is the text bytes of a chunk, and stats also has input="sam" and host_lines, the lines io/sam.py encoded.
+    ``bam_path`` may be a list or tuple of such paths: their records merged into the one sorted file (see "Several inputs" at the head
+    of the module); ranges and range_records run over all inputs in list order, host_lines is there when a part is SAM text, input only
+    when all are; a list of one path is that path, an empty one a ValueError."""
     from . import ingest_sort, kernels
+    paths = input_paths(bam_path)
     torch, lib, dev, clock = index.on_device("sort_bam needs the GPU (svx_record_sort, svx_bgzf_deflate)", device, STAGES)
     if tables not in TABLES:
         raise ValueError("tables: %r is none of %s" % (tables, ", ".join(TABLES)))
     dv = _Dev(torch, lib, kernels, dev, clock)
     chunk_blocks = max(int(chunk_bytes or DEFAULT_CHUNK_BYTES) // BLOCK, 1)
     budget = None if memory_bytes is None else max(int(memory_bytes), 1)
-    opened, kp, writer, counts = None, KeyPass(), None, {"span_range_reads": 0}
+    ins, opened, kp, writer, counts = None, None, KeyPass(), None, {"span_range_reads": 0}
+    bam_path = paths[0] if len(paths) == 1 else "%s (+ %d more)" % (paths[0], len(paths) - 1)       # (the inputs' name in a message)
     try:
-        opened = _open(bam_path)
+        ins = _open_all(paths)
+        opened = ins.merged
         with torch.cuda.device(dev):
             if budget is None:                                  # half of what is free: the rest is for a range, its inflate workspace, keys and chunks
                 budget = max(int(torch.cuda.mem_get_info(dev)[0]) // 2, 1)
-            opened, spanned = opened.source.key_pass(dv, opened, budget, range_bytes, kp)
+            opened, kp, spanned = _key_passes(dv, ins, budget, range_bytes)
             od = _order(dv, opened, kp, spanned, budget)
             pieces = _pieces_spanned if spanned else _pieces_in_core
             writer = BgzfWriter(out_path, DeviceEncode(dv, tables), clock, bam_path)
@@ -745,21 +1005,27 @@ def sort_bam(bam_path, out_path, device="cuda", range_bytes=None, chunk_bytes=No
             commit_pair(writer.tmp, out_path, _bai(opened, kp, od, written))
             clock.lap("index", False)
     except index.IndexBuildError as exc:
-        raise SortWriteError("%s: %s" % (bam_path, exc)) from None
+        raise SortWriteError("%s: %s" % (kp.reading or bam_path, exc)) from None
     except torch.cuda.OutOfMemoryError as exc:
         raise SortWriteError("%s: the device has no room for the file's records -- %d inflated record bytes in all, %d seen so far, a budget of "
                              "%s bytes for them; a smaller one (--memory, SVX_SORT_MEMORY; sort_bam's memory_bytes) writes the file in more "
-                             "spans (%s)" % (bam_path, kp.seen if opened.room is None else opened.room, kp.seen, budget, str(exc).split("\n")[0])) from None
+                             "spans (%s)" % (bam_path, kp.seen if opened is None or opened.room is None else opened.room, kp.seen, budget,
+                                             str(exc).split("\n")[0])) from None
     except _lib.SvxError as exc:
-        raise SortWriteError("%s: %s" % (bam_path, exc)) from None
+        raise SortWriteError("%s: %s" % (kp.reading or bam_path, exc)) from None
     except OSError as exc:
         raise SortWriteError("%s: writing %s failed (%s)" % (bam_path, out_path, exc)) from None
     finally:
         if writer is not None:
             writer.discard()
     if stats is not None:
-        if opened.source.name == "sam":
-            stats.update(input="sam", host_lines=len(kp.host_records))
+        sam_parts = [part for o, part, _r, _n in kp.parts if o.source is SAM_SOURCE]
+        if sam_parts:
+            stats.update(host_lines=sum(len(part.host_records) for part in sam_parts))
+            if len(sam_parts) == len(kp.parts):
+                stats.update(input="sam")
+        stats.update(inputs=len(kp.parts), input_records=[part.n for _o, part, _r, _n in kp.parts],
+                     retid_inputs=sum(o.remap is not None for o, _part, _r, _n in kp.parts))
         stats.update(ranges=len(kp.range_records), records=kp.n, blocks=written.blocks, stored_blocks=written.stored_blocks,
                      dynamic_blocks=written.dynamic_blocks, chunks=written.chunks, spans=od.spans, span_range_reads=counts["span_range_reads"],
                      range_records=kp.range_records, stream_bytes=od.stream_bytes, memory_bytes=budget,
@@ -773,7 +1039,7 @@ def main(argv=None):
     import argparse
     import json
     ap = argparse.ArgumentParser(prog="python -m svision_amd.sort", description="Write the coordinate-sorted BAM of an unsorted BAM or of SAM text, and its .bai, on the GPU.")
-    ap.add_argument("bam")
+    ap.add_argument("bam", nargs="+", help="an unsorted BAM or SAM text; several: their records merged into the one sorted file")
     ap.add_argument("-o", "--output", required=True, help="the sorted BAM to write (its index: OUTPUT + .bai)")
     ap.add_argument("--device", default="cuda")
     ap.add_argument("--chunk-bytes", type=int, default=None, help="inflated bytes a chunk of the output (default %d)" % DEFAULT_CHUNK_BYTES)
@@ -788,7 +1054,7 @@ def main(argv=None):
         ap.error("SVX_SORT_TABLES=%s: fixed or dynamic" % args.tables)
     stats = {}
     try:
-        path = sort_bam(args.bam, args.output, device=args.device, chunk_bytes=args.chunk_bytes, stats=stats, tables=args.tables,
+        path = sort_bam(args.bam[0] if len(args.bam) == 1 else args.bam, args.output, device=args.device, chunk_bytes=args.chunk_bytes, stats=stats, tables=args.tables,
                         memory_bytes=args.memory)
     except (SortWriteError, _lib.SvxError, OSError) as exc:
         print("svision_amd.sort: %s" % exc, file=sys.stderr)
@@ -800,6 +1066,9 @@ def main(argv=None):
           % (path, stats["records"], stats["blocks"],
              "%d stored" % stats["stored_blocks"] + (", %d dynamic" % stats["dynamic_blocks"] if args.tables == "dynamic" else ""),
              stats["inflated_bytes"], stats["compressed_bytes"], stats["ranges"], stats["chunks"], sum(stats["seconds"].values())))
+    if len(args.bam) > 1:
+        print("%s: %d inputs merged (records: %s), %d of them renumbered into the merged reference dictionary"
+              % (path, len(args.bam), ", ".join(str(v) for v in stats.get("input_records", [])), stats.get("retid_inputs", 0)))
     if stats.get("spans", 1) > 1:
         print("%s: the records exceed the budget of %d bytes (--memory): written in %d span(s), %d range(s) read again"
               % (path, stats["memory_bytes"], stats["spans"], stats["span_range_reads"]))
