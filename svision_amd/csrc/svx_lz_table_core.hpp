@@ -48,7 +48,8 @@ SVX_LZT_HD uint32_t n_words(uint32_t ph, uint32_t isize) { return round16(ph + i
 SVX_LZT_HD uint32_t n_chunks(uint32_t ph, uint32_t isize) { return round16(ph + isize) / 16u; }     // groups of 16 entries
 
 // where block b's sequence stream lies in the workspace of svx_bgzf_inflate_fast: 1.5 x the inflated bytes in front of it + 1 KB per block
-SVX_LZT_HD uint64_t slot_base(const uint64_t* dst_off, uint32_t b) { const uint64_t d = dst_off[b] - dst_off[0]; return d + (d >> 1) + 1024ull * b; }
+SVX_LZT_HD uint64_t slot_at(uint64_t d, uint32_t b) { return d + (d >> 1) + 1024ull * b; }      // d = the inflated bytes in front of block b
+SVX_LZT_HD uint64_t slot_base(const uint64_t* dst_off, uint32_t b) { return slot_at(dst_off[b] - dst_off[0], b); }
 
 // ---- build
 // thread t < 32 of the block: the entries in front of position 0 (t < 16) and behind position isize - 1 (t >= 16)
@@ -67,17 +68,22 @@ SVX_LZT_HD int batch_check(uint32_t W, uint32_t T, uint32_t isize, uint32_t L, u
 // one sequence whose first byte is position w: the match may reach back to the block's first byte, not further
 SVX_LZT_HD int seq_check(Seq s, uint32_t w) { return (s.ml && s.d > w + s.nl) ? LZ_BAD_DIST : LZ_OK; }
 
-// one checked sequence at position w, its first literal the block's l-th: w + nl + ml <= isize <= MAX_OUT, l + nl <= nlit
-SVX_LZT_HD void seq_write(uint16_t* tab, uint32_t ph, Seq s, uint32_t w, const uint8_t* lit_end, uint32_t l)
+// one checked sequence at position w, its first literal the block's l-th: w + nl + ml <= isize <= MAX_OUT, l + nl <= nlit.
+// `parts`: measurement builds only (SVX_LZT_DBG: 1 = the literal part, 2 = the match part; both everywhere else)
+SVX_LZT_HD void seq_write(uint16_t* tab, uint32_t ph, Seq s, uint32_t w, const uint8_t* lit_end, uint32_t l, uint32_t parts = 3u)
 {
     uint16_t* e = tab + ph + w;
     const uint8_t* q = lit_end - 1 - l;
-    SVX_LZT_ROLLED
-    for (uint32_t k = 0; k < s.nl; ++k) e[k] = (uint16_t)(MAX_OUT | q[-(int32_t)k]);
+    if (parts & 1u) {
+        SVX_LZT_ROLLED
+        for (uint32_t k = 0; k < s.nl; ++k) e[k] = (uint16_t)(MAX_OUT | q[-(int32_t)k]);
+    }
     e += s.nl;
     const uint32_t from = w + s.nl - s.d;
-    SVX_LZT_ROLLED
-    for (uint32_t k = 0; k < s.ml; ++k) e[k] = (uint16_t)(from + k);
+    if (parts & 2u) {
+        SVX_LZT_ROLLED
+        for (uint32_t k = 0; k < s.ml; ++k) e[k] = (uint16_t)(from + k);
+    }
 }
 
 // ---- resolve: one step of one thread = the 4 entries of word q (8-byte aligned; only this thread ever writes them).  Reads the

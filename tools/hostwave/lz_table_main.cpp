@@ -13,6 +13,9 @@
 // their size (the output behind a canary of `ph` bytes -- its neighbour's bytes, which must not change).
 //
 // usage: lz_table_host [file of BGZF blocks]...    (the crafted sequence streams always run)
+//        lz_table_host --count [file]...           the turns of the build's write loops, per block and per file, with every part
+//                                                  written by its sequence's thread and with the parts of 16 / 32 / 64 entries or
+//                                                  more written by the wave (count_block)
 #include <zlib.h>
 #include <cstdint>
 #include <cstdio>
@@ -234,6 +237,66 @@ static bool zlib_inflate(const uint8_t* src, size_t n, std::vector<uint8_t>& out
 
 struct Totals { long blocks = 0, skipped = 0, handed = 0; uint32_t max_rounds = 0; uint64_t rounds = 0, bytes = 0, reads = 0, writes = 0, seqs = 0, lits = 0; };
 
+// ---- counting mode: the turns of the build's write loops, by the sequence streams alone (nothing is written).  A turn = one
+// trip of a wave through a write loop, whatever the number of its lanes that are active in it.  Per batch of T sequences the
+// build lasts as long as its slowest wave (the others wait at the barrier), so a block's turns are the sum over its batches of
+// the largest value over the batch's waves of
+//   by owner (every part by its sequence's thread: the kernel)   longest literal part + longest match part in the wave
+//   LONG_RUN = R (parts of R entries or more by the whole wave,  longest literal part < R + longest match part < R in the wave
+//   64 entries a turn: counted, built, measured slower and not   + the sum over the wave's parts >= R of ceil(entries / 64)
+//   taken -- profiles/lz_table_build.txt)
+static const uint32_t THRESHOLDS[3] = {16, 32, 64}, WAVE = 64;
+struct Turns { uint64_t seqs = 0, bytes = 0, owner = 0, owner_lit = 0, owner_match = 0, scheme[3] = {0, 0, 0}, long_parts[3] = {0, 0, 0}, long_bytes[3] = {0, 0, 0}; };
+
+static Turns count_block(const Split& sp, uint32_t T)
+{
+    Turns c;
+    const uint32_t nseq = (uint32_t)sp.hdr.size();
+    c.seqs = nseq;
+    for (uint32_t s0 = 0; s0 < nseq; s0 += T) {
+        uint64_t worst_owner = 0, worst_lit = 0, worst_match = 0, worst[3] = {0, 0, 0};
+        for (uint32_t t0 = 0; t0 < T && s0 + t0 < nseq; t0 += WAVE) {
+            uint32_t max_nl = 0, max_ml = 0, short_nl[3] = {0, 0, 0}, short_ml[3] = {0, 0, 0};
+            uint64_t coop[3] = {0, 0, 0};
+            for (uint32_t t = t0; t < t0 + WAVE && s0 + t < nseq; ++t) {
+                const Seq s = unpack(sp.hdr[s0 + t]);
+                c.bytes += s.nl + s.ml;
+                if (s.nl > max_nl) max_nl = s.nl;
+                if (s.ml > max_ml) max_ml = s.ml;
+                for (int i = 0; i < 3; ++i) {
+                    if (s.nl >= THRESHOLDS[i]) { coop[i] += (s.nl + WAVE - 1) / WAVE; ++c.long_parts[i]; c.long_bytes[i] += s.nl; }
+                    else if (s.nl > short_nl[i]) short_nl[i] = s.nl;
+                    if (s.ml >= THRESHOLDS[i]) { coop[i] += (s.ml + WAVE - 1) / WAVE; ++c.long_parts[i]; c.long_bytes[i] += s.ml; }
+                    else if (s.ml > short_ml[i]) short_ml[i] = s.ml;
+                }
+            }
+            if ((uint64_t)max_nl + max_ml > worst_owner) { worst_owner = (uint64_t)max_nl + max_ml; worst_lit = max_nl; worst_match = max_ml; }
+            for (int i = 0; i < 3; ++i) { const uint64_t v = short_nl[i] + short_ml[i] + coop[i]; if (v > worst[i]) worst[i] = v; }
+        }
+        c.owner += worst_owner; c.owner_lit += worst_lit; c.owner_match += worst_match;
+        for (int i = 0; i < 3; ++i) c.scheme[i] += worst[i];
+    }
+    return c;
+}
+
+static void add(Turns& a, const Turns& b)
+{
+    a.seqs += b.seqs; a.bytes += b.bytes; a.owner += b.owner; a.owner_lit += b.owner_lit; a.owner_match += b.owner_match;
+    for (int i = 0; i < 3; ++i) { a.scheme[i] += b.scheme[i]; a.long_parts[i] += b.long_parts[i]; a.long_bytes[i] += b.long_bytes[i]; }
+}
+
+static void print_turns(const char* what, const Turns& c)
+{
+    printf("%s: sequences %llu, bytes %llu, turns by owner %llu (literals %llu + matches %llu)", what, (unsigned long long)c.seqs, (unsigned long long)c.bytes,
+           (unsigned long long)c.owner, (unsigned long long)c.owner_lit, (unsigned long long)c.owner_match);
+    for (int i = 0; i < 3; ++i)
+        printf("; LONG_RUN %u: turns %llu, long parts %llu, long bytes %llu", THRESHOLDS[i], (unsigned long long)c.scheme[i], (unsigned long long)c.long_parts[i],
+               (unsigned long long)c.long_bytes[i]);
+    printf("\n");
+}
+
+static bool g_count = false;                             // --count: the build's turns per block and per file, nothing else
+
 static void run_file(const char* path, Totals& tot)
 {
     FILE* f = fopen(path, "rb");
@@ -243,6 +306,7 @@ static void run_file(const char* path, Totals& tot)
     for (size_t k; (k = fread(tmp, 1, sizeof tmp, f)) > 0;) raw.insert(raw.end(), tmp, tmp + k);
     fclose(f);
     Totals t;
+    Turns turns;
     size_t p = 0;
     long index = 0;
     while (p + 18 <= raw.size()) {
@@ -263,6 +327,14 @@ static void run_file(const char* path, Totals& tot)
         if (!zlib_inflate(&raw[at], n, want) || want.size() != isize) { ++t.skipped; continue; }       // malformed: the tokens kernel's business
         Split sp;
         if (!deflate_to_split(&raw[at], n, sp)) { fail(std::string(path) + ": the parser refuses a block zlib takes"); continue; }
+        if (g_count) {
+            if (isize > MAX_OUT) { ++t.handed; continue; }
+            const Turns c = count_block(sp, 1024);
+            print_turns((std::string(path) + " block " + std::to_string(index - 1)).c_str(), c);
+            add(turns, c);
+            ++t.blocks;
+            continue;
+        }
         const uint32_t ph = (uint32_t)(index * 7 + 3) & 15u;
         const struct { uint32_t T; Order o; } modes[] = {{1024, LOCKSTEP}, {1024, REVERSE}, {512, FORWARD}};
         for (const auto& m : modes) {
@@ -273,6 +345,12 @@ static void run_file(const char* path, Totals& tot)
         }
         if (isize > MAX_OUT) { ++t.handed; continue; }
         ++t.blocks; t.bytes += isize; t.seqs += sp.hdr.size(); t.lits += sp.lit.size();
+    }
+    if (g_count) {
+        printf("%s: counted  blocks %ld (+ %ld malformed skipped, %ld above 0xFF00 handed over)\n", path, t.blocks, t.skipped, t.handed);
+        print_turns((std::string(path) + " in all").c_str(), turns);
+        tot.blocks += t.blocks;
+        return;
     }
     printf("%s: ok  blocks %ld (+ %ld malformed skipped, %ld above 0xFF00 handed over), sequences/block %.0f, literal bytes %.1f %%, rounds mean %.2f max %u, "
            "table reads/byte %.1f writes/byte %.2f\n", path, t.blocks, t.skipped, t.handed, t.blocks ? (double)t.seqs / t.blocks : 0.0,
@@ -310,6 +388,8 @@ static void crafted()
         cases.push_back(c);
         Case d = c; d.name = "distance_past_the_start"; d.sp.hdr = {H(3, 5, 4)}; d.want_status = LZ_BAD_DIST; d.want.clear();
         cases.push_back(d);
+        Case f = c; f.name = "long_match_past_the_start"; f.sp.hdr = {H(3, 258, 4)}; f.isize = 261; f.want_status = LZ_BAD_DIST; f.want.clear();
+        cases.push_back(f);
         Case e = c; e.name = "distance_past_the_start_second_batch"; e.sp.hdr.clear(); e.sp.lit.clear();
         for (uint32_t i = 0; i < 1500; ++i) { e.sp.hdr.push_back(H(1, 0, 1)); e.sp.lit.push_back('q'); }
         e.sp.hdr.push_back(H(0, 4, 1501)); e.isize = 1504; e.want_status = LZ_BAD_DIST; e.want.clear();
@@ -338,9 +418,11 @@ static void crafted()
 
 int main(int argc, char** argv)
 {
-    crafted();
+    g_count = argc > 1 && std::string(argv[1]) == "--count";
+    const int first = g_count ? 2 : 1;
+    if (!g_count) crafted();
     Totals tot;
-    for (int i = 1; i < argc; ++i) run_file(argv[i], tot);
-    printf("%ld blocks in %d files, %d failures\n", tot.blocks, argc - 1, g_failed);
+    for (int i = first; i < argc; ++i) run_file(argv[i], tot);
+    printf("%ld blocks in %d files, %d failures\n", tot.blocks, argc - first, g_failed);
     return g_failed ? 1 : 0;
 }
