@@ -32,7 +32,8 @@ def parse_arguments(arguments=None):
                                             "-b <input bam path> -g <reference> -m <model path>" % __version__)
     g = p.add_argument_group("Input/Output parameters")
     g.add_argument("-o", dest="out_path", type=os.path.abspath, required=True, help="Absolute path to output")
-    g.add_argument("-b", dest="bam_path", type=os.path.abspath, required=True, help="Absolute path to bam file")
+    g.add_argument("-b", dest="bam_path", type=_bam_arg, required=True, help="Absolute path to bam file; SVX_DEVICE_SORT=write: ``-`` is "
+                   "an aligner's output on standard input")
     g.add_argument("-m", dest="model_path", type=os.path.abspath, required=True, help="Absolute path to CNN predict model")
     g.add_argument("-g", dest="genome", type=os.path.abspath, required=True, help="Absolute path to your reference genome")
     g.add_argument("-n", dest="sample", type=str, required=True, help="Name of the BAM sample name")
@@ -232,13 +233,13 @@ def _write_sorted(options):
     import time
     t0 = time.perf_counter()
     inputs = _input_list(options.bam_path) or [options.bam_path]       # several: merged into OUT/<first input's stem>.merged.sorted.bam
-    name = os.path.basename(inputs[0])
+    name = "stdin" if inputs[0] == "-" else os.path.basename(inputs[0])
     out = os.path.join(options.out_path, (name[:-4] if name.endswith((".bam", ".sam")) else name) + (".merged" if len(inputs) > 1 else "") + ".sorted.bam")
     stats_path = out + ".stats.json"
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, PYTHONPATH=os.pathsep.join([root] + [p for p in os.environ.get("PYTHONPATH", "").split(os.pathsep) if p]))
     r = subprocess.run([sys.executable, "-m", "svision_amd.sort"] + inputs + ["-o", out, "--stats-json", stats_path,
-                        "--device", "cuda:%d" % int(os.environ.get("LOCAL_RANK", "0"))], capture_output=True, text=True, env=env)
+                        "--device", "cuda:%d" % int(os.environ.get("LOCAL_RANK", "0"))], capture_output=True, text=True, env=env)      # (``-``: the child inherits standard input)
     try:
         if r.stderr.strip():                                        # the child's whole stderr (a traceback with its context) for the log
             logging.debug("svision_amd.sort (exit status %d) wrote:\n%s", r.returncode, r.stderr.rstrip())
@@ -263,12 +264,18 @@ def _write_sorted(options):
 RunInput = collections.namedtuple("RunInput", "sample fasta references lengths index build_index")
 
 
+def _bam_arg(value):
+    """``-b``: an absolute path; ``-`` -- standard input, alone or as a part of a comma list -- stays as it is."""
+    return value if value == "-" or "-" in value.split(",") else os.path.abspath(value)
+
+
 def _input_list(bam_path):
-    """A ``-b`` value that names no existing file, but whose comma-separated parts all do -> those files (absolute paths); else None."""
-    if os.path.exists(bam_path) or "," not in bam_path:
+    """A ``-b`` value that names no existing file, but whose comma-separated parts all do -> those files (absolute paths); else None.
+    One part may be ``-``, standard input."""
+    if bam_path == "-" or os.path.exists(bam_path) or "," not in bam_path:
         return None
-    parts = [os.path.abspath(p) for p in bam_path.split(",")]
-    return parts if all(os.path.isfile(p) for p in parts) else None
+    parts = [p if p == "-" else os.path.abspath(p) for p in bam_path.split(",")]
+    return parts if parts.count("-") <= 1 and all(p == "-" or os.path.isfile(p) for p in parts) else None
 
 
 def _is_sam_text(path):
@@ -291,12 +298,16 @@ def _open_input(options, sample, ws, tick):
     if sample is None:
         # file-driven run: header now, the records chromosome by chromosome while the pipeline runs (ingest.ChromosomeFeed)
         several = _input_list(options.bam_path)
+        piped = options.bam_path == "-" or bool(several and "-" in several)
+        if piped and os.environ.get("SVX_DEVICE_SORT") != "write":
+            logging.error("-b -: standard input is taken under SVX_DEVICE_SORT=write only, which sorts an aligner's output on the device in one pass")
+            raise SystemExit(1)
         if several and os.environ.get("SVX_DEVICE_SORT") != "write":
             logging.error("-b names %d files: SVX_DEVICE_SORT=write merges them into one sorted BAM on the device (one rank); every other setting "
                           "takes one file -- merge them first with `python -m svision_amd.sort %s -o merged.bam`", len(several), " ".join(several))
             raise SystemExit(1)
         # (SAM text under SVX_DEVICE_SORT=write takes the road of an unsorted BAM; every other setting reads it as a BAM and refuses it)
-        head = None if several or os.environ.get("SVX_DEVICE_SORT") == "write" and _is_sam_text(options.bam_path) else read_bam_header(options.bam_path)
+        head = None if several or piped or os.environ.get("SVX_DEVICE_SORT") == "write" and _is_sam_text(options.bam_path) else read_bam_header(options.bam_path)
         if head is not None and head.sort_order == "coordinate":
             fasta = Fasta(options.genome)
             index = find_index(options.bam_path)
@@ -542,7 +553,7 @@ def run(options, sample=None, classifier=None):
         logging.info("CMD: %s", " ".join(sys.argv))
         logging.info("WORKDIR DIR: %s", os.path.abspath(dirs.out_path))
         logging.info("CNN MODEL: %s", os.path.abspath(options.model_path))
-        logging.info("INPUT BAM: %s", os.path.abspath(options.bam_path))
+        logging.info("INPUT BAM: %s", options.bam_path)
         tick = _Ticker()
         inp = _open_input(options, sample, ws, tick)
         tasks, mine = _plan(options, inp, rank, ws)

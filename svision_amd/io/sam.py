@@ -1,6 +1,7 @@
 """SAM text -> the BAM record bytes htslib writes for it (``sam_parse1`` + ``bam_write1``): the host statement of the rules the
 device parser (svision_amd/csrc/svx_sam_core.hpp) follows, the road of every line that parser hands back (``SVX_SAM_HOST``), and the
-yardstick of its CPU model (tools/hostwave/sam_main.cpp).  Pure Python + ``struct``.
+yardstick of its CPU model (tools/hostwave/sam_main.cpp).  Pure Python + ``struct``.  At the end of the file: :class:`StreamReader`,
+the text of a pipe read once -- its first bytes, its header, its chunks filled by a thread of their own (host only, no torch).
 
 The header.  The ``@`` lines in front of the first record are the BAM header's text, byte for byte; the reference dictionary is
 the ``@SQ`` lines' ``SN`` / ``LN`` in order.  No ``@SQ`` line: SamError.  An ``@`` line behind a record: SamError.
@@ -30,8 +31,14 @@ and any number of tags:
 Errors raise :class:`SamError` (a ValueError) whose message names the 1-based line number and whose ``code`` is the device
 parser's code for the same line (include/svx.h, SVX_SAM_E_*)."""
 import collections
+import os
+import queue
 import re
+import select
 import struct
+import threading
+import time
+import zlib
 
 HOST = -1                                                       # SVX_SAM_HOST: valid as far as seen, not taken by the kernels
 E_FIELDS, E_NUMBER, E_NAME, E_RNAME, E_CIGAR, E_QUAL, E_TAG, E_RANGE, E_HEADER = -2, -3, -4, -5, -6, -7, -8, -9, -10
@@ -306,3 +313,228 @@ def is_sam_text(start):
     if start[:2] == b"\x1f\x8b" or start[:4] == b"BAM\x01" or not start:
         return False
     return start.split(b"\n", 1)[0].count(b"\t") >= 10
+
+
+# ---- a stream: a pipe, a FIFO, standard input -- text that is seen once ----
+STREAM_NAME = "<stdin>"                                         # what ``-`` is called in messages
+STREAM_SAM, STREAM_BAM, STREAM_GZIP, STREAM_EMPTY, STREAM_OTHER = "sam", "bam", "gzip", "empty", "other"
+
+
+def stream_kind(start):
+    """The first bytes of a stream -> what it holds: STREAM_SAM (:func:`is_sam_text`), STREAM_BAM (BGZF or gzip magic whose inflated
+    head is ``BAM\\1``; a gzip stream that does not inflate counts too: the BAM road names what is broken), STREAM_GZIP (other gzip
+    data: compressed SAM), STREAM_EMPTY (no byte), STREAM_OTHER."""
+    if not start:
+        return STREAM_EMPTY
+    if is_sam_text(start):
+        return STREAM_SAM
+    if start[:2] == b"\x1f\x8b":
+        try:
+            magic = zlib.decompressobj(31).decompress(bytes(start), 4)
+        except zlib.error:
+            return STREAM_BAM
+        return STREAM_BAM if magic[:4] == b"BAM\x01" else STREAM_GZIP
+    return STREAM_OTHER
+
+
+class StreamReader:
+    """A stream of SAM text read ONCE: ``src`` is a file descriptor or an object with ``readinto`` (and, for a descriptor's sake,
+    maybe ``fileno``).  :meth:`peek` and :meth:`header` read through a buffer of the reader's own, and what they read beyond what
+    they return stays there for :meth:`chunks`.  A descriptor is polled in front of every read, so :meth:`close` ends a reading thread
+    within ``POLL_S`` although the writer is silent; ``close`` closes a descriptor the reader owns (``own``), so that the writer ends
+    with EPIPE and does not block on a full pipe.  ``wait_pipe`` / ``wait_buffer``: the seconds the thread of :meth:`chunks` waited for
+    the stream and for a free buffer; ``text_bytes``: the bytes read so far."""
+    POLL_S = 0.05
+    PEEK = 1 << 16
+
+    def __init__(self, src, own=False):
+        self.fd = src if isinstance(src, int) else None
+        self.obj = None if isinstance(src, int) else src
+        self.own, self.buf, self.eof, self.text_bytes = own, bytearray(), False, 0
+        self.wait_pipe = self.wait_buffer = 0.0
+        self._stop, self._thread, self._closed = threading.Event(), None, False
+        self._poll = None
+        if self.fd is not None:
+            self._poll = select.poll()
+            self._poll.register(self.fd, select.POLLIN | select.POLLHUP | select.POLLERR)
+
+    # -- one read: up to len(view) bytes into a writable memoryview -> the bytes read, 0 at the end (or when the reader was closed)
+    def read_into(self, view):
+        if self.fd is None:
+            n = self.obj.readinto(view)
+            return n or 0
+        while not self._stop.is_set():
+            if self._poll.poll(int(self.POLL_S * 1000)):
+                return os.readv(self.fd, [view])
+        return 0
+
+    def _more(self, want=1 << 16):
+        """The reader's buffer grown by one read -> whether bytes came."""
+        if self.eof:
+            return False
+        piece = bytearray(want)
+        n = self.read_into(memoryview(piece))
+        if n <= 0:
+            self.eof = True
+            return False
+        self.buf += piece[:n]
+        self.text_bytes += n
+        return True
+
+    def peek(self):
+        """-> the first bytes of the stream, enough to say what it holds (:func:`stream_kind`): ``PEEK`` bytes of gzip data, else
+        the first line (up to 1 MB); they stay in the buffer."""
+        while len(self.buf) < 2 and self._more():
+            pass
+        if self.buf[:2] == b"\x1f\x8b":
+            while len(self.buf) < self.PEEK and self._more():
+                pass
+        else:
+            while b"\n" not in self.buf and len(self.buf) < 1 << 20 and self._more():
+                pass
+        return bytes(self.buf[:1 << 20])
+
+    def header(self, limit=1 << 30):
+        """-> the ``@`` lines' bytes, every one closed by ``\\n`` (as :func:`header_end` gives a file's): reading stops behind the first
+        line that does not start with ``@``; the bytes read beyond the header stay in the buffer."""
+        at = 0
+        while True:
+            if at == len(self.buf) and not self._more():
+                break                                           # the stream ends behind a whole header line
+            if self.buf[at] != 64:                              # "@"
+                break
+            nl, scanned = self.buf.find(b"\n", at), len(self.buf)
+            while nl < 0 and self._more():                      # the line goes on: only the bytes that came are searched
+                nl, scanned = self.buf.find(b"\n", scanned), len(self.buf)
+            if nl < 0:                                          # a last header line without its newline
+                self.buf += b"\n"
+                nl = len(self.buf) - 1
+            at = nl + 1
+            if at > limit:
+                raise SamError("a header of more than 2^30 bytes", E_HEADER)
+        text = bytes(self.buf[:at])
+        del self.buf[:at]
+        return text
+
+    def chunks(self, range_bytes, first_line=0, alloc=None, buffers=2):
+        """The rest of the stream -> (buffer, n_bytes, the number of lines in front of the chunk's first) per chunk: ``buffer[:n_bytes]``
+        is about ``range_bytes`` of text cut behind its last newline, the tail carried into the next chunk; a line longer than that
+        grows its chunk; a last line without newline is a line.  The chunks cover the stream once, in order, whatever the reads
+        return.  ``alloc(n) -> a writable buffer of n bytes`` (default: bytearray; the sort passes pinned memory) is called for
+        ``buffers`` (at least two) of them, and again where a long line needs a larger one.  Reading runs on a thread of its own,
+        ahead of the caller by the free buffers; a chunk's buffer is the caller's until it asks for the next one."""
+        range_bytes = max(int(range_bytes), 1)
+        alloc = alloc or bytearray
+        free, ready = queue.Queue(), queue.Queue()
+        for _ in range(max(int(buffers), 2)):
+            free.put(alloc(range_bytes))
+
+        def fill():
+            tail, line = bytes(self.buf), first_line
+            self.buf = bytearray()
+            try:
+                while not self._stop.is_set() and (tail or not self.eof):
+                    t0 = time.perf_counter()
+                    buf = free.get()
+                    self.wait_buffer += time.perf_counter() - t0
+                    if buf is None:
+                        return
+                    view = memoryview(buf).cast("B")
+                    if len(tail) > len(view):                   # (the header's read-ahead, or a long line's end, beyond a buffer)
+                        buf = alloc(2 * len(tail))
+                        view = memoryview(buf).cast("B")
+                    n = len(tail)
+                    view[:n] = tail
+                    cut, scanned = _chunk_cut(view, n, range_bytes, self.eof, 0)
+                    while not cut and not self.eof:
+                        if n == len(view):                      # one line fills the buffer: a larger one
+                            bigger = alloc(2 * len(view))
+                            memoryview(bigger).cast("B")[:n] = view[:n]
+                            buf, view = bigger, memoryview(bigger).cast("B")
+                        t0 = time.perf_counter()
+                        got = self.read_into(view[n:range_bytes if n < range_bytes else len(view)])
+                        self.wait_pipe += time.perf_counter() - t0
+                        if got <= 0:
+                            self.eof = True
+                        else:
+                            self.text_bytes += got
+                            n += got
+                        cut, scanned = _chunk_cut(view, n, range_bytes, self.eof, scanned)
+                    if self._stop.is_set():
+                        return
+                    tail = bytes(view[cut:n])
+                    if cut:
+                        lines = _count_newlines(view, cut) + (view[cut - 1] != 10)
+                        ready.put((buf, cut, line))
+                        line += lines
+                    else:
+                        free.put(buf)
+                ready.put(None)
+            except BaseException as exc:                        # (handed to the caller, raised there)
+                ready.put(exc)
+
+        self._thread = threading.Thread(target=fill, name="svx-sam-stream", daemon=True)
+        self._free = free
+        self._thread.start()
+        try:
+            while True:
+                item = ready.get()
+                if item is None:
+                    return
+                if isinstance(item, BaseException):
+                    raise item
+                yield item
+                free.put(item[0])
+        finally:
+            self.close()
+
+    def close(self):
+        """The reading thread ended and the descriptor, where the reader owns it, closed; what was not read is dropped."""
+        self._stop.set()
+        if self._thread is not None:
+            self._free.put(None)
+            self._thread.join()
+            self._thread = None
+        if not self._closed:
+            self._closed = True
+            if self.own and self.fd is not None:
+                os.close(self.fd)
+            elif self.own and hasattr(self.obj, "close"):
+                self.obj.close()
+
+
+_SEARCH = 1 << 20                                               # bytes of a view copied at a time to be searched
+
+
+def _find_newline(view, lo, hi, last=False):
+    """The first (``last``: the last) newline of view[lo:hi] -> its index, -1: none.  A piece of _SEARCH bytes at a time."""
+    starts = range(lo, hi, _SEARCH)
+    for at in reversed(starts) if last else starts:
+        piece = bytes(view[at:min(at + _SEARCH, hi)])
+        k = piece.rfind(b"\n") if last else piece.find(b"\n")
+        if k >= 0:
+            return at + k
+    return -1
+
+
+def _chunk_cut(view, n, range_bytes, eof, scanned):
+    """Where the chunk at the front of view[:n] ends, by the rule of :func:`chunk_places`: behind the last newline of its first
+    ``range_bytes``; none there: behind the first one after them (a long line); the stream's end closes the last chunk.  ``scanned``:
+    0 for a new chunk, then what the call before returned -- the bytes of the chunk that are known to hold no newline, which are not
+    searched again.  -> (the cut, 0: more bytes are needed; ``scanned``)."""
+    if n >= range_bytes:
+        if scanned < range_bytes:
+            at = _find_newline(view, 0, range_bytes, last=True)
+            if at >= 0:
+                return at + 1, scanned
+            scanned = range_bytes
+        at = _find_newline(view, scanned, n)
+        if at >= 0:
+            return at + 1, n
+        scanned = n
+    return (n if eof else 0), scanned
+
+
+def _count_newlines(view, n):
+    import numpy as np
+    return int(np.count_nonzero(np.frombuffer(view[:n], np.uint8) == 10))

@@ -67,7 +67,44 @@ bytes, keys and fields come about -- and the two files are those of the same rec
   in spans  the places of :func:`span_ranges` are chunks of text: each is encoded into a chunk-local buffer and goes through
             svx_record_scatter_segments like a BAM's range.  A chunk with another number of lines, or a line whose record has another
             length than in the key pass, means the file changed: SortWriteError
-Compressed SAM (gzip, BGZF) and stdin are not taken: the text is read twice.
+A regular file of compressed SAM (gzip, BGZF) is not taken: the text of a file is read twice, and there is no device decoder for it.
+
+A pipe.  ``minimap2 -a ref.fa reads.fq | python -m svision_amd.sort - -o sorted.bam``: ``-`` is standard input (``<stdin>`` in messages),
+and any path that os.stat says is no regular file -- a FIFO, /dev/fd/N, ``<(winnowmap -a ...)`` -- takes the same road, decided
+before a byte is read.  The text is seen ONCE, and the two files are those of the same bytes read from a regular file:
+
+  open      io.sam.StreamReader: the first bytes say what the stream holds (io.sam.stream_kind), the ``@`` lines are read up to the
+            first line without ``@``; what was read beyond them stays in the reader's buffer
+  key pass  the ONLY pass (:func:`_pipe_key_pass`): the reader's thread drains the pipe into two pinned buffers, chunks of ``range_bytes``
+            cut by the rule of io.sam.chunk_places, while the device works on the chunk before; per chunk upload, svx_sam_lines,
+            svx_sam_measure, the read-back, the host's lines -- all as for a file, with the stream's line numbers -- and AT ONCE
+            svx_sam_encode into a SEGMENT of exactly the chunk's record bytes, the offsets the exclusive sum of the lengths behind the
+            bytes kept so far.  Keys, fields, lengths, ``range_records`` and ``host_lens`` are kept as for a file
+  the stream grows  by a segment a chunk: nothing is copied while the text arrives and nothing is allocated ahead, so what lies on the
+            device is the record bytes seen so far -- a small pipe takes a small share of the card.  At the end of the input the
+            segments are joined into the one resident stream (``Source.fill``; each goes when it is copied): then, and only then, both
+            copies exist.  :func:`keeps_in_core` keeps a chunk while that join still fits ``memory_bytes``; so (a) the source's record
+            buffers never exceed the budget, (b) never twice the record bytes seen plus one chunk's records -- and a pipe stays in core
+            up to HALF the budget, where a file does up to all of it.  ``stats["stream_bytes"]``: the largest total, the join's
+  the spool beyond it, the source switches to :class:`Spool` and does not fail: an unsorted BAM beside the output, ``out_path +
+            ".spool.<pid>.bam"``, under the stream's header, written through :class:`BgzfWriter` with :class:`DeviceEncode` in the fixed
+            code -- the records kept so far first, then every later chunk's as they are encoded, in arrival order (a chunk's buffer is
+            in transit, like a span pass's chunk-local one, and not kept).  At the end of the input the pass's own results are dropped
+            and the input BECOMES that file: the BAM road above, key pass, spans, ``again``.  One extra write and two reads of
+            BAM-sized data, paid only by a pipe that does not fit
+  among several inputs  a pipe is spooled from its first byte (``room`` is decided behind all key passes, and a pipe cannot be asked
+            again), against the merged names and under the merged header, and is that file from ``_open_all`` on; its place in the
+            list decides ties; without @SQ lines it is usable beside parts that have them.  ``-`` may appear once; further pipes of a run (FIFOs) spool to
+            ``.spool.<pid>.<number>.bam`` and ``stats["pipes"]`` lists them all
+  a BAM on a pipe  (``samtools view -b``, ``dorado aligner``, ``pbmm2``): BGZF or gzip magic whose inflated head is ``BAM\\1``.  No
+            one-pass road is built for it: the bytes are copied as they are into the spool file and the BAM road sorts that file --
+            one behaviour for the user at the price of one write and one read of compressed BAM
+  refused   other gzip data (compressed SAM: ``pigz -dc x.sam.gz | ... -`` is the road), no byte at all (``<stdin>: no input``)
+On any failure the read end is closed BEFORE the error is raised -- standard input is pointed at the null device --, so that the
+pipe's writer ends with EPIPE / SIGPIPE and does not block on a full pipe; no output, no temporary and no spool is left.  An early
+end of the writer is no error by itself: what arrived is the input, and a cut last line fails by the parser's rules with its number.
+``stats["pipe"]``: mode ("in_core", "spooled", "bam_spooled"), grows (segments + the join), spool_bytes, text_bytes, and the seconds the
+reader's thread waited for the pipe and for a free buffer.
 
 Several inputs.  ``sort_bam([a.bam, b.sam, c.bam], out)`` -- ``python -m svision_amd.sort a.bam b.sam c.bam -o out.bam`` -- writes ONE sorted
 BAM of all their records, what ``samtools merge`` in front of the sort would have given: one BAM per SMRT cell, one SAM per FASTQ batch.
@@ -97,7 +134,7 @@ ValueError); no file and no temporary is left behind.
 
 :func:`sort_bam` is the list of its steps, each a function of this module over named values: ``_open_all`` (per input ``_open``: header,
 first record and ``room`` from one pass over the file's members: index.bgzf_members, index.header_place; it also chooses the
-:class:`Source`, BAM or SAM text: the key pass, the reading-again of a span's ranges and the filling of a stream whose size was not
+:class:`Source`, BAM, SAM text or a pipe (``_open_pipe``): the key pass, the reading-again of a span's ranges and the filling of a stream whose size was not
 known; several inputs: :func:`merge_headers`) -> ``_key_passes`` (per input its source's key pass, then ``_join``) -> ``_order`` -> the pieces,
 ``_pieces_in_core`` or ``_pieces_spanned``: generators of (device buffer, first byte, bytes), a chunk each -> :class:`BgzfWriter`,
 which owns the temporary file and the ledger of members and is handed its encoder (:class:`DeviceEncode`; zlib in the CPU tests) ->
@@ -106,6 +143,7 @@ function, :func:`block_cuts`.
 """
 import collections
 import os
+import stat
 import struct
 import sys
 import zlib
@@ -118,7 +156,7 @@ BLOCK = 0xFF00                                                  # htslib's block
 DEFAULT_CHUNK_BYTES = 1024 * BLOCK
 TABLES = ("fixed", "dynamic")                                   # the encoder: svx_bgzf_deflate / svx_bgzf_deflate_dyn
 STAGES = ("read", "upload", "inflate", "crc", "find_starts", "walk", "scan", "read_back", "keep", "join", "sort", "gather", "scatter", "deflate",
-          "pack", "download", "write", "index", "lines", "measure", "encode", "host_lines", "retid")
+          "pack", "download", "write", "index", "lines", "measure", "encode", "host_lines", "retid", "spool")
 SAM_READ_THREADS = 8                                            # svx_read_range's threads for a chunk of text
 DEFAULT_SAM_CHUNK_BYTES = 64 << 20                              # text bytes a chunk of a SAM input (``range_bytes``); see profiles/sort_sam.txt
 
@@ -425,6 +463,93 @@ def commit_pair(tmp_bam, out_path, bai_data):
         index.discard(tmp_bai)
 
 
+# ---- a pipe's records: what is kept on the device, and the spool file beyond the budget (host) ----
+STREAM_SLACK = 4                                                # readable bytes behind a record buffer: the gather's and the encoder's aligned loads
+
+
+def keeps_in_core(kept, chunk, budget):
+    """The growth rule of a pipe's record stream: ``kept`` record bytes lie on the device, a segment a chunk, and the next chunk brings
+    ``chunk`` more -> whether it is kept too.  It is while the JOIN at the end of the input still fits the budget: the one buffer of
+    kept + chunk + STREAM_SLACK bytes beside the segments it is copied from.  So (a) the segments, and the join's two copies, never
+    exceed ``budget``; (b) every segment is exactly its chunk's records, so what is allocated is the record bytes seen so far until the
+    join and twice that + STREAM_SLACK in it -- never beyond twice the bytes seen plus one chunk's records.  False: the spool."""
+    return 2 * (int(kept) + int(chunk)) + STREAM_SLACK <= int(budget)
+
+
+class StreamLedger:
+    """The bytes of a source's record buffers on the device: ``now``, the largest total ``peak``, and how many times they grew."""
+
+    def __init__(self):
+        self.now = self.peak = self.grows = 0
+
+    def add(self, n_bytes, grow=True):
+        self.now += int(n_bytes)
+        self.peak = max(self.peak, self.now)
+        self.grows += bool(grow)
+
+    def drop(self, n_bytes):
+        self.now -= int(n_bytes)
+
+
+def spool_path(out_path, number=0):
+    """The spool file of a run's pipe: beside the output; ``number``: 0 for the run's first pipe, whose name has no number."""
+    return "%s.spool.%d%s.bam" % (out_path, os.getpid(), ".%d" % number if number else "")
+
+
+class Spool:
+    """The spool file of a pipe that is not kept in core: an UNSORTED BAM beside the output, ``out_path.spool.<pid>.bam`` -- ``header``
+    (the bytes in front of a BAM's first record) and then the records as :meth:`put` is handed them, in arrival order -- written
+    through :class:`BgzfWriter` and its ``encode`` (``as_buffer``: bytes -> the buffer that encoder takes).  :meth:`finish` closes it
+    with the end-of-file marker and puts it in place; :meth:`discard` removes it, finished or not."""
+
+    def __init__(self, out_path, header, encode, clock, as_buffer, source=None, number=0):
+        self.path, self.bytes = spool_path(out_path, number), 0
+        self.writer = BgzfWriter(self.path, encode, clock, source)
+        try:
+            self.writer.put_header(as_buffer(header), len(header))
+        except BaseException:
+            self.writer.discard()
+            raise
+
+    def put(self, buf, n_bytes, step=DEFAULT_CHUNK_BYTES):
+        """The records buf[:n_bytes] (whole records; STREAM_SLACK readable bytes behind them), encoded ``step`` bytes a call."""
+        for lo, hi in chunk_cuts(0, int(n_bytes), max(int(step) // BLOCK, 1) * BLOCK):
+            self.writer.put(buf, lo, hi - lo)
+
+    def finish(self):
+        self.bytes = self.writer.finish().compressed_bytes
+        index.into_place(self.writer.tmp, self.path)
+        return self.path
+
+    def discard(self):
+        self.writer.discard()
+        index.discard(self.path)
+
+
+def spool_copy(reader, out_path, clock, number=0):
+    """BAM on a pipe: the stream's bytes as they are -- what the reader's buffer holds, then the rest -- into the spool file
+    -> (its path, the bytes); the ``spool`` stage of ``clock`` is the copy's seconds."""
+    path = spool_path(out_path, number)
+    f, tmp = index.temp_beside(path)
+    n = 0
+    try:
+        with f:
+            piece = bytearray(1 << 20)
+            f.write(reader.buf)
+            n, reader.buf = len(reader.buf), bytearray()
+            while True:
+                got = reader.read_into(memoryview(piece))
+                if got <= 0:
+                    break
+                f.write(piece[:got])
+                n += got
+        index.into_place(tmp, path)
+    finally:
+        index.discard(tmp)
+    clock.lap("spool", False)
+    return path, n
+
+
 # ---- the device steps ----
 _Dev = collections.namedtuple("_Dev", "torch lib kernels dev clock")
 
@@ -471,7 +596,8 @@ class DeviceEncode:
 
 # ``remap``: None, or the int32 table of :func:`merge_headers` that takes the input's reference indices into the merged dictionary
 # (a BAM input of several whose table is not the identity: svx_record_retid).
-Opened = collections.namedtuple("Opened", "path head first header room source remap", defaults=(None, None))
+# ``pipe``: None, or the :class:`_Pipe` the input came through -- still to be read (PIPE_SOURCE) or already in its spool file.
+Opened = collections.namedtuple("Opened", "path head first header room source remap pipe", defaults=(None, None, None))
 # The input's kind, chosen at open: ``key_pass(dv, opened, range_bytes, kp, d_stream)``: the input's ranges -> ``kp`` (the input's own
 # KeyPass) filled, the records' bytes kept in ``d_stream`` from byte ``kp.base`` on where it is given; ``again(dv, opened, kp, need) ->
 # per range of ``need`` (k, records completed, device bytes, the records' offsets in them [n + 1])``, the ranges of the key pass read
@@ -494,18 +620,28 @@ def input_paths(bam_path):
     return paths
 
 
-def _open_all(paths):
+# What the steps of one run share besides the device: where the output goes (a spool lies beside it), the output's chunk, the budget
+# for the records' bytes, ``pipes``: every :class:`_Pipe` the run opened, for sort_bam to close and to clean up behind, and the clock.
+_Run = collections.namedtuple("_Run", "out_path chunk_blocks budget range_bytes pipes clock")
+
+
+def _open_all(paths, dv=None, run=None):
     """open, every input: -> Inputs.  One input: as it is opened.  Several: the headers merged (:func:`merge_headers`) -- a SAM part
     takes the merged dictionary for its own, so its records are encoded in the merged numbering and a part without header is
     usable; a BAM part whose table is not the identity carries it as ``remap`` --, ``room`` the sum where every part's is known."""
     from .io import sam
+    if paths.count("-") > 1:
+        raise SortWriteError("%s is named twice: standard input is one stream" % sam.STREAM_NAME)
     if len(paths) == 1:
-        opened = _open(paths[0])
-        return Inputs([opened], opened, paths[0])
-    opened = [_open(p, alone=False) for p in paths]
-    merged = merge_headers([(o.path, o.head.text if o.source is SAM_SOURCE else o.head.header_text, o.head.references, o.head.lengths) for o in opened])
+        opened = _open(paths[0], run=run)
+        return Inputs([opened], opened, opened.path if opened.pipe is None else opened.pipe.name)
+    opened = [_open(p, alone=False, run=run) for p in paths]
+    merged = merge_headers([(o.path, o.head.text if o.source in (SAM_SOURCE, PIPE_SOURCE) else o.head.header_text, o.head.references, o.head.lengths) for o in opened])
     for i, o in enumerate(opened):
-        if o.source is SAM_SOURCE:
+        if o.source is PIPE_SOURCE:                             # a pipe among several: spooled from its first byte, in the merged numbering
+            opened[i] = _pipe_spooled(dv, o._replace(head=sam.SamHead(merged.references, merged.lengths, o.head.text, o.head.sort_order)),
+                                      sam.bam_header_bytes(sam.SamHead(merged.references, merged.lengths, merged.text, "coordinate")))
+        elif o.source is SAM_SOURCE:
             opened[i] = o._replace(head=sam.SamHead(merged.references, merged.lengths, o.head.text, o.head.sort_order))
         elif not np.array_equal(merged.maps[i], np.arange(len(merged.maps[i]))):       # (a dictionary that opens the merged one: nothing to rewrite)
             opened[i] = o._replace(remap=merged.maps[i])
@@ -516,12 +652,29 @@ def _open_all(paths):
                                  None if None in rooms else sum(rooms), None), label)
 
 
-def _open(bam_path, alone=True):
+_COMPRESSED_SAM = ("%s: gzip- or BGZF-compressed data that is no BAM -- compressed SAM is not taken: decompress it, or convert it with "
+                   "`samtools view -b`; through a pipe it is: `pigz -dc x.sam.gz | python -m svision_amd.sort - -o sorted.bam`")
+
+
+def is_stream(path):
+    """Whether an input takes the one-pass road: ``-`` (standard input), or a path that is no regular file (a FIFO, /dev/fd/N) --
+    decided by os.stat, before a byte is read."""
+    if path == "-":
+        return True
+    try:
+        return not stat.S_ISREG(os.stat(path).st_mode)
+    except OSError:
+        return False                                            # (the file road names what is wrong with the path)
+
+
+def _open(bam_path, alone=True, run=None):
     """open: -> Opened(the path, read_bam_header's table, first_record's (file offset, entry, references), the header's bytes as the
     output takes them, ``room``: the records' inflated bytes by the members' ISIZE fields) -- one pass over the file's members.  SAM
     text (a first byte ``@``, or a first line of 11 tab-separated fields): :func:`_open_sam`."""
     from .io import sam
     from .io.bam import read_bam_header
+    if is_stream(bam_path):
+        return _open_pipe(bam_path, alone, run)
     try:
         with open(bam_path, "rb") as f:
             start = f.read(1 << 20)
@@ -535,8 +688,7 @@ def _open(bam_path, alone=True):
         except zlib.error:
             magic = b"BAM\x01"                                   # (not for this check to report: the BAM road names what is broken)
         if magic[:4] != b"BAM\x01":
-            raise SortWriteError("%s: gzip- or BGZF-compressed data that is no BAM -- compressed SAM is not taken: decompress it, or "
-                                 "convert it with `samtools view -b`" % bam_path)
+            raise SortWriteError(_COMPRESSED_SAM % bam_path)
     try:
         head = read_bam_header(bam_path)
         members = index.bgzf_members(bam_path)
@@ -645,6 +797,11 @@ def _key_passes(dv, ins, budget, range_bytes):
         kp.parts.append((opened, part, ranges, records))
         kp.reading = opened.path
         opened.source.key_pass(dv, opened, range_bytes, part, kp.d_stream)
+        if opened.source is PIPE_SOURCE and opened.pipe.mode == "spooled":
+            # the pipe did not fit: what its pass kept is dropped, the input becomes its spool file and takes the road of a BAM
+            again = _open(opened.pipe.spool_file)._replace(pipe=opened.pipe)
+            del part, kp
+            return _key_passes(dv, Inputs([again], again, ins.label), budget, None)
         kp.seen += part.seen
         ranges, records = ranges + len(part.range_records), records + sum(part.range_records)
     kp.reading = None
@@ -838,6 +995,39 @@ def _sam_refuse(opened, tid_of, data, line_off, i, line_no, code):
     return SortWriteError("%s: line %d: not an alignment line (svx_sam_measure: %d)" % (opened.path, line_no, code))
 
 
+def _sam_measured(dv, opened, kp, tid_of, data, d_text, d_line_off, n_lines, line_no, seen):
+    """A chunk's lines measured (svx_sam_measure) and read back -> (the records' lengths with the host's lines patched in, the lengths
+    as svx_sam_encode takes them, tid, pos, flag, span on the host, the keys d_tid and d_pos on the device).  An error code raises
+    with the line's number -- ``line_no`` lines lie in front of the chunk --; a line the kernels leave to the host is encoded by
+    io.sam.encode_line and kept in ``kp.host_records`` by record number, ``seen`` records lying in front of the chunk."""
+    from .io import sam
+    torch, kernels, dev, clock = dv.torch, dv.kernels, dv.dev, dv.clock
+    d_len, d_tid, d_pos, d_flag, d_span = kernels.sam_measure(d_text, len(data), d_line_off, n_lines, kp.sam_table)
+    clock.lap("measure")
+    length, tid, pos, flag, span = (t.cpu().numpy() for t in (d_len, d_tid, d_pos, d_flag, d_span))
+    line_off = d_line_off[:n_lines + 1].cpu().numpy()
+    clock.lap("read_back")
+    bad = np.flatnonzero(length < kernels.SAM_HOST)
+    if bad.size:
+        raise _sam_refuse(opened, tid_of, data, line_off, int(bad[0]), line_no + int(bad[0]) + 1, int(length[bad[0]]))
+    kernel_len = length.copy()
+    left = np.flatnonzero(length == kernels.SAM_HOST)
+    for i in left:
+        line = data[int(line_off[i]):int(line_off[i + 1])].tobytes()
+        line = line[:-1] if line.endswith(b"\n") else line
+        try:
+            rec = sam.encode_line(line, tid_of)
+            tid[i], pos[i], flag[i], span[i] = sam.fields_of(line, tid_of)
+        except sam.SamError as exc:
+            raise SortWriteError("%s: %s" % (opened.path, exc.at(line_no + int(i) + 1))) from None
+        length[i] = len(rec)
+        kp.host_records[seen + int(i)] = rec
+    if left.size:
+        d_tid, d_pos = torch.from_numpy(tid).to(dev), torch.from_numpy(pos).to(dev)
+    clock.lap("host_lines", False)
+    return length, kernel_len, tid, pos, flag, span, d_tid, d_pos
+
+
 def _sam_key_pass(dv, opened, range_bytes, kp, d_stream=None):
     """key pass of SAM text: one pass over the chunks (io.sam.chunk_places: ``range_bytes`` of text, cut at line ends): svx_sam_lines,
     svx_sam_measure, the lengths and fields read back.  An error code raises with the file's line number; a line the kernels leave to the
@@ -851,29 +1041,7 @@ def _sam_key_pass(dv, opened, range_bytes, kp, d_stream=None):
     line_no, seen = opened.first[1], 0
     for place in sam.chunk_places(opened.path, opened.first[0], range_bytes or DEFAULT_SAM_CHUNK_BYTES):
         data, d_text, d_line_off, n_lines = _sam_chunk(dv, opened, kp, place)
-        d_len, d_tid, d_pos, d_flag, d_span = kernels.sam_measure(d_text, len(data), d_line_off, n_lines, kp.sam_table)
-        clock.lap("measure")
-        length, tid, pos, flag, span = (t.cpu().numpy() for t in (d_len, d_tid, d_pos, d_flag, d_span))
-        line_off = d_line_off[:n_lines + 1].cpu().numpy()
-        clock.lap("read_back")
-        bad = np.flatnonzero(length < kernels.SAM_HOST)
-        if bad.size:
-            raise _sam_refuse(opened, tid_of, data, line_off, int(bad[0]), line_no + int(bad[0]) + 1, int(length[bad[0]]))
-        kernel_len = length.copy()
-        left = np.flatnonzero(length == kernels.SAM_HOST)
-        for i in left:
-            line = data[int(line_off[i]):int(line_off[i + 1])].tobytes()
-            line = line[:-1] if line.endswith(b"\n") else line
-            try:
-                rec = sam.encode_line(line, tid_of)
-                tid[i], pos[i], flag[i], span[i] = sam.fields_of(line, tid_of)
-            except sam.SamError as exc:
-                raise SortWriteError("%s: %s" % (opened.path, exc.at(line_no + int(i) + 1))) from None
-            length[i] = len(rec)
-            kp.host_records[seen + int(i)] = rec
-        if left.size:
-            d_tid, d_pos = torch.from_numpy(tid).to(dev), torch.from_numpy(pos).to(dev)
-        clock.lap("host_lines", False)
+        length, kernel_len, tid, pos, flag, span, d_tid, d_pos = _sam_measured(dv, opened, kp, tid_of, data, d_text, d_line_off, n_lines, line_no, seen)
         kp.range_records.append(n_lines)
         kp.places.append(place)
         kp.host_lens.append(kernel_len)
@@ -884,7 +1052,7 @@ def _sam_key_pass(dv, opened, range_bytes, kp, d_stream=None):
         kp.seen += int(length.sum())
         seen += n_lines
         line_no += n_lines
-        del d_text, d_line_off, d_len, d_flag, d_span
+        del d_text, d_line_off
         clock.lap("keep")
 
 
@@ -945,8 +1113,202 @@ def _sam_again(dv, opened, kp, need):
         del d_local, d_src_off
 
 
+# ---- a pipe: SAM text that is seen once ----
+class _Pipe:
+    """An input that is read once -- standard input, a FIFO, /dev/fd/N: its name in messages (``<stdin>`` for ``-``), the
+    io.sam.StreamReader over its descriptor, ``mode`` ("in_core", "spooled", "bam_spooled"), the ledger of its record buffers on the
+    device, its segments (a chunk's records each) while it is kept in core, its :class:`Spool` beyond the budget, and what the
+    statistics report.  :meth:`close` ends the reader and closes the descriptor; ``failed``: standard input's descriptor is
+    pointed at the null device, so that the writer of the pipe ends with EPIPE and does not block; :meth:`discard` removes the spool."""
+
+    def __init__(self, path, run):
+        from .io import sam
+        self.name, self.run, self.stdin, self.number = sam.STREAM_NAME if path == "-" else path, run, path == "-", len(run.pipes)
+        self.mode, self.ledger, self.segments, self.spool, self.spool_file = "in_core", StreamLedger(), [], None, None
+        self.spool_bytes = self.host_lines = self.records = 0
+        self.reader = sam.StreamReader(0 if self.stdin else os.open(path, os.O_RDONLY), own=not self.stdin)
+
+    def close(self, failed=False):
+        self.reader.close()
+        if failed and self.stdin:
+            null = os.open(os.devnull, os.O_RDONLY)
+            os.dup2(null, 0)
+            os.close(null)
+
+    def discard(self):
+        self.segments = []
+        if self.spool is not None:
+            self.spool.discard()
+        index.discard(self.spool_file)
+
+    def stats(self):
+        return dict(mode=self.mode, grows=self.ledger.grows, spool_bytes=self.spool_bytes, text_bytes=self.reader.text_bytes,
+                    reader_wait_pipe_s=round(self.reader.wait_pipe, 6), reader_wait_buffer_s=round(self.reader.wait_buffer, 6))
+
+
+def _open_pipe(path, alone, run):
+    """open, an input that is read once: its first bytes say what it holds (io.sam.stream_kind).  SAM text: the ``@`` lines are read
+    -> an Opened as :func:`_open_sam` gives, its source PIPE_SOURCE; the text behind them waits in the pipe.  A BAM: its bytes are
+    copied as they are into the spool file, and that file is opened as any BAM.  Compressed SAM, no byte, anything else: refused."""
+    from .io import sam
+    if run is None:
+        raise SortWriteError("%s: not a regular file" % path)
+    try:
+        pipe = _Pipe(path, run)
+    except OSError as exc:
+        raise SortWriteError("%s: %s" % (path, exc)) from None
+    run.pipes.append(pipe)
+    name = pipe.name
+    try:
+        kind = sam.stream_kind(pipe.reader.peek())
+        if kind == sam.STREAM_EMPTY:
+            raise SortWriteError("%s: no input" % name)
+        if kind == sam.STREAM_GZIP:
+            raise SortWriteError(_COMPRESSED_SAM % name)
+        if kind == sam.STREAM_OTHER:
+            raise SortWriteError("%s: neither SAM text nor a BAM" % name)
+        if kind == sam.STREAM_BAM:
+            pipe.mode = "bam_spooled"
+            pipe.spool_file, pipe.spool_bytes = spool_copy(pipe.reader, run.out_path, run.clock, pipe.number)
+            pipe.close()
+            return _open(pipe.spool_file, alone)._replace(pipe=pipe)
+        text = pipe.reader.header()
+        first = (len(text), text.count(b"\n"))
+        if not alone and not any(l.startswith(b"@SQ\t") for l in text.split(b"\n")):
+            return Opened(name, sam.SamHead([], [], text.decode("latin-1"), None), first, None, None, PIPE_SOURCE, None, pipe)
+        head = sam.parse_header(text)
+        return Opened(name, head, first, sorted_header_bytes(sam.bam_header_bytes(head)), None, PIPE_SOURCE, None, pipe)
+    except (sam.SamError, OSError) as exc:
+        raise SortWriteError("%s: %s" % (name, exc)) from None
+
+
+def _pipe_join(dv, pipe, d_out, at=0):
+    """The segments of a pipe kept in core, end to end into ``d_out`` from byte ``at`` on; each goes when it is copied."""
+    for k, d_seg in enumerate(pipe.segments):
+        d_out[at:at + d_seg.numel()].copy_(d_seg)
+        at += d_seg.numel()
+        pipe.segments[k] = None
+        pipe.ledger.drop(d_seg.numel())
+        del d_seg
+    pipe.segments = []
+    dv.clock.lap("keep")
+    return at
+
+
+def _pipe_to_spool(dv, opened, kp, header):
+    """The budget does not hold the next chunk (or the pipe is one of several inputs): the spool file is opened with ``header``, and
+    the records kept so far go in first -- joined into one buffer, which the rule of :func:`keeps_in_core` has left room for."""
+    torch, pipe = dv.torch, opened.pipe
+    pipe.mode = "spooled"
+    pipe.spool = Spool(pipe.run.out_path, header, DeviceEncode(dv, "fixed"), dv.clock,
+                       lambda b: torch.from_numpy(np.frombuffer(b, np.uint8).copy()).to(dv.dev), pipe.name, pipe.number)
+    if pipe.segments:
+        d_kept = torch.empty(kp.seen + STREAM_SLACK, dtype=torch.uint8, device=dv.dev)
+        pipe.ledger.add(d_kept.numel())
+        d_kept[kp.seen:] = 0
+        _pipe_join(dv, pipe, d_kept)
+        pipe.spool.put(d_kept, kp.seen, pipe.run.chunk_blocks * BLOCK)
+        pipe.ledger.drop(d_kept.numel())
+        del d_kept
+    kp.host, kp.d_keys, kp.lens = [], [], []                    # (the spool's own key pass computes them again)
+
+
+def _pipe_key_pass(dv, opened, range_bytes, kp, d_stream=None, spool_header=None):
+    """key pass of a pipe, the ONLY pass over its text: per chunk of io.sam.StreamReader.chunks -- read on a thread of its own into
+    pinned buffers while the device works on the chunk before -- upload, svx_sam_lines, svx_sam_measure, the read-back and the host's
+    lines as :func:`_sam_key_pass` has them, and AT ONCE svx_sam_encode: the chunk's records into a segment of exactly their bytes,
+    their offsets the exclusive sum of the lengths behind the bytes kept so far; the host's encodings copied to theirs.  Keys, fields,
+    lengths, ``range_records`` and ``host_lens`` are kept as for a SAM file.  The segments are joined by :func:`_pipe_fill`.
+    A chunk that :func:`keeps_in_core` refuses (``spool_header`` given: the first) opens the spool: from then on every chunk's
+    records are appended to it in arrival order and nothing is kept; ``opened.pipe.mode`` says so to the caller."""
+    from .io import sam
+    torch, kernels, dev, clock, pipe = dv.torch, dv.kernels, dv.dev, dv.clock, opened.pipe
+    tid_of, kp.sam_table = sam.tid_table(opened.head.references), kernels.sam_ref_table(opened.head.references, dev)
+    pinned = {}
+
+    def alloc(n):                                               # a pinned buffer as the reader takes it: its NumPy view
+        t = torch.empty(n, dtype=torch.uint8, pin_memory=True)
+        a = t.numpy()
+        pinned[a.ctypes.data] = t
+        return a
+    if spool_header is not None:
+        _pipe_to_spool(dv, opened, kp, spool_header)
+    seen, at = 0, opened.first[0]
+    d_status = torch.zeros(1, dtype=torch.int32, device=dev)
+    for buf, n, line_no in pipe.reader.chunks(range_bytes or DEFAULT_SAM_CHUNK_BYTES, opened.first[1], alloc):
+        clock.lap("read", False)
+        data = buf[:n]
+        d_text = torch.empty(n + kernels.SAM_SLACK, dtype=torch.uint8, device=dev)
+        d_text[:n].copy_(pinned[buf.ctypes.data][:n], non_blocking=True)
+        d_text[n:] = 0
+        clock.lap("upload")
+        d_line_off, n_lines = kernels.sam_lines(d_text, n)
+        clock.lap("lines")
+        length, kernel_len, tid, pos, flag, span, d_tid, d_pos = _sam_measured(dv, opened, kp, tid_of, data, d_text, d_line_off, n_lines, line_no, seen)
+        length = length.astype(np.int64)
+        need = int(length.sum())
+        if pipe.spool is None and need and not keeps_in_core(kp.seen, need, pipe.run.budget):
+            _pipe_to_spool(dv, opened, kp, sam.bam_header_bytes(opened.head))
+        # ---- the chunk's records: a segment of their bytes (kept), or a buffer with the encoder's slack (spooled at once)
+        off = np.cumsum(length) - length + kp.seen
+        d_seg = torch.empty(need + (STREAM_SLACK if pipe.spool is not None else 0), dtype=torch.uint8, device=dev)
+        d_seg[need:] = 0
+        if n_lines:
+            kernels.sam_encode(d_text, n, d_line_off, n_lines, kp.sam_table, torch.from_numpy(kernel_len).to(dev), torch.from_numpy(off).to(dev),
+                               kp.seen, d_seg, d_status)
+        clock.lap("encode")
+        for i in np.flatnonzero(kernel_len < 0):
+            rec = kp.host_records.pop(seen + int(i))
+            d_seg[int(off[i]) - kp.seen:int(off[i]) - kp.seen + len(rec)].copy_(torch.frombuffer(bytearray(rec), dtype=torch.uint8))
+            pipe.host_lines += 1
+        clock.lap("host_lines")
+        if int(d_status.item()):
+            raise SortWriteError("%s: a line's record is not of the length svx_sam_measure gave it" % opened.path)
+        if pipe.spool is not None:
+            pipe.spool.put(d_seg, need, pipe.run.chunk_blocks * BLOCK)
+        else:
+            if need:
+                pipe.segments.append(d_seg)
+                pipe.ledger.add(need)
+            if n_lines:
+                kp.host.append((tid, pos, flag.astype(np.uint16), span))
+                kp.lens.append(length)
+                kp.d_keys.append((d_tid, d_pos))
+        kp.range_records.append(n_lines)
+        kp.places.append((at, n))
+        kp.host_lens.append(kernel_len)
+        kp.seen += need
+        pipe.records += n_lines
+        seen, at = seen + n_lines, at + n
+        del d_text, d_line_off, d_seg
+        clock.lap("keep")
+    pipe.close()
+    if pipe.spool is not None:
+        pipe.spool_file = pipe.spool.finish()
+        pipe.spool_bytes = pipe.spool.bytes
+
+
+def _pipe_fill(dv, opened, kp):
+    """in one piece, a pipe: its segments joined into the resident stream (``kp.d_stream``) -- both copies exist while they are."""
+    pipe = opened.pipe
+    pipe.ledger.add(kp.d_stream.numel())
+    _pipe_join(dv, pipe, kp.d_stream, int(kp.off_in[0]) if kp.n else kp.base)
+
+
+def _pipe_again(dv, opened, kp, need):
+    raise SortWriteError("%s: a pipe cannot be read again" % opened.path)      # (not reached: a pipe beyond the budget is spooled)
+
+
+def _pipe_spooled(dv, opened, header):
+    """A pipe among several inputs: its text through :func:`_pipe_key_pass` into the spool file from the first byte on, under the
+    merged ``header`` and in the merged numbering -> the Opened of that file, a BAM like any other."""
+    _pipe_key_pass(dv, opened, opened.pipe.run.range_bytes, KeyPass(), None, header)
+    return _open(opened.pipe.spool_file, alone=False)._replace(pipe=opened.pipe)
+
+
 BAM_SOURCE = Source("bam", _key_pass, _bam_again, lambda dv, opened, kp: _bam_fill(dv, opened, kp))
 SAM_SOURCE = Source("sam", _sam_key_pass, _sam_again, lambda dv, opened, kp: _sam_fill(dv, opened, kp))     # (looked up at the call: tests replace it)
+PIPE_SOURCE = Source("pipe", _pipe_key_pass, _pipe_again, _pipe_fill)
 
 
 def _bai(opened, kp, od, written):
@@ -976,7 +1338,13 @@ def sort_bam(bam_path, out_path, device="cuda", range_bytes=None, chunk_bytes=No
     ``range_bytes`` is the text bytes of a chunk, and stats also has input="sam" and host_lines, the lines io/sam.py encoded.
     ``bam_path`` may be a list or tuple of such paths: their records merged into the one sorted file (see "Several inputs" at the head
     of the module); ranges and range_records run over all inputs in list order, host_lines is there when a part is SAM text, input only
-    when all are; a list of one path is that path, an empty one a ValueError."""
+    when all are; a list of one path is that path, an empty one a ValueError.  ``-`` (standard input) or a path that is no regular file
+    is read once (see "A pipe" at the head of the module): stats also has ``pipe`` -- mode, grows, spool_bytes, text_bytes and the
+    reader thread's waits; ``pipes``: the same of every such input in list order, with its name --, input="sam" as for a SAM file, and
+    stream_bytes is the largest total of the pipe's record buffers.  A side effect on the calling PROCESS: when the call fails while
+    ``-`` is among the inputs, descriptor 0 is pointed at the null device (``os.dup2``) before the error is raised -- that closes the
+    pipe's read end, so that its writer ends with EPIPE and does not block; a caller that needs standard input afterwards hands the
+    stream in as a path (/dev/fd/N of a duplicate) instead, whose descriptor is the call's own."""
     from . import ingest_sort, kernels
     paths = input_paths(bam_path)
     torch, lib, dev, clock = index.on_device("sort_bam needs the GPU (svx_record_sort, svx_bgzf_deflate)", device, STAGES)
@@ -985,14 +1353,16 @@ def sort_bam(bam_path, out_path, device="cuda", range_bytes=None, chunk_bytes=No
     dv = _Dev(torch, lib, kernels, dev, clock)
     chunk_blocks = max(int(chunk_bytes or DEFAULT_CHUNK_BYTES) // BLOCK, 1)
     budget = None if memory_bytes is None else max(int(memory_bytes), 1)
-    ins, opened, kp, writer, counts = None, None, KeyPass(), None, {"span_range_reads": 0}
-    bam_path = paths[0] if len(paths) == 1 else "%s (+ %d more)" % (paths[0], len(paths) - 1)       # (the inputs' name in a message)
+    ins, opened, kp, writer, counts, pipes, done = None, None, KeyPass(), None, {"span_range_reads": 0}, [], False
+    from .io.sam import STREAM_NAME
+    first_name = STREAM_NAME if paths[0] == "-" else paths[0]
+    bam_path = first_name if len(paths) == 1 else "%s (+ %d more)" % (first_name, len(paths) - 1)       # (the inputs' name in a message)
     try:
-        ins = _open_all(paths)
-        opened = ins.merged
         with torch.cuda.device(dev):
             if budget is None:                                  # half of what is free: the rest is for a range, its inflate workspace, keys and chunks
                 budget = max(int(torch.cuda.mem_get_info(dev)[0]) // 2, 1)
+            ins = _open_all(paths, dv, _Run(out_path, chunk_blocks, budget, range_bytes, pipes, clock))
+            opened = ins.merged
             opened, kp, spanned = _key_passes(dv, ins, budget, range_bytes)
             od = _order(dv, opened, kp, spanned, budget)
             pieces = _pieces_spanned if spanned else _pieces_in_core
@@ -1004,6 +1374,7 @@ def sort_bam(bam_path, out_path, device="cuda", range_bytes=None, chunk_bytes=No
             written = writer.finish()
             commit_pair(writer.tmp, out_path, _bai(opened, kp, od, written))
             clock.lap("index", False)
+            done = True
     except index.IndexBuildError as exc:
         raise SortWriteError("%s: %s" % (kp.reading or bam_path, exc)) from None
     except torch.cuda.OutOfMemoryError as exc:
@@ -1016,19 +1387,27 @@ def sort_bam(bam_path, out_path, device="cuda", range_bytes=None, chunk_bytes=No
     except OSError as exc:
         raise SortWriteError("%s: writing %s failed (%s)" % (bam_path, out_path, exc)) from None
     finally:
+        for pipe in pipes:                                      # the read end first: the pipe's writer must not block on it
+            pipe.close(failed=not done)
         if writer is not None:
             writer.discard()
+        for pipe in pipes:
+            pipe.discard()
     if stats is not None:
-        sam_parts = [part for o, part, _r, _n in kp.parts if o.source is SAM_SOURCE]
+        was_text = lambda o: o.source is SAM_SOURCE or o.pipe is not None and o.pipe.mode != "bam_spooled"
+        sam_parts = [(o, part) for o, part, _r, _n in kp.parts if was_text(o)]
         if sam_parts:
-            stats.update(host_lines=sum(len(part.host_records) for part in sam_parts))
+            stats.update(host_lines=sum(len(part.host_records) if o.pipe is None else o.pipe.host_lines for o, part in sam_parts))
             if len(sam_parts) == len(kp.parts):
                 stats.update(input="sam")
+        if pipes:
+            # ``pipe``: the first input that was read once; ``pipes``: every one of them, in list order, with its name
+            stats.update(pipe=pipes[0].stats(), pipes=[dict(pipe.stats(), name=pipe.name) for pipe in pipes])
         stats.update(inputs=len(kp.parts), input_records=[part.n for _o, part, _r, _n in kp.parts],
                      retid_inputs=sum(o.remap is not None for o, _part, _r, _n in kp.parts))
         stats.update(ranges=len(kp.range_records), records=kp.n, blocks=written.blocks, stored_blocks=written.stored_blocks,
                      dynamic_blocks=written.dynamic_blocks, chunks=written.chunks, spans=od.spans, span_range_reads=counts["span_range_reads"],
-                     range_records=kp.range_records, stream_bytes=od.stream_bytes, memory_bytes=budget,
+                     range_records=kp.range_records, stream_bytes=max([od.stream_bytes] + [pipe.ledger.peak for pipe in pipes]), memory_bytes=budget,
                      compressed_bytes=written.compressed_bytes, inflated_bytes=written.inflated_bytes, pos_bits=od.pos_bits,
                      passes=len(ingest_sort.digit_plan(len(opened.head.references), od.pos_bits)),
                      seconds={k: round(v, 6) for k, v in clock.times.items()})
@@ -1039,7 +1418,9 @@ def main(argv=None):
     import argparse
     import json
     ap = argparse.ArgumentParser(prog="python -m svision_amd.sort", description="Write the coordinate-sorted BAM of an unsorted BAM or of SAM text, and its .bai, on the GPU.")
-    ap.add_argument("bam", nargs="+", help="an unsorted BAM or SAM text; several: their records merged into the one sorted file")
+    ap.add_argument("bam", nargs="+", help="an unsorted BAM or SAM text; several: their records merged into the one sorted file.  ``-`` (once) is "
+                                           "standard input, and a path that is no regular file (a FIFO, /dev/fd/N) is read once like it: an aligner's "
+                                           "output through a pipe")
     ap.add_argument("-o", "--output", required=True, help="the sorted BAM to write (its index: OUTPUT + .bai)")
     ap.add_argument("--device", default="cuda")
     ap.add_argument("--chunk-bytes", type=int, default=None, help="inflated bytes a chunk of the output (default %d)" % DEFAULT_CHUNK_BYTES)
@@ -1066,6 +1447,13 @@ def main(argv=None):
           % (path, stats["records"], stats["blocks"],
              "%d stored" % stats["stored_blocks"] + (", %d dynamic" % stats["dynamic_blocks"] if args.tables == "dynamic" else ""),
              stats["inflated_bytes"], stats["compressed_bytes"], stats["ranges"], stats["chunks"], sum(stats["seconds"].values())))
+    if "pipe" in stats:
+        pipe = stats["pipe"]
+        name = next(("<stdin>" if b == "-" else b for b in args.bam if is_stream(b)), "<stdin>")
+        print("%s: %s (%d bytes) %s" % (path, name, pipe["text_bytes"],
+                                        "kept in core: its records grew %d time(s) on the device" % pipe["grows"] if pipe["mode"] == "in_core" else
+                                        "spooled: %d bytes of unsorted BAM beside the output, sorted from there%s"
+                                        % (pipe["spool_bytes"], " (a BAM on a pipe is copied as it is)" if pipe["mode"] == "bam_spooled" else "")))
     if len(args.bam) > 1:
         print("%s: %d inputs merged (records: %s), %d of them renumbered into the merged reference dictionary"
               % (path, len(args.bam), ", ".join(str(v) for v in stats.get("input_records", [])), stats.get("retid_inputs", 0)))

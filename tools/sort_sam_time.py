@@ -1,6 +1,7 @@
 """Numbers for profiles/sort_sam.txt: sort_bam on an aligner's SAM text against sort_bam on the same records as an unsorted BAM.
 
     python tools/sort_sam_time.py --shape hifi|ont [--mb 40] [--coverage 30] [--out DIR] [--runs 3] [--once sam|bam] [--chunks]
+                                  [--pipe [--memory BYTES]]
 
   files     a synthetic sample (svision_amd.synth: one contig of --mb megabases at --coverage x; ``ont``: log-normal read lengths, 6 %
             small events), its records shuffled (seed 1), random bases and phred values, NM:i and rq:f on every read and an MM:Z / ML:B:C
@@ -13,6 +14,10 @@
   --chunks  sort_bam(text) once more at range_bytes of 16, 64 and 256 MB
   --once    ONE sort_bam of the text or the BAM and nothing else (files of an earlier call with the same --out are taken): the run a
             kernel trace is taken of
+  --pipe    numbers for profiles/sort_pipe.txt instead: the same text three ways, alternating, --runs times after one warm-up of each --
+            as a file, through ``cat`` (sort_bam reads /dev/fd/N: one pass, the records kept in core) and through ``cat`` under a budget
+            of --memory bytes (default: a fifth of the records' bytes), which spools; wall and stage seconds, what the reader thread
+            waited for, how many times the stream grew, and whether the three outputs are identical
 Prints one JSON object."""
 import argparse
 import json
@@ -67,6 +72,36 @@ def timed(path, out, **kw):
     return stats
 
 
+def timed_pipe(text, out, **kw):
+    """sort_bam on the text as ``cat`` writes it into a pipe."""
+    import subprocess
+    with subprocess.Popen(["cat", text], stdout=subprocess.PIPE) as cat:
+        try:
+            return timed("/dev/fd/%d" % cat.stdout.fileno(), out, **kw)
+        finally:
+            cat.stdout.close()
+            cat.wait()
+
+
+def pipe_runs(text, d, runs, memory):
+    outs = {w: os.path.join(d, "pipe_%s.bam" % w) for w in ("file", "in_core", "spooled")}
+    got = {w: [] for w in outs}
+    for r in range(runs + 1):
+        st = timed(text, outs["file"])
+        budget = memory or max((st["stream_bytes"] - 4) // 5, 1)
+        for w, one in (("file", st), ("in_core", timed_pipe(text, outs["in_core"])), ("spooled", timed_pipe(text, outs["spooled"], memory_bytes=budget))):
+            if r:
+                got[w].append(one)
+    res = {"memory_bytes_spooled": budget,
+           "outputs_identical": all(open(outs["file"] + e, "rb").read() == open(outs[w] + e, "rb").read() for w in ("in_core", "spooled") for e in ("", ".bai"))}
+    for w, sts in got.items():
+        stages = sorted({k for st in sts for k, v in st["seconds"].items() if v > 0})
+        res[w] = {"wall_seconds": [st["wall_seconds"] for st in sts], "seconds": {k: [st["seconds"][k] for st in sts] for k in stages},
+                  "records": sts[0]["records"], "ranges": sts[0]["ranges"], "spans": sts[0]["spans"], "stream_bytes": sts[0]["stream_bytes"],
+                  "pipe": [st.get("pipe") for st in sts]}
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shape", choices=("hifi", "ont"), default="hifi")
@@ -76,6 +111,8 @@ def main():
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--once", choices=("sam", "bam"), default=None)
     ap.add_argument("--chunks", action="store_true")
+    ap.add_argument("--pipe", action="store_true")
+    ap.add_argument("--memory", type=sort.parse_memory, default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("sort_sam_time.py measures on the GPU; there is none")
@@ -84,6 +121,12 @@ def main():
     text = os.path.join(d, "%s.%d.%d.sam" % (args.shape, args.mb, args.coverage))
     unsorted = text[:-4] + ".unsorted.bam"
     res = {"shape": args.shape}
+    if args.pipe:
+        if not os.path.exists(text):
+            write_text(text, args.shape, args.mb, args.coverage)
+        res.update(text_bytes=os.path.getsize(text), **pipe_runs(text, d, args.runs, args.memory))
+        print(json.dumps(res))
+        return
     if not (os.path.exists(text) and os.path.exists(unsorted)):
         write_text(text, args.shape, args.mb, args.coverage)
         t0 = time.perf_counter()
