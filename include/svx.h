@@ -602,6 +602,32 @@ int            svx_sam_measure(const uint8_t* d_text, const int64_t* d_line_off,
 int            svx_sam_encode(const uint8_t* d_text, const int64_t* d_line_off, uint32_t n_lines, const uint32_t* d_ref_hash,
                               const int32_t* d_ref_tid, const uint32_t* d_ref_name_off, const uint8_t* d_ref_names, uint32_t n_ref,
                               const int32_t* d_len, const int64_t* d_off, int64_t out_base, uint8_t* d_out, int32_t* d_status, void* stream);
+/* SAM text -> the caller's packed arrays (svx_sam.hip over svx_sam_core.hpp; ABI 420, additive): the front end of
+ * svision_amd/ingest_sort.py for text, a pipe and several inputs.  No BAM record is built: a chunk's lines become what
+ * svx_bam_walk_extract(_seq) writes for the same records.  d_text, d_line_off and the reference table as above; a wave a line, a
+ * bounded grid whose waves stride over the lines.
+ *   svx_sam_pack_count    d_status [i] = 0, SVX_SAM_HOST, or the SVX_SAM_E_* code svx_sam_measure gives for the same fault in the
+ *                         first eleven fields.  The tags are not read (a malformed tag refuses no line here), QUAL is held to SEQ's
+ *                         length and not read, and the number of CIGAR operations has no limit.  SVX_SAM_HOST, the only one of these
+ *                         kernels: a CIGAR of the shape <l_seq>S<n>N, the placeholder beside a CG:B:I tag -- the caller encodes that
+ *                         line on the host and puts its counts and bytes into the line's own slots.  d_fields: five planes of
+ *                         n_lines (tid, pos, flag, mapq, l_seq), d_counts: three (CIGAR words, name bytes = the name + one '\n',
+ *                         SEQ bytes = (l_seq + 1) / 2, 0 without with_seq); zero where d_status [i] is not 0
+ *   svx_sam_pack_extract  d_cig_off d_name_off d_seq_off [n_lines + 1]: the exclusive prefix of the counts (the caller's; a line it
+ *                         took on the host has its counts in it).  Every line with d_status [i] == 0: d_tid d_pos d_l_seq d_flag
+ *                         d_mapq [i], its words to d_cigar + d_cig_off [i], its name and the '\n' to d_names + d_name_off [i], its
+ *                         4-bit SEQ as BAM stores it (the spare nibble of an odd length zero) to d_seq + d_seq_off [i] -- byte-aligned
+ *                         neighbours, single byte stores.  d_seq and d_seq_off both NULL: no bases.  Every store is checked against the
+ *                         record's own slot [off [i], off [i + 1]); other lines are skipped and their elements left as they are
+ * No atomics, every loop bounded by the line's bytes, reads inside the chunk and its slack. */
+int            svx_sam_pack_count(const uint8_t* d_text, const int64_t* d_line_off, uint32_t n_lines, const uint32_t* d_ref_hash,
+                                  const int32_t* d_ref_tid, const uint32_t* d_ref_name_off, const uint8_t* d_ref_names, uint32_t n_ref,
+                                  int with_seq, int32_t* d_status, int32_t* d_fields, int32_t* d_counts, void* stream);
+int            svx_sam_pack_extract(const uint8_t* d_text, const int64_t* d_line_off, uint32_t n_lines, const uint32_t* d_ref_hash,
+                                    const int32_t* d_ref_tid, const uint32_t* d_ref_name_off, const uint8_t* d_ref_names, uint32_t n_ref,
+                                    const int32_t* d_status, int32_t* d_tid, int32_t* d_pos, int16_t* d_flag, uint8_t* d_mapq, int32_t* d_l_seq,
+                                    const int64_t* d_cig_off, uint32_t* d_cigar, const int64_t* d_name_off, uint8_t* d_names,
+                                    const int64_t* d_seq_off, uint8_t* d_seq, void* stream);
 /* host helpers of the device-side ingestion: parallel positional read into caller memory; the whole BGZF blocks of a
  * buffer (payload offset / size, ISIZE, file offset; -> their number or -1, *used = bytes they cover); QNAME ids by
  * first occurrence (-> number of distinct names, written '\n'-separated to uniq) */

@@ -92,6 +92,8 @@ SYMBOLS = {
     "svx_sam_lines": (ctypes.c_int, [_vp, _u64, _vp, _u64, _vp, _vp, _u64, _vp]),
     "svx_sam_measure": (ctypes.c_int, [_vp, _vp, _u32] + [_vp] * 4 + [_u32] + [_vp] * 5 + [_vp]),
     "svx_sam_encode": (ctypes.c_int, [_vp, _vp, _u32] + [_vp] * 4 + [_u32, _vp, _vp, ctypes.c_int64, _vp, _vp, _vp]),
+    "svx_sam_pack_count": (ctypes.c_int, [_vp, _vp, _u32] + [_vp] * 4 + [_u32, ctypes.c_int] + [_vp] * 3 + [_vp]),
+    "svx_sam_pack_extract": (ctypes.c_int, [_vp, _vp, _u32] + [_vp] * 4 + [_u32] + [_vp] * 12 + [_vp]),
     "svx_read_range": (ctypes.c_int, [ctypes.c_char_p, _u64, _u64, _vp, ctypes.c_int]),
     "svx_bgzf_index": (ctypes.c_int64, [_vp, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _vp]),
     "svx_name_ids": (ctypes.c_int64, [_vp, _vp, _u64, _vp, _vp, _vp]),

@@ -32,7 +32,7 @@ def parse_arguments(arguments=None):
                                             "-b <input bam path> -g <reference> -m <model path>" % __version__)
     g = p.add_argument_group("Input/Output parameters")
     g.add_argument("-o", dest="out_path", type=os.path.abspath, required=True, help="Absolute path to output")
-    g.add_argument("-b", dest="bam_path", type=_bam_arg, required=True, help="Absolute path to bam file; SVX_DEVICE_SORT=write: ``-`` is "
+    g.add_argument("-b", dest="bam_path", type=_bam_arg, required=True, help="Absolute path to bam file; SVX_DEVICE_SORT=write or =1: ``-`` is "
                    "an aligner's output on standard input")
     g.add_argument("-m", dest="model_path", type=os.path.abspath, required=True, help="Absolute path to CNN predict model")
     g.add_argument("-g", dest="genome", type=os.path.abspath, required=True, help="Absolute path to your reference genome")
@@ -198,9 +198,10 @@ def load_rank_table(options, rank, ws):
     return table
 
 
-def _load_unsorted(options):
-    """SVX_DEVICE_SORT=1 and a header that does not say ``SO:coordinate``: the whole file taken apart and its records sorted on the
-    device (svision_amd/ingest_sort.py) -> the resident Sample the run goes on with."""
+def _load_unsorted(options, several=None):
+    """SVX_DEVICE_SORT=1 and a header that does not say ``SO:coordinate``, an aligner's SAM text, ``-b -`` or a list of inputs
+    (``several``): everything taken apart and the records sorted on the device (svision_amd/ingest_sort.py) -> the resident Sample the
+    run goes on with.  No alignment file is written."""
     import time
     import torch
     from .ingest_sort import SortIngestError, load_sample
@@ -209,13 +210,15 @@ def _load_unsorted(options):
         torch.cuda.set_device(sdist.local_device_index())
     stats = {}
     try:
-        sample = load_sample(options.bam_path, Fasta(options.genome), options.min_sv_size, device=torch.device("cuda", torch.cuda.current_device()),
-                             with_seq=bool(options.hash or options.graph), stats=stats)
+        sample = load_sample(several or options.bam_path, Fasta(options.genome), options.min_sv_size,
+                             device=torch.device("cuda", torch.cuda.current_device()), with_seq=bool(options.hash or options.graph), stats=stats)
     except SortIngestError as exc:
         logging.error("%s", exc)
         raise SystemExit(1)
-    logging.info("%s is not coordinate sorted: %d records sorted on the device in %.2f s (%d range(s), %d radix passes)", options.bam_path,
-                 stats["records"], time.perf_counter() - t0, stats["ranges"], stats["passes"])
+    kinds = stats.get("inputs", ["bam"])
+    logging.info("%s is %s: %d records sorted on the device in %.2f s (%d range(s), %d radix passes)", options.bam_path,
+                 "%d inputs" % len(kinds) if len(kinds) > 1 else "not coordinate sorted" if kinds[0] == "bam" else "SAM text", stats["records"],
+                 time.perf_counter() - t0, stats["ranges"], stats["passes"])
     return sample
 
 
@@ -278,6 +281,11 @@ def _input_list(bam_path):
     return parts if parts.count("-") <= 1 and all(p == "-" or os.path.isfile(p) for p in parts) else None
 
 
+def _is_stream(path):
+    from . import sort
+    return sort.is_stream(path)
+
+
 def _is_sam_text(path):
     from .io import sam
     try:
@@ -298,16 +306,21 @@ def _open_input(options, sample, ws, tick):
     if sample is None:
         # file-driven run: header now, the records chromosome by chromosome while the pipeline runs (ingest.ChromosomeFeed)
         several = _input_list(options.bam_path)
-        piped = options.bam_path == "-" or bool(several and "-" in several)
-        if piped and os.environ.get("SVX_DEVICE_SORT") != "write":
-            logging.error("-b -: standard input is taken under SVX_DEVICE_SORT=write only, which sorts an aligner's output on the device in one pass")
+        # (a path that is no regular file -- a FIFO, /dev/fd/N -- is a pipe like ``-``: it is seen once, so no byte of it is read here)
+        piped = options.bam_path == "-" or bool(several and "-" in several) or (several is None and _is_stream(options.bam_path))
+        switch = os.environ.get("SVX_DEVICE_SORT")
+        if piped and switch not in ("write", "1"):
+            logging.error("-b %s: standard input or a pipe is taken under SVX_DEVICE_SORT=write, which sorts an aligner's output on the device in one "
+                          "pass and writes the sorted BAM, and under SVX_DEVICE_SORT=1, which calls from it and writes no alignment file",
+                          "-" if several or options.bam_path == "-" else options.bam_path)
             raise SystemExit(1)
-        if several and os.environ.get("SVX_DEVICE_SORT") != "write":
-            logging.error("-b names %d files: SVX_DEVICE_SORT=write merges them into one sorted BAM on the device (one rank); every other setting "
-                          "takes one file -- merge them first with `python -m svision_amd.sort %s -o merged.bam`", len(several), " ".join(several))
+        if several and switch not in ("write", "1"):
+            logging.error("-b names %d files: SVX_DEVICE_SORT=write merges them into one sorted BAM on the device, SVX_DEVICE_SORT=1 calls from "
+                          "them as they are (one rank); every other setting takes one file -- merge them first with "
+                          "`python -m svision_amd.sort %s -o merged.bam`", len(several), " ".join(several))
             raise SystemExit(1)
-        # (SAM text under SVX_DEVICE_SORT=write takes the road of an unsorted BAM; every other setting reads it as a BAM and refuses it)
-        head = None if several or piped or os.environ.get("SVX_DEVICE_SORT") == "write" and _is_sam_text(options.bam_path) else read_bam_header(options.bam_path)
+        # (SAM text under SVX_DEVICE_SORT=write / =1 takes the road of an unsorted BAM; every other setting reads it as a BAM and refuses it)
+        head = None if several or piped or switch in ("write", "1") and _is_sam_text(options.bam_path) else read_bam_header(options.bam_path)
         if head is not None and head.sort_order == "coordinate":
             fasta = Fasta(options.genome)
             index = find_index(options.bam_path)
@@ -334,10 +347,12 @@ def _open_input(options, sample, ws, tick):
         if ws > 1:
             # (every rank would read and sort the whole file; the ranks share chromosomes, not records in file order)
             logging.error("SVX_DEVICE_SORT=1 sorts an unsorted BAM in a single-rank run only: sort and index %s first "
-                          "(`samtools sort`, then `python -m svision_amd.index`) and start the %d ranks again", options.bam_path, ws)
+                          "(`samtools sort`, then `python -m svision_amd.index`) and start the %d ranks again", " ".join(several or [options.bam_path]), ws)
             raise SystemExit(1)
-        sample = _load_unsorted(options)
+        sample = _load_unsorted(options, several)
         tick("unsorted BAM: records sorted on the device")
+        if several or piped:                                        # a stable name for the run: ``stdin``, the first input of a list
+            options.bam_path = "stdin" if (several or [options.bam_path])[0] == "-" else (several or [options.bam_path])[0]
     _sample.register(options.bam_path, sample)
     return RunInput(sample, sample.fasta, sample.table.references, sample.table.lengths, None, False)
 

@@ -6,6 +6,9 @@
 // sam_emit_kernel      the tile again: a thread's newlines, ranked by the tile's base + the workgroup's prefix -> line_off
 // sam_measure_kernel   a WAVE a line: the record's bytes or a negative code, and tid pos flag span
 // sam_encode_kernel    a WAVE a line: the record at its offset
+// sam_pack_count_kernel / sam_pack_extract_kernel
+//                      a WAVE a line, a bounded grid whose waves stride over the lines: the line's fields and the sizes of its CIGAR
+//                      words, name and SEQ; then those written into the caller's packed arrays (no BAM record in between)
 // No atomics, no communication between workgroups, no spin-wait; a wave's lanes meet in ballots and shuffles only.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -115,6 +118,29 @@ void sam_encode_kernel(const uint8_t* __restrict__ text, const int64_t* __restri
     svx_sam::encode_line(w, text, line_off, i, rt, len, off, out_base, out, status);
 }
 
+// the pack kernels' grid: at most PACK_BLOCKS workgroups, every wave takes the lines i, i + the grid's waves, ...
+constexpr uint32_t PACK_BLOCKS = 4096;
+
+__global__ __launch_bounds__(WAVES * 64)
+void sam_pack_count_kernel(const uint8_t* __restrict__ text, const int64_t* __restrict__ line_off, uint32_t n_lines, svx_sam::RefTable rt,
+                           int with_seq, int32_t* __restrict__ status, int32_t* __restrict__ fields, int32_t* __restrict__ counts)
+{
+    Wave w{threadIdx.x & 63u};
+    for (uint64_t i = (uint64_t)blockIdx.x * WAVES + (threadIdx.x >> 6); i < n_lines; i += (uint64_t)gridDim.x * WAVES)   // (whole waves leave)
+        svx_sam::pack_count_line(w, text, line_off, i, n_lines, rt, with_seq != 0, status, fields, counts);
+}
+
+__global__ __launch_bounds__(WAVES * 64)
+void sam_pack_extract_kernel(const uint8_t* __restrict__ text, const int64_t* __restrict__ line_off, uint32_t n_lines, svx_sam::RefTable rt,
+                             const int32_t* __restrict__ status, svx_sam::PackOut out)
+{
+    Wave w{threadIdx.x & 63u};
+    for (uint64_t i = (uint64_t)blockIdx.x * WAVES + (threadIdx.x >> 6); i < n_lines; i += (uint64_t)gridDim.x * WAVES)
+        svx_sam::pack_extract_line(w, text, line_off, i, rt, status, out);
+}
+
+inline uint32_t pack_grid(uint32_t n_lines) { const uint32_t b = (n_lines + WAVES - 1) / WAVES; return b < PACK_BLOCKS ? b : PACK_BLOCKS; }
+
 inline uint64_t tiles_of(uint64_t n) { return (n + svx_sam::TILE - 1) / svx_sam::TILE; }
 inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 inline int launched() { return hipGetLastError() == hipSuccess ? SVX_OK : SVX_ELAUNCH; }
@@ -166,5 +192,34 @@ extern "C" int svx_sam_encode(const uint8_t* d_text, const int64_t* d_line_off, 
     const svx_sam::RefTable rt{d_ref_hash, d_ref_tid, d_ref_name_off, d_ref_names, n_ref};
     hipLaunchKernelGGL(sam_encode_kernel, dim3((n_lines + WAVES - 1) / WAVES), dim3(WAVES * 64), 0, static_cast<hipStream_t>(stream), d_text,
                        d_line_off, n_lines, rt, d_len, d_off, out_base, d_out, d_status);
+    return launched();
+}
+
+extern "C" int svx_sam_pack_count(const uint8_t* d_text, const int64_t* d_line_off, uint32_t n_lines, const uint32_t* d_ref_hash,
+                                  const int32_t* d_ref_tid, const uint32_t* d_ref_name_off, const uint8_t* d_ref_names, uint32_t n_ref,
+                                  int with_seq, int32_t* d_status, int32_t* d_fields, int32_t* d_counts, void* stream)
+{
+    if (n_lines == 0) return SVX_OK;
+    if (!d_text || !d_line_off || !d_ref_hash || !d_ref_tid || !d_ref_name_off || !d_ref_names || !d_status || !d_fields || !d_counts) return SVX_EINVAL;
+    const svx_sam::RefTable rt{d_ref_hash, d_ref_tid, d_ref_name_off, d_ref_names, n_ref};
+    hipLaunchKernelGGL(sam_pack_count_kernel, dim3(pack_grid(n_lines)), dim3(WAVES * 64), 0, static_cast<hipStream_t>(stream), d_text, d_line_off,
+                       n_lines, rt, with_seq, d_status, d_fields, d_counts);
+    return launched();
+}
+
+extern "C" int svx_sam_pack_extract(const uint8_t* d_text, const int64_t* d_line_off, uint32_t n_lines, const uint32_t* d_ref_hash,
+                                    const int32_t* d_ref_tid, const uint32_t* d_ref_name_off, const uint8_t* d_ref_names, uint32_t n_ref,
+                                    const int32_t* d_status, int32_t* d_tid, int32_t* d_pos, int16_t* d_flag, uint8_t* d_mapq, int32_t* d_l_seq,
+                                    const int64_t* d_cig_off, uint32_t* d_cigar, const int64_t* d_name_off, uint8_t* d_names,
+                                    const int64_t* d_seq_off, uint8_t* d_seq, void* stream)
+{
+    if (n_lines == 0) return SVX_OK;
+    if (!d_text || !d_line_off || !d_ref_hash || !d_ref_tid || !d_ref_name_off || !d_ref_names || !d_status || !d_tid || !d_pos || !d_flag || !d_mapq
+        || !d_l_seq || !d_cig_off || !d_cigar || !d_name_off || !d_names || (d_seq != nullptr) != (d_seq_off != nullptr))
+        return SVX_EINVAL;
+    const svx_sam::RefTable rt{d_ref_hash, d_ref_tid, d_ref_name_off, d_ref_names, n_ref};
+    const svx_sam::PackOut out{d_tid, d_pos, d_l_seq, d_flag, d_mapq, d_cig_off, d_cigar, d_name_off, d_names, d_seq_off, d_seq};
+    hipLaunchKernelGGL(sam_pack_extract_kernel, dim3(pack_grid(n_lines)), dim3(WAVES * 64), 0, static_cast<hipStream_t>(stream), d_text, d_line_off,
+                       n_lines, rt, d_status, out);
     return launched();
 }

@@ -19,6 +19,9 @@
 //                     the commas below = the value's index
 //          record<false> measures: the record's bytes, or a negative code.  record<true> writes what record<false> measured and
 //          nothing else: every store lies in out[0 .. len).
+// pack     ONE WAVE a line, the same E: pack_measure -> the line's fields and the sizes of its CIGAR words, name and SEQ (or a code);
+//          pack_extract_line writes them into the caller's packed arrays, the arrays of svx_bam_walk_extract(_seq) -- no BAM record
+//          in between, the tags never read.  The host program tools/hostwave/sam_pack_main.cpp runs these.  At the end of the file.
 // Every loop is bounded by the line's [lo, hi); reads reach at most 15 bytes behind hi (the 16-byte loads of SEQ and QUAL).
 #pragma once
 #include <stdint.h>
@@ -472,6 +475,176 @@ SVX_SAM_HD void encode_line(E& ex, const uint8_t* text, const int64_t* line_off,
         return;
     }
     record<true>(ex, text, lo, hi, rt, out + (off[i] - out_base), nullptr);
+}
+
+// ---- pack: a line -> the caller's packed arrays (svx_sam_pack_count / svx_sam_pack_extract), no BAM record in between ----
+// What the device ingest keeps of a record (svx_bam_walk_extract(_seq) of the same record): tid pos flag mapq l_seq, the CIGAR words,
+// the name and one '\n', the 4-bit SEQ.  The first eleven fields are held to record<>'s rules, in record<>'s order, so a fault there
+// has record<>'s code; QUAL is measured, not read; the tags are not looked at; the number of operations has no limit.  The one line
+// left to the host (HOST): a CIGAR of the shape <l_seq>S<n>N, the placeholder beside a CG:B:I tag, whose real words are in that tag.
+struct Packed { int32_t tid, pos, flag, mapq, l_seq, words, name_bytes, seq_bytes; };
+
+// the bounds s[k] .. e[k] of the first eleven fields -> the tabs seen, at most 11 (10: no tag behind QUAL, e[10] = hi)
+template <class E>
+SVX_SAM_HD uint32_t split_fields(E& ex, const uint8_t* text, uint64_t lo, uint64_t hi, uint64_t* s, uint64_t* e)
+{
+    uint32_t n_tab = 0;
+    s[0] = lo;
+    for (uint64_t at = lo; at < hi && n_tab < 11; at += WAVE) {
+        uint64_t m = ex.ballot([&](uint32_t l) { return at + l < hi && text[at + l] == '\t'; });
+        for (; m && n_tab < 11; m &= m - 1) {
+            const uint64_t p = at + ctz64(m);
+            e[n_tab] = p;
+            if (++n_tab < 11) s[n_tab] = p + 1;
+        }
+    }
+    if (n_tab == 10) e[10] = hi;
+    return n_tab;
+}
+
+// The line text[lo .. hi) measured: 0 and *pk, HOST (*pk as the placeholder reads, not for use), or a negative code.
+template <class E>
+SVX_SAM_HD int32_t pack_measure(E& ex, const uint8_t* text, uint64_t lo, uint64_t hi, const RefTable& rt, bool with_seq, Packed* pk)
+{
+    if (lo >= hi) return E_FIELDS;
+    if (text[lo] == '@') return E_HEADER;
+    uint64_t s[11], e[11];
+    if (split_fields(ex, text, lo, hi, s, e) < 10) return E_FIELDS;
+    const uint64_t l_name = e[0] - s[0];
+    if (l_name < 1 || l_name > 254) return E_NAME;
+    int64_t flag, pos, mapq, pnext, tlen;
+    int32_t rc;
+    if ((rc = parse_ranged(text, s[1], e[1], 0, 65535, &flag))) return rc;
+    const int32_t tid = ref_lookup(text, s[2], e[2], rt);
+    if (tid < -1) return E_RNAME;
+    if ((rc = parse_ranged(text, s[3], e[3], 0, 0x7FFFFFFF, &pos))) return rc;
+    if ((rc = parse_ranged(text, s[4], e[4], 0, 255, &mapq))) return rc;
+    const bool no_cigar = e[5] - s[5] == 1 && text[s[5]] == '*';
+    uint64_t n_ops = 0;
+    if (!no_cigar) {
+        if (e[5] == s[5] || is_digit(text[e[5] - 1])) return E_CIGAR;
+        // every lane walks its own bytes of the field, 64 apart: the letters that are no operation, and the letters
+        const uint64_t got = ex.sum([&](uint32_t l) -> uint64_t {
+            uint64_t n = 0;
+            for (uint64_t p = s[5] + l; p < e[5]; p += WAVE) {
+                if (is_digit(text[p])) continue;
+                if (cigar_word(text, s[5], p) == ~0u) return 1ull << 56;
+                ++n;
+            }
+            return n;
+        });
+        if (got >> 56) return E_CIGAR;
+        n_ops = got;
+    }
+    if (!(e[6] - s[6] == 1 && text[s[6]] == '=') && ref_lookup(text, s[6], e[6], rt) < -1) return E_RNAME;
+    if ((rc = parse_ranged(text, s[7], e[7], 0, 0x7FFFFFFF, &pnext))) return rc;
+    if ((rc = parse_ranged(text, s[8], e[8], -0x7FFFFFFFll, 0x7FFFFFFF, &tlen))) return rc;
+    const uint64_t l_seq = e[9] - s[9] == 1 && text[s[9]] == '*' ? 0 : e[9] - s[9];
+    const bool no_qual = e[10] - s[10] == 1 && text[s[10]] == '*';
+    if (!no_qual && e[10] - s[10] != l_seq) return E_QUAL;
+    if (l_seq > 0x7FFFFFFF || n_ops > 0x7FFFFFFF) return E_FIELDS;
+    pk->tid = tid; pk->pos = (int32_t)(pos - 1); pk->flag = (int32_t)flag; pk->mapq = (int32_t)mapq; pk->l_seq = (int32_t)l_seq;
+    pk->words = (int32_t)n_ops; pk->name_bytes = (int32_t)(l_name + 1); pk->seq_bytes = with_seq ? (int32_t)((l_seq + 1) / 2) : 0;
+    if (n_ops != 2) return 0;
+    // two operations are at most 20 bytes, within one step: the first letter from a ballot.  <l_seq>S<n>N is the host's.
+    // KEEP THIS ORDER -- *pk assigned above, the placeholder decided last, by one expression.  An earlier form found the first letter
+    // with `while (is_digit(text[p])) ++p;` in FRONT of the assignments and returned HOST from inside that block.  hipcc (ROCm 7.2,
+    // -O3, gfx950) compiled it wrongly: in the kernel's ISA the register that held l_seq for the final stores was reused as the zero of
+    // the HOST path's merge and not written again on the way back, so a two-operation line that is no placeholder came out with
+    // status 0 and l_seq 0.  The source had no undefined behaviour that was found, and the host model ran it right under ASan and
+    // UBSan: a compiler fault, as far as it could be read.  The two `two_ops_*` shapes of tests/sam_pack_cases.py hold it down on
+    // the device (tests/test_gpu_sam_pack.py); a change here wants that test run, and a look at the stores at the kernel's end.
+    const uint64_t letters = ex.ballot([&](uint32_t l) { return s[5] + l < e[5] && !is_digit(text[s[5] + l]); });
+    const uint32_t w0 = cigar_word(text, s[5], s[5] + ctz64(letters | 1ull << 63)), w1 = cigar_word(text, s[5], e[5] - 1);
+    return (w0 & 15u) == 4 && (w0 >> 4) == l_seq && (w1 & 15u) == 3 ? HOST : 0;
+}
+
+// A wave's line of svx_sam_pack_count: status [i]; fields: five planes of n_lines (tid pos flag mapq l_seq), counts: three (CIGAR
+// words, name bytes, SEQ bytes) -- zero where the status is not 0.
+template <class E>
+SVX_SAM_HD void pack_count_line(E& ex, const uint8_t* text, const int64_t* line_off, uint64_t i, uint64_t n_lines, const RefTable& rt,
+                                bool with_seq, int32_t* status, int32_t* fields, int32_t* counts)
+{
+    uint64_t lo, hi;
+    line_bounds(text, line_off, i, &lo, &hi);
+    Packed pk = {0, 0, 0, 0, 0, 0, 0, 0};
+    const int32_t st = pack_measure(ex, text, lo, hi, rt, with_seq, &pk);
+    if (st != 0) pk = Packed{0, 0, 0, 0, 0, 0, 0, 0};             // (the host's line: measured, but its counts are the host's to give)
+    ex.each([&](uint32_t l) {
+        if (l != 0) return;
+        status[i] = st;
+        fields[i] = pk.tid; fields[n_lines + i] = pk.pos; fields[2 * n_lines + i] = pk.flag; fields[3 * n_lines + i] = pk.mapq;
+        fields[4 * n_lines + i] = pk.l_seq;
+        counts[i] = pk.words; counts[n_lines + i] = pk.name_bytes; counts[2 * n_lines + i] = pk.seq_bytes;
+    });
+}
+
+// What svx_sam_pack_extract writes to: element i of the field arrays, and the record's own slots [off[i], off[i + 1]) of the rest.
+struct PackOut {
+    int32_t* tid; int32_t* pos; int32_t* l_seq; int16_t* flag; uint8_t* mapq;
+    const int64_t* cig_off; uint32_t* cigar; const int64_t* name_off; uint8_t* names; const int64_t* seq_off; uint8_t* seq;
+};
+
+// A wave's line of svx_sam_pack_extract: a line of status 0 written -- the fields, and the words, name bytes and (o.seq given) SEQ bytes
+// into slots of exactly the sizes svx_sam_pack_count gave.  Every store is checked against its slot, so offsets that are not the
+// counts' prefix lose data and write nowhere else.  Lines of another status are the caller's.
+template <class E>
+SVX_SAM_HD void pack_extract_line(E& ex, const uint8_t* text, const int64_t* line_off, uint64_t i, const RefTable& rt, const int32_t* status,
+                                  const PackOut& o)
+{
+    if (status[i] != 0) return;
+    uint64_t lo, hi, s[11], e[11];
+    line_bounds(text, line_off, i, &lo, &hi);
+    if (lo >= hi || split_fields(ex, text, lo, hi, s, e) < 10) return;          // (not a line of status 0)
+    int64_t flag = 0, pos = 0, mapq = 0;
+    if (parse_ranged(text, s[1], e[1], 0, 65535, &flag) || parse_ranged(text, s[3], e[3], 0, 0x7FFFFFFF, &pos)
+        || parse_ranged(text, s[4], e[4], 0, 255, &mapq)) return;
+    const int32_t tid = ref_lookup(text, s[2], e[2], rt);
+    const uint64_t l_seq = e[9] - s[9] == 1 && text[s[9]] == '*' ? 0 : e[9] - s[9];
+    ex.each([&](uint32_t l) {
+        if (l != 0) return;
+        o.tid[i] = tid; o.pos[i] = (int32_t)(pos - 1); o.l_seq[i] = (int32_t)l_seq; o.flag[i] = (int16_t)(uint16_t)flag; o.mapq[i] = (uint8_t)mapq;
+    });
+    // ---- the name and its '\n'
+    const uint64_t l_name = e[0] - s[0];
+    const uint64_t name_room = (uint64_t)(o.name_off[i + 1] - o.name_off[i]);
+    if (name_room == l_name + 1) {
+        uint8_t* const to = o.names + o.name_off[i];
+        copy_text(ex, text, s[0], e[0], to);
+        ex.each([&](uint32_t l) { if (l == 0) to[l_name] = '\n'; });
+    }
+    // ---- the CIGAR words: the lane of a letter, its index the letters in front of it
+    if (!(e[5] - s[5] == 1 && text[s[5]] == '*')) {
+        const uint64_t room = (uint64_t)(o.cig_off[i + 1] - o.cig_off[i]);
+        uint32_t* const to = o.cigar + o.cig_off[i];
+        uint64_t n_ops = 0;
+        for (uint64_t at = s[5]; at < e[5]; at += WAVE) {
+            const uint64_t letters = ex.ballot([&](uint32_t l) { return at + l < e[5] && !is_digit(text[at + l]); });
+            ex.each([&](uint32_t l) {
+                if (!(letters >> l & 1)) return;
+                const uint64_t k = n_ops + popc64(letters & ((1ull << l) - 1));
+                if (k < room) to[k] = cigar_word(text, s[5], at + l);
+            });
+            n_ops += popc64(letters);
+        }
+    }
+    // ---- SEQ: 16 text bytes a lane and step -> 8 bytes, single byte stores (the neighbours' bytes are other waves')
+    if (o.seq && l_seq) {
+        const uint64_t room = (uint64_t)(o.seq_off[i + 1] - o.seq_off[i]);
+        uint8_t* const to = o.seq + o.seq_off[i];
+        if (room == (l_seq + 1) / 2) {
+            for (uint64_t at = 0; at < l_seq; at += WAVE * 16) {
+                ex.each([&](uint32_t l) {
+                    const uint64_t p = at + (uint64_t)l * 16;
+                    if (p >= l_seq) return;
+                    uint8_t b[16];
+                    memcpy(b, text + s[9] + p, 16);             // (up to 15 bytes behind the field: the line's own bytes or the slack)
+                    for (uint32_t j = 0; j < 16 && p + j < l_seq; j += 2)
+                        to[(p + j) / 2] = (uint8_t)(base_code(b[j]) << 4 | (p + j + 1 < l_seq ? base_code(b[j + 1]) : 0u));
+                });
+            }
+        }
+    }
 }
 
 }  // namespace svx_sam

@@ -17,10 +17,28 @@ what was missing is the order.  :func:`load_sample`:
 The whole file's packed records are resident on the device on this path -- nothing streams out before the last range is read.
 The table equals, array for array, read_bam() of the same records written as a file sorted stably by that key.  A corrupt block, a
 CRC mismatch, a malformed or cut chain or a device allocation that fails raises SortIngestError; no partial result is returned.
+
+The input may also be SAM text, a pipe, or a list of BAM / SAM inputs: what an aligner writes, taken with no alignment file in
+between.  The pass then has a second form, for text:
+
+  text      a SAM file in chunks of ``range_bytes`` of text cut at line ends (io.sam.chunk_places); a path that is no regular file
+            (``-``, a FIFO, /dev/fd/N) through io.sam.StreamReader, read ONCE on a thread of its own into pinned buffers.  Per chunk:
+            upload, svx_sam_lines, svx_sam_pack_count, the counts read back, svx_sam_pack_extract -- the chunk's lines become the
+            arrays a range of a BAM leaves (no BAM record in between, the tags are never read), and the text is dropped.  A line whose
+            CIGAR is the placeholder ``<l_seq>S<n>N`` (SVX_SAM_HOST) is encoded by io.sam.encode_line; its counts and bytes go into
+            the line's own slots, so the chunk's records stay in file order
+  several   the header is sort.merge_headers over the inputs; SAM parts resolve their names against the merged dictionary (a part
+            without header is fine), a BAM part's tids go through its old -> merged table; the parts follow each other in list
+            order, so the stable sort leaves ties in list order, then file order.  At most one input is ``-``
+A BAM or gzip data on a pipe is refused (SVX_DEVICE_SORT=write takes a BAM there).  A failure closes the pipe's read end, so the
+aligner ends with SIGPIPE; the message names the input and the line.
 """
+import os
+import struct
+
 import numpy as np
 
-STAGES = ("read", "upload", "inflate", "crc", "find_starts", "walk", "concat", "sort", "gather", "read_back", "names", "scan")
+STAGES = ("read", "upload", "inflate", "crc", "find_starts", "walk", "lines", "pack", "concat", "sort", "gather", "read_back", "names", "scan")
 
 
 class SortIngestError(ValueError):
@@ -69,39 +87,294 @@ def _cat_offsets(torch, parts, totals, dev):
     return torch.cat(out)
 
 
+class _Source:
+    """One input of :func:`load_sample`: ``kind`` ("bam", "sam": text in a regular file, "pipe": text read once), the path, the ``name``
+    messages call it (``<stdin>`` for ``-``), its own header -- ``references``, ``lengths``, ``text`` (a headerless SAM part: none) --,
+    ``bam_head`` (read_bam_header's, a BAM), ``first``: (the file offset, the lines) in front of the first alignment line of text,
+    ``reader``: the io.sam.StreamReader of a pipe, and ``remap``: a BAM part's old -> merged tid table among several inputs."""
+    bam_head = reader = remap = None
+    first = (0, 0)
+
+    def __init__(self, kind, path, name):
+        self.kind, self.path, self.name = kind, path, name
+
+    def close(self, failed=False):
+        """The pipe's reader ended and its descriptor closed; ``failed``: standard input is pointed at the null device, so that the
+        writer of the pipe ends with EPIPE and does not block."""
+        if self.reader is None:
+            return
+        self.reader.close()
+        if failed and self.path == "-":
+            null = os.open(os.devnull, os.O_RDONLY)
+            os.dup2(null, 0)
+            os.close(null)
+
+
+def _open_source(path, alone):
+    """An input opened and its header read -> _Source.  SAM text without an @SQ line is fine as one of several inputs (not ``alone``)."""
+    from . import sort
+    from .io import sam
+    from .io.bam import read_bam_header
+    if sort.is_stream(path):
+        src = _Source("pipe", path, sam.STREAM_NAME if path == "-" else path)
+        try:
+            src.reader = sam.StreamReader(0 if path == "-" else os.open(path, os.O_RDONLY), own=path != "-")
+        except OSError as exc:
+            raise SortIngestError("%s: %s" % (src.name, exc)) from None
+        try:
+            kind = sam.stream_kind(src.reader.peek())
+            if kind == sam.STREAM_BAM:
+                raise SortIngestError("%s: a BAM on a pipe is not taken under SVX_DEVICE_SORT=1 -- SVX_DEVICE_SORT=write sorts it in one pass, "
+                                      "or give the aligner's SAM text" % src.name)
+            if kind == sam.STREAM_GZIP:
+                raise SortIngestError("%s: gzip-compressed data that is no BAM -- compressed SAM is not taken: decompress it in the pipe, "
+                                      "`pigz -dc x.sam.gz | ... -b -`" % src.name)
+            if kind != sam.STREAM_SAM:
+                raise SortIngestError("%s: %s" % (src.name, "no input" if kind == sam.STREAM_EMPTY else "neither SAM text nor a BAM"))
+            text = src.reader.header()
+        except BaseException:
+            src.close(failed=True)
+            raise
+    else:
+        try:
+            with open(path, "rb") as f:
+                start = f.read(1 << 20)
+        except OSError as exc:
+            raise SortIngestError("%s: %s" % (path, exc)) from None
+        if not sam.is_sam_text(start):
+            src = _Source("bam", path, path)
+            try:
+                src.bam_head = read_bam_header(path)
+            except ValueError as exc:                           # (the host reader inflates in front of the header's end: a corrupt block shows here)
+                raise SortIngestError(str(exc)) from None
+            src.references, src.lengths, src.text = src.bam_head.references, src.bam_head.lengths, src.bam_head.header_text
+            return src
+        src = _Source("sam", path, path)
+        try:
+            text = sam.header_end(path)
+        except (sam.SamError, OSError) as exc:
+            raise SortIngestError("%s: %s" % (path, exc)) from None
+    src.first = (len(text), text.count(b"\n"))
+    if not alone and not any(l.startswith(b"@SQ\t") for l in text.split(b"\n")):
+        src.references, src.lengths, src.text = [], [], text.decode("latin-1")
+        return src
+    try:
+        head = sam.parse_header(text)
+    except sam.SamError as exc:
+        src.close(failed=True)
+        raise SortIngestError("%s: %s" % (src.name, exc)) from None
+    src.references, src.lengths, src.text = head.references, head.lengths, head.text
+    return src
+
+
+def _host_packed(line, tid_of):
+    """A line the kernels leave to the host -> ((tid, pos, flag, mapq, l_seq), the CIGAR words (uint32), the name bytes and their
+    '\\n', the 4-bit SEQ bytes) by io.sam.encode_line -- which checks the whole line, its tags too.  The words of a placeholder CIGAR
+    are those of the line's first CG:B:I tag, as the BAM walk takes them; without that tag the two operations are what they say."""
+    from .io import sam
+    rec = sam.encode_line(line, tid_of)
+    tid, pos, l_name, mapq, _bin, n_cig, flag, l_seq = struct.unpack_from("<iiBBHHHi", rec, 4)
+    words = np.frombuffer(rec, "<u4", n_cig, 36 + l_name)
+    for tag in line.split(b"\t")[11:]:
+        if tag == b"CG:B:I" or tag.startswith(b"CG:B:I,"):
+            words = np.array([int(v) for v in tag[7:].split(b",")] if len(tag) > 7 else [], np.uint32)
+            break
+    seq_at = 36 + l_name + 4 * n_cig
+    return (tid, pos, flag, mapq, l_seq), words, rec[36:36 + l_name - 1] + b"\n", rec[seq_at:seq_at + (l_seq + 1) // 2]
+
+
+class _TextPass:
+    """What the chunks of one text input share: the device, the merged dictionary as the kernels' table and as the host's, the
+    buffers, the count of the lines the host took, and ``n_lines``: the lines of the chunk taken last."""
+
+    def __init__(self, torch, lib, kernels, dev, clock, references, with_seq):
+        from . import index
+        from .io import sam
+        self.torch, self.lib, self.kernels, self.dev, self.clock, self.with_seq = torch, lib, kernels, dev, clock, with_seq
+        self.tid_of, self.table = sam.tid_table(references), kernels.sam_ref_table(references, dev)
+        self.pinned, self.host_lines, self.n_lines, self.Range = None, 0, 0, index.RecordRange
+
+    def refuse(self, src, line, line_no, code):
+        """The error of a line, worded by the host statement of the rules."""
+        from .io import sam
+        try:
+            sam.encode_line(b"\t".join(line.split(b"\t")[:11]), self.tid_of)
+        except sam.SamError as exc:
+            return SortIngestError("%s: %s" % (src.name, exc.at(line_no)))
+        return SortIngestError("%s: line %d: not an alignment line (svx_sam_pack_count: %d)" % (src.name, line_no, code))
+
+    def chunk(self, src, data, pinned, n, line_no):
+        """A chunk of text -- ``data``: its bytes on the host, ``pinned``: the pinned tensor they lie in, ``line_no`` lines in front
+        of it -> the RecordRange of its records (None: no line), the text dropped."""
+        from .io import sam
+        torch, kernels, dev, clock, with_seq = self.torch, self.kernels, self.dev, self.clock, self.with_seq
+        d_text = torch.empty(n + kernels.SAM_SLACK, dtype=torch.uint8, device=dev)
+        d_text[:n].copy_(pinned[:n], non_blocking=True)
+        d_text[n:] = 0
+        clock.lap("upload")
+        d_line_off, n_lines = kernels.sam_lines(d_text, n)
+        self.n_lines = n_lines
+        clock.lap("lines")
+        if n_lines == 0:
+            return None
+        d_status, _d_fields, d_counts = kernels.sam_pack_count(d_text, n, d_line_off, n_lines, self.table, with_seq)
+        status, counts = d_status.cpu().numpy(), d_counts.cpu().numpy().astype(np.int64)
+        host = {}
+        if status.any():
+            line_off = d_line_off[:n_lines + 1].cpu().numpy()
+
+            def line(i):
+                text = bytes(data[int(line_off[i]):int(line_off[i + 1])])
+                return text[:-1] if text.endswith(b"\n") else text
+            bad = np.flatnonzero(status < kernels.SAM_HOST)
+            if bad.size:
+                raise self.refuse(src, line(int(bad[0])), line_no + int(bad[0]) + 1, int(status[bad[0]]))
+            for i in np.flatnonzero(status == kernels.SAM_HOST):
+                try:
+                    host[int(i)] = _host_packed(line(int(i)), self.tid_of)
+                except sam.SamError as exc:
+                    raise SortIngestError("%s: %s" % (src.name, exc.at(line_no + int(i) + 1))) from None
+                _fields, words, name, bases = host[int(i)]
+                counts[:, i] = len(words), len(name), len(bases) if with_seq else 0
+            self.host_lines += len(host)
+        # ---- the records' slots: the exclusive prefix of the counts, the host's lines among them
+        off = np.zeros((3, n_lines + 1), np.int64)
+        np.cumsum(counts, axis=1, out=off[:, 1:])
+        rng = self.Range()
+        rng.n_rec, rng.words, rng.name_bytes, rng.seq_bytes = n_lines, int(off[0, -1]), int(off[1, -1]), int(off[2, -1])
+        out = {"d_tid": torch.empty(n_lines, dtype=torch.int32, device=dev), "d_pos": torch.empty(n_lines, dtype=torch.int32, device=dev),
+               "d_l_seq": torch.empty(n_lines, dtype=torch.int32, device=dev), "d_flag": torch.empty(n_lines, dtype=torch.int16, device=dev),
+               "d_mapq": torch.empty(n_lines, dtype=torch.uint8, device=dev),
+               "d_cigar": torch.empty(max(rng.words, 1) + 4, dtype=torch.int32, device=dev),
+               "d_names": torch.empty(max(rng.name_bytes, 1), dtype=torch.uint8, device=dev)}
+        if with_seq:
+            out["d_seq"] = torch.empty((max(rng.seq_bytes, 1) + 15) // 16 * 16, dtype=torch.uint8, device=dev)
+        d_off = kernels.sam_pack_extract(d_text, n, d_line_off, n_lines, self.table, d_status, list(off[:3 if with_seq else 2]), out)
+        for i, (fields, words, name, bases) in host.items():
+            for key, v in zip(("d_tid", "d_pos", "d_flag", "d_mapq", "d_l_seq"), fields):
+                out[key][i] = v - 65536 if key == "d_flag" and v > 32767 else v
+            pieces = [("d_cigar", 0, words.view(np.int32)), ("d_names", 1, np.frombuffer(name, np.uint8))]
+            if with_seq:
+                pieces.append(("d_seq", 2, np.frombuffer(bases, np.uint8)))
+            for key, k, piece in pieces:
+                if piece.size:
+                    out[key][int(off[k, i]):int(off[k, i]) + piece.size].copy_(torch.from_numpy(piece.copy()))
+        for key, t in out.items():
+            setattr(rng, key, t)
+        rng.d_cig_off, rng.d_name_off = d_off[0], d_off[1]
+        if with_seq:
+            rng.d_seq_off = d_off[2]
+        clock.lap("pack")
+        return rng
+
+    def parts(self, src, range_bytes):
+        """Generator: the RecordRange of every chunk of the text input ``src``."""
+        from . import sort
+        from .io import sam
+        torch, clock = self.torch, self.clock
+        step = range_bytes or sort.DEFAULT_SAM_CHUNK_BYTES
+        if src.kind == "sam":
+            line_no = src.first[1]
+            for at, n in sam.chunk_places(src.path, src.first[0], step):
+                if self.pinned is None or self.pinned.numel() < n:
+                    self.pinned = torch.empty(n, dtype=torch.uint8, pin_memory=True)
+                if self.lib.svx_read_range(src.path.encode(), at, n, self.pinned.data_ptr(), sort.SAM_READ_THREADS) != 0:
+                    raise SortIngestError("%s: %s" % (src.path, self.lib.svx_bam_error().decode()))
+                clock.lap("read", False)
+                yield self.chunk(src, self.pinned[:n].numpy(), self.pinned, n, line_no)
+                line_no += self.n_lines                         # (svx_sam_lines' count of the chunk: no second count on the host)
+            return
+        pinned = {}
+
+        def alloc(n):                                           # a pinned buffer as the reader takes it: its NumPy view
+            t = torch.empty(n, dtype=torch.uint8, pin_memory=True)
+            a = t.numpy()
+            pinned[a.ctypes.data] = t
+            return a
+        for buf, n, line_no in src.reader.chunks(step, src.first[1], alloc):
+            clock.lap("read", False)
+            yield self.chunk(src, buf[:n], pinned[buf.ctypes.data], n, line_no)
+
+
+def _remapped(torch, src, d_tid, dev):
+    """A BAM part's packed tids through its old -> merged table; -1 stays, a value outside the part's dictionary raises."""
+    if bool(((d_tid < -1) | (d_tid >= len(src.remap))).any()):
+        raise SortIngestError("%s: a record names a reference outside the file's dictionary of %d" % (src.name, len(src.remap)))
+    if np.array_equal(src.remap, np.arange(len(src.remap))):
+        return d_tid
+    d_map = torch.from_numpy(np.ascontiguousarray(src.remap, np.int32)).to(dev)
+    return torch.where(d_tid < 0, d_tid, d_map[d_tid.clamp(min=0).long()])
+
+
 def load_sample(bam_path, fasta, min_sv, device="cuda", with_seq=False, range_bytes=None, stats=None):
-    """The :class:`svision_amd.sample.Sample` of a BAM whose records come in any order (see the head of the module).  ``with_seq``: the
-    table carries the read bases (--hash / --graph).  ``range_bytes``: compressed bytes a range (default: the device decoder's group
-    size; tests).  ``stats``: a dict that receives the number of ranges and records, the CIGAR words and the seconds per stage."""
-    from . import index, kernels
-    from .io.bam import AlignmentTable, read_bam_header
+    """The :class:`svision_amd.sample.Sample` of records that come in any order (see the head of the module).  ``bam_path``: a BAM, SAM
+    text, ``-`` or another path that is no regular file (text read once), or a list of those.  ``with_seq``: the table carries the
+    read bases (--hash / --graph).  ``range_bytes``: compressed bytes a range of a BAM (default: the device decoder's group size),
+    text bytes a chunk of SAM text (default: sort.DEFAULT_SAM_CHUNK_BYTES); tests.  ``stats``: a dict that receives the number of
+    ranges and records, the CIGAR words, the inputs' kinds, the lines the host took and the seconds per stage."""
+    from . import index, kernels, sort
+    from .io import sam
+    from .io.bam import AlignmentTable
     from .sample import Sample
     torch, lib, dev, clock = index.on_device("load_sample needs the GPU (svx_record_sort)", device, STAGES)
-    try:
-        head = read_bam_header(bam_path)
-    except ValueError as exc:                                   # (the host reader inflates in front of the header's end: a corrupt block shows here)
-        raise SortIngestError(str(exc)) from None
-    n_ref = len(head.references)
+    paths = sort.input_paths(bam_path)
+    label = paths[0] if len(paths) == 1 else "%s (+ %d more)" % (paths[0], len(paths) - 1)
+    if paths.count("-") > 1:
+        raise SortIngestError("%s is named twice: standard input is one stream" % sam.STREAM_NAME)
     fields = ("d_tid", "d_pos", "d_flag", "d_mapq", "d_l_seq")
-    parts, n, words, name_bytes, seq_bytes, ranges = [], 0, 0, 0, 0, 0
+    parts, n, words, name_bytes, seq_bytes, ranges, host_lines, sources = [], 0, 0, 0, 0, 0, 0, []
     try:
-        with torch.cuda.device(dev):
-            for rng in index.record_ranges(bam_path, head, dev, clock, range_bytes, with_seq=with_seq):
-                ranges += 1
-                rng.d_raw = rng.d_starts = rng.d_base = None    # the range's inflated bytes go now, not with the next range
-                if rng.n_rec:
-                    parts.append(rng)
-                    n, words, name_bytes, seq_bytes = n + rng.n_rec, words + rng.words, name_bytes + rng.name_bytes, seq_bytes + rng.seq_bytes
-            if n > 0xFFFFFFFF:
-                raise SortIngestError("%s: %d records -- svx_record_sort takes up to 2^32 - 1" % (bam_path, n))
-            if n == 0:
-                raise SortIngestError("%s holds no record" % bam_path)
-            arrays = _sort_and_gather(torch, kernels, dev, clock, parts, fields, n, words, n_ref, head.lengths, with_seq)
-    except index.IndexBuildError as exc:
-        raise SortIngestError(str(exc)) from None
-    except torch.cuda.OutOfMemoryError as exc:
-        raise SortIngestError("%s: the device has no room for the file's packed records -- %d records and %d CIGAR words seen so far (%s)"
-                              % (bam_path, n, words, str(exc).split("\n")[0])) from None
+        for p in paths:
+            sources.append(_open_source(p, len(paths) == 1))
+        if len(sources) == 1:
+            references, lengths, header_text = sources[0].references, sources[0].lengths, sources[0].text
+            label = sources[0].name
+        else:
+            try:
+                merged = sort.merge_headers([(s.name, s.text, s.references, s.lengths) for s in sources])
+            except sort.SortWriteError as exc:
+                raise SortIngestError(str(exc)) from None
+            references, lengths, header_text = merged.references, merged.lengths, merged.text
+            for s, table in zip(sources, merged.maps):
+                s.remap = table if s.kind == "bam" else None
+        n_ref = len(references)
+        try:
+            with torch.cuda.device(dev):
+                for src in sources:
+                    if src.kind == "bam":
+                        ranges_of = index.record_ranges(src.path, src.bam_head, dev, clock, range_bytes, with_seq=with_seq)
+                    else:
+                        text_pass = _TextPass(torch, lib, kernels, dev, clock, references, with_seq)
+                        ranges_of = text_pass.parts(src, range_bytes)
+                    for rng in ranges_of:
+                        ranges += 1
+                        if rng is None:
+                            continue
+                        rng.d_raw = rng.d_starts = rng.d_base = None    # the range's inflated bytes go now, not with the next range
+                        if rng.n_rec:
+                            if src.remap is not None:
+                                rng.d_tid = _remapped(torch, src, rng.d_tid, dev)
+                            parts.append(rng)
+                            n, words, name_bytes, seq_bytes = n + rng.n_rec, words + rng.words, name_bytes + rng.name_bytes, seq_bytes + rng.seq_bytes
+                    if src.kind != "bam":
+                        host_lines += text_pass.host_lines
+                        del text_pass
+                if n > 0xFFFFFFFF:
+                    raise SortIngestError("%s: %d records -- svx_record_sort takes up to 2^32 - 1" % (label, n))
+                if n == 0:
+                    raise SortIngestError("%s holds no record" % label)
+                arrays = _sort_and_gather(torch, kernels, dev, clock, parts, fields, n, words, n_ref, lengths, with_seq)
+        except index.IndexBuildError as exc:
+            raise SortIngestError(str(exc)) from None
+        except torch.cuda.OutOfMemoryError as exc:
+            raise SortIngestError("%s: the device has no room for the file's packed records -- %d records and %d CIGAR words seen so far (%s)"
+                                  % (label, n, words, str(exc).split("\n")[0])) from None
+    except BaseException:
+        for s in sources:
+            s.close(failed=True)
+        raise
+    for s in sources:
+        s.close()
     del parts
     host, d_cigar, d_cig_off, d_pos, pos_bits = arrays
     # QNAME ids by first occurrence in the SORTED file (ingest_gpu.DeviceDecoder._make_finish is the pattern)
@@ -113,15 +386,15 @@ def load_sample(bam_path, fasta, min_sv, device="cuda", with_seq=False, range_by
     n_unique = int(lib.svx_name_ids(names_h.ctypes.data, name_off.ctypes.data, n, name_id.ctypes.data, uniq.ctypes.data, ub.ctypes.data))
     name_list = uniq[:int(ub[0])].tobytes().decode().split("\n")[:-1] if n_unique else []
     clock.lap("names", False)
-    table = AlignmentTable(head.references, head.lengths, host["tid"], host["pos"], host["flag"].view(np.uint16), host["mapq"], host["l_seq"],
-                           name_id, name_list, host["cigar"][:words].view(np.uint32), host["cig_off"], head.header_text)
+    table = AlignmentTable(references, lengths, host["tid"], host["pos"], host["flag"].view(np.uint16), host["mapq"], host["l_seq"],
+                           name_id, name_list, host["cigar"][:words].view(np.uint32), host["cig_off"], header_text)
     if with_seq:
         table.seq_packed, table.seq_off = host["seq"][:seq_bytes], host["seq_off"][:n]
     sample = Sample.from_device(table, fasta, min_sv, d_cigar[:max(words, 1)], d_cig_off, d_pos)
     clock.lap("scan")
     if stats is not None:
         stats.update(ranges=ranges, records=n, cigar_words=words, pos_bits=pos_bits, passes=len(digit_plan(n_ref, pos_bits)),
-                     seconds={k: round(v, 6) for k, v in clock.times.items()})
+                     inputs=[s.kind for s in sources], host_lines=host_lines, seconds={k: round(v, 6) for k, v in clock.times.items()})
     return sample
 
 

@@ -1088,3 +1088,57 @@ def sam_encode(d_text, n_bytes, line_off, n_lines, table, d_len, d_off, out_base
                                   table.name_off.data_ptr(), table.names.data_ptr(), table.n, d_len.data_ptr(), d_off.data_ptr(), int(out_base),
                                   out.data_ptr(), status.data_ptr(), _stream_ptr(d_text.device)), "svx_sam_encode")
     return out
+
+
+# ---- SAM text -> the device ingest's packed arrays (svx_sam.hip; the caller: svision_amd/ingest_sort.py) ----
+def sam_pack_count(d_text, n_bytes, line_off, n_lines, table, with_seq=False):
+    """A wave a line -> (status int32 [n_lines], fields int32 [5, n_lines]: tid pos flag mapq l_seq, counts int32 [3, n_lines]: CIGAR
+    words, name bytes, SEQ bytes) on the device.  status: 0, SAM_HOST (a ``<l_seq>S<n>N`` CIGAR: the caller's), or an error code
+    (svision_amd.io.sam.E_*).  See include/svx.h svx_sam_pack_count."""
+    lib = _lib.load()
+    _require_text(d_text, n_bytes)
+    dev = d_text.device
+    if line_off.dtype != torch.int64 or line_off.numel() < n_lines + 1 or n_lines > 0xFFFFFFFF:
+        raise _lib.SvxError("line_off must be int64 [n_lines + 1]")
+    status = torch.empty(n_lines, dtype=torch.int32, device=dev)
+    fields, counts = torch.empty((5, n_lines), dtype=torch.int32, device=dev), torch.empty((3, n_lines), dtype=torch.int32, device=dev)
+    _lib.check(lib.svx_sam_pack_count(d_text.data_ptr(), line_off.data_ptr(), n_lines, table.hash.data_ptr(), table.tid.data_ptr(),
+                                      table.name_off.data_ptr(), table.names.data_ptr(), table.n, int(bool(with_seq)), status.data_ptr(),
+                                      fields.data_ptr(), counts.data_ptr(), _stream_ptr(dev)), "svx_sam_pack_count")
+    return status, fields, counts
+
+
+def sam_pack_extract(d_text, n_bytes, line_off, n_lines, table, status, offsets, out):
+    """A wave a line: every line with ``status[i] == 0`` into the packed arrays ``out`` -- a dict of device tensors d_tid d_pos d_l_seq
+    (int32 [n_lines]), d_flag (int16), d_mapq (uint8), d_cigar (int32), d_names (uint8) and, for the bases, d_seq (uint8).
+    ``offsets``: host int64 arrays [n_lines + 1] (cigar, names and, with d_seq, seq), the exclusive prefix of sam_pack_count's counts;
+    they must ascend and end inside their array, which is checked here.  -> the offsets on the device, in that order.  See
+    include/svx.h svx_sam_pack_extract."""
+    lib = _lib.load()
+    _require_text(d_text, n_bytes)
+    dev = d_text.device
+    with_seq = out.get("d_seq") is not None
+    want = (("d_tid", torch.int32), ("d_pos", torch.int32), ("d_l_seq", torch.int32), ("d_flag", torch.int16), ("d_mapq", torch.uint8))
+    for name, dtype in want:
+        _require_cuda(out[name], name)
+        if out[name].dtype != dtype or out[name].numel() < n_lines:
+            raise _lib.SvxError("%s must be %s [n_lines]" % (name, dtype))
+    data = [("d_cigar", torch.int32), ("d_names", torch.uint8)] + ([("d_seq", torch.uint8)] if with_seq else [])
+    if len(offsets) != len(data) or status.dtype != torch.int32 or status.numel() < n_lines or line_off.numel() < n_lines + 1:
+        raise _lib.SvxError("status must be int32 [n_lines], and one offsets array per data array")
+    d_off = []
+    for (name, dtype), off in zip(data, offsets):
+        _require_cuda(out[name], name)
+        off = np.ascontiguousarray(off, np.int64)
+        if out[name].dtype != dtype or off.size != n_lines + 1 or int(off[0]) < 0 or (np.diff(off) < 0).any() or int(off[-1]) > out[name].numel():
+            raise _lib.SvxError("svx_sam_pack_extract: the offsets of %s do not ascend inside its %d elements" % (name, out[name].numel()))
+        d_off.append(torch.from_numpy(off).to(dev))
+    spare = torch.empty(4, dtype=torch.uint8, device=dev)      # (an array of no element has no address: nothing is written there)
+    ptr = lambda t: t.data_ptr() if t.numel() else spare.data_ptr()
+    seq = (d_off[2].data_ptr(), ptr(out["d_seq"])) if with_seq else (None, None)
+    _lib.check(lib.svx_sam_pack_extract(d_text.data_ptr(), line_off.data_ptr(), n_lines, table.hash.data_ptr(), table.tid.data_ptr(),
+                                        table.name_off.data_ptr(), table.names.data_ptr(), table.n, status.data_ptr(), out["d_tid"].data_ptr(),
+                                        out["d_pos"].data_ptr(), out["d_flag"].data_ptr(), out["d_mapq"].data_ptr(), out["d_l_seq"].data_ptr(),
+                                        d_off[0].data_ptr(), ptr(out["d_cigar"]), d_off[1].data_ptr(), ptr(out["d_names"]),
+                                        seq[0], seq[1], _stream_ptr(dev)), "svx_sam_pack_extract")
+    return d_off
