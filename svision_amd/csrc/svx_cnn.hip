@@ -396,6 +396,10 @@ void active_lists_kernel(const uint32_t* __restrict__ touched, const uint32_t* _
     const uint32_t img = blockIdx.x;
     const uint32_t n_all = n;                                // images launched (the image counter of d_totals)
     if (live) n = min(n, *live);                             // lists over the launch's distinct images only
+    if (n == 0 && img == 0) {                                // no live image: no list, but the counts and the image counter are still this launch's
+        if (t < 4) counts[t] = 0;
+        if (t == 0 && totals) atomicAdd(&totals[4], (unsigned long long)n_all);
+    }
     if (img >= n) return;
     uint32_t part[8] = {0, 0, 0, 0, 0, 0, 0, 0};             // [0..4): images before this one, [4..8): all images
     for (uint32_t i = t; i < n; i += BLOCK) {

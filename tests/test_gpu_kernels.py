@@ -362,22 +362,13 @@ def test_fc8_softmax_and_packed_predict():
     assert np.abs(packed[:, :5] - prob.cpu().numpy()).max() < 1e-5
 
 
-def _dilate(m, r):
-    out = np.zeros_like(m)
-    h, w = m.shape[-2:]
-    pad = np.pad(m, [(0, 0)] * (m.ndim - 2) + [(r, r), (r, r)])
-    for dy in range(2 * r + 1):
-        for dx in range(2 * r + 1):
-            out |= pad[..., dy:dy + h, dx:dx + w]
-    return out
-
-
 def test_active_sets_match_a_numpy_restatement(oracle_lib):
     """Touched pixels of the first layer (vs the oracle's rasterised images) and the four pixel lists derived from them
     (vs dilation / pooling of boolean arrays)."""
     from oracle import cbind
     from bench import random_weights
     from svision_amd.network.alexnet import AlexNet
+    from tests.conv1cases import dilate, pool_any
     n = 70
     rec_np = datagen.random_records(n, seed=21, hostile=True)
     net = AlexNet(random_weights(0), device=DEV)
@@ -393,14 +384,10 @@ def test_active_sets_match_a_numpy_restatement(oracle_lib):
     assert np.array_equal(got, want)
     l2, l3, l4, l5, counts = kernels.alexnet_active_sets(touched)
     counts = counts.cpu().numpy()
-    a2 = _dilate(want, 2)
-    p2 = np.zeros((n, 13, 13), bool)
-    for y in range(13):
-        for x in range(13):
-            p2[:, y, x] = a2[:, 2 * y:2 * y + 3, 2 * x:2 * x + 3].any((1, 2))
-    a3 = _dilate(p2, 1)
-    a4 = _dilate(a3, 1)
-    a5 = _dilate(a4, 1)
+    a2 = dilate(want, 2)
+    a3 = dilate(pool_any(a2), 1)
+    a4 = dilate(a3, 1)
+    a5 = dilate(a4, 1)
     for lst, cnt, mask in ((l2, counts[0], a2), (l3, counts[1], a3), (l4, counts[2], a4), (l5, counts[3], a5)):
         assert np.array_equal(lst.cpu().numpy()[:cnt], np.flatnonzero(mask.reshape(-1)))          # active first, ascending
         assert np.array_equal(lst.cpu().numpy()[cnt:], np.flatnonzero(~mask.reshape(-1)))         # then everything else
