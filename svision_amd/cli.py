@@ -187,7 +187,8 @@ def load_rank_table(options, rank, ws):
     """The alignment records rank ``rank`` of ``ws`` needs.  With a ``.bai`` next to the BAM and more than one rank, a
     rank is a set of chromosomes: the header gives the task list, the index gives the byte range holding this rank's
     records, and only that range is read and inflated (upstream: AlignmentFile.fetch(chrom), run_collection.py:26)."""
-    index = next((c for c in (options.bam_path + ".bai", os.path.splitext(options.bam_path)[0] + ".bai") if os.path.exists(c)), None)
+    from .io.bam import find_index
+    index = find_index(options.bam_path)                        # (.bai, else .csi)
     if ws == 1 or index is None:
         return read_bam(options.bam_path, with_seq=bool(options.hash or options.graph))
     head = read_bam(options.bam_path, tids=[], index=index)
@@ -228,7 +229,8 @@ def _write_sorted(options):
     one has not touched the device when the helpers of ``-t N`` are forked.  It inherits the environment: ``SVX_SORT_TABLES=dynamic``
     there is ``--tables dynamic`` (Huffman codes built per block; default: the fixed code), ``SVX_SORT_MEMORY=BYTES`` (K, M or G) is
     ``--memory``: the device memory for the records' inflated bytes, beyond which the file is written in spans, a pass over the input
-    for each (default: half of the free device memory).  ``-b a.bam,b.bam,c.sam`` (:func:`_input_list`): the inputs merged into the one sorted
+    for each (default: half of the free device memory), ``SVX_SORT_INDEX=csi`` is ``--csi``: the index written as a ``.csi``, the format for
+    positions from 2^29 on.  ``-b a.bam,b.bam,c.sam`` (:func:`_input_list`): the inputs merged into the one sorted
     file ``OUT/<first input's stem>.merged.sorted.bam``."""
     import json
     import subprocess
@@ -257,7 +259,7 @@ def _write_sorted(options):
     logging.info("%s is %s: %d records sorted on the device in %.2f s (%d range(s), %d radix passes)", options.bam_path,
                  "%d inputs to merge" % len(inputs) if len(inputs) > 1 else "SAM text" if stats.get("input") == "sam" else "not coordinate sorted", stats["records"], time.perf_counter() - t0,
                  stats["ranges"], stats["passes"])
-    logging.info("sorted file: %s (+ .bai), %d BGZF blocks, %d -> %d bytes, written in %d span(s) under a budget of %d bytes for the records "
+    logging.info("sorted file: %s (+ its index), %d BGZF blocks, %d -> %d bytes, written in %d span(s) under a budget of %d bytes for the records "
                  "(SVX_SORT_MEMORY)", out, stats["blocks"], stats["inflated_bytes"], stats["compressed_bytes"], stats["spans"], stats["memory_bytes"])
     return out
 
@@ -324,11 +326,13 @@ def _open_input(options, sample, ws, tick):
         if head is not None and head.sort_order == "coordinate":
             fasta = Fasta(options.genome)
             index = find_index(options.bam_path)
-            build_index = index is None and os.environ.get("SVX_BUILD_INDEX") == "1"
+            # (SVX_BUILD_INDEX=1: a .bai; =csi: a .csi, the format for positions from 2^29 on -- "bai" / "csi", or False)
+            build_index = index is None and {"1": "bai", "csi": "csi"}.get(os.environ.get("SVX_BUILD_INDEX"), False)
             if build_index and ws > 1:
                 # (every rank would build the same file; one build in front of the launch serves them all)
-                logging.error("SVX_BUILD_INDEX=1 builds the index in a single-rank run only: build it first with "
-                              "`python -m svision_amd.index %s` and start the %d ranks again", options.bam_path, ws)
+                logging.error("SVX_BUILD_INDEX=%s builds the index in a single-rank run only: build it first with "
+                              "`python -m svision_amd.index %s%s` and start the %d ranks again", os.environ["SVX_BUILD_INDEX"],
+                              "--csi " if build_index == "csi" else "", options.bam_path, ws)
                 raise SystemExit(1)
             return RunInput(None, fasta, head.references, head.lengths, index, build_index)
         if os.environ.get("SVX_DEVICE_SORT") == "write":
@@ -411,10 +415,11 @@ def _set_up_device(dev, options, inp, tasks, mine, dirs, rank, ws, tick):
     index, device = inp.index, torch.device("cuda", torch.cuda.current_device())
     threads = decode_threads(int(os.environ.get("LOCAL_WORLD_SIZE", ws)), options.thread_num)      # inflate threads of this rank
     if inp.build_index:
-        # SVX_BUILD_INDEX=1 and no .bai next to the BAM: built on the device (svision_amd/index.py) into the output directory --
+        # SVX_BUILD_INDEX=1 (=csi: a .csi) and no index next to the BAM: built on the device (svision_amd/index.py) into the output directory --
         # the BAM's own may be read-only --, and the device engine serves the run
         from .index import build_index
-        index = build_index(options.bam_path, os.path.join(dirs.out_path, os.path.basename(options.bam_path) + ".bai"), device=device)
+        index = build_index(options.bam_path, os.path.join(dirs.out_path, os.path.basename(options.bam_path) + "." + inp.build_index), device=device,
+                            **(dict(fmt="csi") if inp.build_index == "csi" else {}))
         logging.info("no index next to %s: built %s on the device", options.bam_path, index)
         tick("index built on the device")
     dev.feed = ChromosomeFeed(options.bam_path, inp.fasta, options, [c for c in mine if c in inp.references], inp.references, inp.lengths,

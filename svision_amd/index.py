@@ -1,4 +1,5 @@
-"""Build the ``.bai`` of a BAM that has none, on the device: ``python -m svision_amd.index sample.bam [-o sample.bam.bai]``.
+"""Build the ``.bai`` of a BAM that has none, on the device: ``python -m svision_amd.index sample.bam [-o sample.bam.bai]`` -- or its
+``.csi`` (``--csi [-m MIN_SHIFT]``), the format for references with positions from 2^29 on, which a ``.bai`` cannot address.
 
 The device ingest engine (svision_amd/ingest_gpu.py) starts every parallel step of its record walk at an entry of the .bai
 linear index; a file without one was left to the host engine.  Indexing it with the usual tools is a single-threaded pass over
@@ -14,7 +15,7 @@ yields every record's reference span -- except knowing where records start when 
   carry      a record the range's end cuts is not lost: the next range begins with the block it starts in, and its start is
              that range's known record start -- at most one record's blocks are inflated twice.  A range in which no record
              completes is read again, twice as large
-  assembly   host: svision_amd.io.bai.bai_bytes, written under a temporary name in the target's directory and renamed
+  assembly   host: svision_amd.io.bai.bai_bytes (``fmt="csi"``: io.csi.csi_bytes), written under a temporary name in the target's directory and renamed
 
 A corrupt block, a CRC mismatch, a malformed or cut record chain or a file that is not coordinate-sorted raises IndexBuildError
 (a ValueError); no file is left behind.  A plain loop: nothing here overlaps reading, inflating and walking.
@@ -409,16 +410,36 @@ def _index_fields(lib, torch, kernels, dev, rng, clock):
     return out
 
 
-def build_index(bam_path, out_path=None, device="cuda", range_bytes=None, stats=None):
-    """Write the ``.bai`` of ``bam_path`` to ``out_path`` (default ``bam_path + ".bai"``) and return that path.  ``range_bytes``:
+FORMATS = ("bai", "csi")
+
+
+def too_long_message(exc, references, switch):
+    """What a caller says of a bai.TooLong: the reference's name, the position, why, and the ``switch`` that writes a .csi."""
+    name = references[exc.tid] if 0 <= exc.tid < len(references) else "#%d" % exc.tid
+    return "a record at position %d of %s ends at %d: %s -- %s" % (exc.pos, name, exc.end, exc.why, switch)
+
+
+def index_bytes(fmt, min_shift, head, tid, pos, end, flag, voff, voff_end):
+    """The assembly call of either format over the same record arrays -> the index file's bytes."""
+    if fmt == "csi":
+        from .io import csi
+        return csi.csi_bytes(len(head.references), head.lengths, tid, pos, end, flag, voff, voff_end, min_shift=min_shift)
+    return bai.bai_bytes(len(head.references), tid, pos, end, flag, voff, voff_end)
+
+
+def build_index(bam_path, out_path=None, device="cuda", range_bytes=None, stats=None, fmt="bai", min_shift=14):
+    """Write the ``.bai`` of ``bam_path`` to ``out_path`` (default ``bam_path + ".bai"``) and return that path; ``fmt="csi"``: its
+    ``.csi`` (default ``bam_path + ".csi"``) with bins of 2^``min_shift`` bases at the lowest level.  A ``.bai`` is refused
+    (IndexBuildError, no file) for a record that reaches position 2^29: there is no automatic switch of format.  ``range_bytes``:
     compressed bytes a range (default: the device decoder's group size; tests).  ``stats``: a dict that receives the number of
     ranges, blocks and records and the seconds per stage -- in total ("seconds") and per range ("per_range")."""
     from . import kernels
     from .io.bam import read_bam_header
     torch, lib, dev, clock = on_device("build_index needs the GPU (svx_bam_find_starts)", device)
-    out_path = out_path or bam_path + ".bai"
+    if fmt not in FORMATS:
+        raise ValueError("fmt: %r is none of %s" % (fmt, ", ".join(FORMATS)))
+    out_path = out_path or bam_path + "." + fmt
     head = read_bam_header(bam_path)
-    n_ref = len(head.references)
     parts, per_range, n_blocks, end_voff = [], [], 0, None
     for rng in record_ranges(bam_path, head, dev, clock, range_bytes):
         blocks, dst = rng.blocks, rng.dst
@@ -434,7 +455,10 @@ def build_index(bam_path, out_path=None, device="cuda", range_bytes=None, stats=
     voff_end = np.append(voff[1:], end_voff).astype(np.uint64)
     pos64 = pos.astype(np.int64)
     try:
-        data = bai.bai_bytes(n_ref, tid, pos64, pos64 + np.maximum(span.astype(np.int64), 1), flag, voff, voff_end)
+        data = index_bytes(fmt, min_shift, head, tid, pos64, pos64 + np.maximum(span.astype(np.int64), 1), flag, voff, voff_end)
+    except bai.TooLong as exc:
+        raise IndexBuildError("%s: %s" % (bam_path, too_long_message(exc, head.references, "write a .csi instead: --csi (SVX_BUILD_INDEX=csi)"
+                                                                     if fmt == "bai" else "a larger depth is needed"))) from None
     except ValueError as exc:
         raise IndexBuildError("%s: %s" % (bam_path, exc)) from None
     write_into_place(out_path, data)
@@ -453,14 +477,16 @@ def _umask():
 
 def main(argv=None):
     import argparse
-    ap = argparse.ArgumentParser(prog="python -m svision_amd.index", description="Build the .bai of a coordinate-sorted BAM on the GPU.")
+    ap = argparse.ArgumentParser(prog="python -m svision_amd.index", description="Build the .bai, or the .csi, of a coordinate-sorted BAM on the GPU.")
     ap.add_argument("bam")
-    ap.add_argument("-o", "--output", default=None, help="the index to write (default: BAM + .bai)")
+    ap.add_argument("-o", "--output", default=None, help="the index to write (default: BAM + .bai, with --csi BAM + .csi)")
+    ap.add_argument("-c", "--csi", action="store_true", help="write a .csi: the format for references with positions from 2^29 on")
+    ap.add_argument("-m", "--min-shift", type=int, default=14, metavar="MIN_SHIFT", help="with --csi: log2 of the smallest bin (default 14)")
     ap.add_argument("--device", default="cuda")
     args = ap.parse_args(argv)
     stats = {}
     try:
-        path = build_index(args.bam, args.output, device=args.device, stats=stats)
+        path = build_index(args.bam, args.output, device=args.device, stats=stats, **(dict(fmt="csi", min_shift=args.min_shift) if args.csi else {}))
     except (IndexBuildError, OSError) as exc:
         print("svision_amd.index: %s" % exc, file=sys.stderr)
         return 1

@@ -511,6 +511,7 @@ class ChromosomeFeed:
     def _host_parts(self, which):
         """Stage A, host engine: BGZF inflate on host threads (libdeflate, io.bam.BamStream) -- whole chromosomes, each
         decoded into this process's memory and written to a slot from there.  -> False: the feed is closing."""
+        logging.info("%s: records decoded by the host engine%s", self.bam_path, "" if self.index is None else " through %s" % self.index)
         stream = BamStream(self.bam_path, with_seq=self.with_seq, threads=self.threads, tids=which, index=self.index)
         try:
             for table in stream:
@@ -533,8 +534,12 @@ class ChromosomeFeed:
         n_read = int(os.environ.get("SVX_READ_THREADS", "0")) or min(8, max(1, self.threads))
         dec = self.decoder = DeviceDecoder(self.bam_path, self.index, self.references, self.lengths, self.header_text, self.device,
                                            threads=n_read, take_slot=self.slots.take, with_seq=self.with_seq)
-        if not dec.usable(tids):
+        why = dec.unusable(tids)
+        if why is not None:
+            logging.info("%s: %s", self.index, why)
+            self.stats["engine"] = "cpu"
             return self._host_parts(tids)
+        logging.info("%s: records decoded by the device engine through %s", self.bam_path, self.index)
         windows_of = self._windows_of if self.tasks is not None and not getattr(self.options, "contig", False) else None
         # (SVX_SLICE_MARGIN: tests -- a margin that is too small must be noticed and the slices cut again)
         margin = (int(os.environ.get("SVX_SLICE_MARGIN", "0")) or dec.estimate_reach(tids)) if windows_of is not None else 0

@@ -40,7 +40,8 @@ import numpy as np
 import torch
 
 from . import _lib, kernels, streams
-from .io.bam import AlignmentTable, read_bai_linear
+from .io.bam import AlignmentTable
+from .io.csi import spans as index_spans, voff_at        # noqa: F401 -- (voff_at: the .bai look-up, part of this module's interface)
 
 FIRST_GROUP_BYTES = 192 << 20            # the first launch is small (~7 k blocks): the pipeline starts after ~0.1 s
 STAGE_BYTES = 64 << 20                   # a pinned staging slot of the reader (_StagingRing: eight of them)
@@ -204,23 +205,6 @@ class Unit:
                                                  "" if self.to_end else ", cut")
 
 
-def voff_at(span, coord):
-    """Linear-index look-up: the virtual offset of the first record of the reference overlapping the 16 kb bin of ``coord`` or
-    a later one (SAMv1 5.1.3) -- every record that reaches beyond the start of that bin lies at or behind it --, clamped to
-    the reference's records [lo, hi).  Entries of 0 (bins a writer left unfilled) are skipped."""
-    lo, hi, linear = span
-    if coord <= 0:
-        return int(lo)
-    b = int(coord) >> 14
-    if b >= linear.size:
-        return int(hi)
-    tail = linear[b:]
-    nz = tail[tail != 0]
-    if nz.size == 0:
-        return int(hi)
-    return int(min(max(int(nz[0]), int(lo)), int(hi)))
-
-
 def cut_groups(tids, size_of, first_limits, limit, merge_last=True):
     """Chromosomes in file order -> the groups whose blocks are inflated in one launch: the first groups of at most
     ``first_limits`` compressed bytes (the very first is small: the pipeline behind starts after one short launch), the others of at
@@ -310,7 +294,8 @@ class DeviceDecoder:
         self.take_slot = take_slot or _PrivateSlot               # callable() -> the slot of the next part (ingest._SlotPool.take: shared memory)
         self.with_seq = bool(with_seq)                           # the walk also packs the read bases (svx_bam_walk_*_seq): tables with seq_off + a LazySeq
         self.lib = _lib.load()
-        self.spans = read_bai_linear(index)
+        # per reference None or its span in the index, .bai (LinearSpan) or .csi (CsiSpan): lo, hi, seeds, from_voff, to_voff
+        self.spans = index_spans(index, decoder=True)
         self.size = os.path.getsize(path)
         self.stats = {"read_s": 0.0, "h2d_inflate_s": 0.0, "walk_s": 0.0, "d2h_s": 0.0, "names_s": 0.0, "blocks": 0, "bytes_in": 0, "bytes_inflated": 0}
         self._mark("index read")
@@ -320,7 +305,18 @@ class DeviceDecoder:
             self.trace.append((round(time.perf_counter() - self._t0, 4), what))
 
     def usable(self, tids):
-        return all(t < len(self.spans) and (self.spans[t] is None or self.spans[t][2].size > 0) for t in tids)
+        return self.unusable(tids) is None
+
+    def unusable(self, tids):
+        """Why the index does not serve the device engine for ``tids``, or None where it does."""
+        for t in tids:
+            if t >= len(self.spans):
+                return "the index has %d references, the run wants reference %d" % (len(self.spans), t)
+            span = self.spans[t]
+            if span is not None and not span.usable:
+                return ("the .csi has min_shift %d: the device engine cuts its slices at 16 kb windows (min_shift 14)" % span.min_shift
+                        if hasattr(span, "min_shift") else "the .bai has no linear index for reference %d" % t)
+        return None
 
     def _with_records(self, tids):
         """The references of ``tids`` that have records, in file order."""
@@ -364,14 +360,16 @@ class DeviceDecoder:
             i = 0
             while i < len(wins):
                 j = i + 1
-                v0 = voff_at(span, wins[i][0])
-                while j < len(wins) and (((voff_at(span, wins[j][1]) >> 16) - (v0 >> 16)) <= slice_bytes
+                v0 = span.from_voff(wins[i][0])
+                while j < len(wins) and (((span.to_voff(wins[j][1]) >> 16) - (v0 >> 16)) <= slice_bytes
                                          or (i > 0 and wins[j - 1][1] - wins[i][0] < min_span)):
                     j += 1
                 lo, hi = wins[i][0], wins[j - 1][1]
                 # (on the right TWICE the margin: the entry of a bin is the first record that overlaps it, which may start a whole read
-                # length in front of it -- and the slice holds the records in front of THAT one)
-                vlo, vhi = voff_at(span, lo - margin), (span[1] if j == len(wins) and hi >= self.lengths[t] else voff_at(span, hi + 2 * margin))
+                # length in front of it -- and the slice holds the records in front of THAT one.  A .csi's right end is a true upper
+                # bound -- every record that starts in front of the coordinate is in --, yet the formula stays: the completeness check
+                # goes by the slice's LAST record, which has to start behind what the windows need)
+                vlo, vhi = span.from_voff(lo - margin), (span[1] if j == len(wins) and hi >= self.lengths[t] else span.to_voff(hi + 2 * margin))
                 vhi = max(vhi, vlo)
                 if vhi == vlo and vlo < span[1]:
                     # Both look-ups found the SAME record: either a coverage gap (it starts behind the slice) or ONE record that spans
@@ -379,9 +377,7 @@ class DeviceDecoder:
                     # record behind it that starts inside the windows, must not be dropped as "a slice without a record" (ADVICE r5).
                     # The slice takes the records up to the next entry of the index that lies behind this one: it is never empty
                     # here, and the consumer's completeness check (ChromosomeFeed._slice_complete) sees the spanning record.
-                    tail = span[2][max(0, (hi + 2 * margin) >> 14):]
-                    later = tail[tail > vlo]
-                    vhi = int(min(int(later[0]), int(span[1]))) if later.size else int(span[1])
+                    vhi = span.next_behind(hi + 2 * margin, vlo)
                 units.append(Unit(t, lo, hi, vlo, vhi, left_edge=None if vlo == span[0] else max(0, (lo - margin) >> 14 << 14), to_end=vhi == span[1],
                                   first=i == 0, last=j == len(wins), windows=wins[i:j]))
                 i = j
@@ -406,7 +402,7 @@ class DeviceDecoder:
         try:
             tid = min((s[0], t) for t, s in enumerate(self.spans) if s is not None and (tids is None or t in tids))[1]
             # (from the middle of the reference: the reads at its start are cut to it -- all of them short)
-            v0 = voff_at(self.spans[tid], self.lengths[tid] // 2) if tid < len(self.lengths) else self.spans[tid][0]
+            v0 = self.spans[tid].from_voff(self.lengths[tid] // 2) if tid < len(self.lengths) else self.spans[tid][0]
             if v0 >= self.spans[tid][1]:
                 v0 = self.spans[tid][0]
             start = v0 >> 16

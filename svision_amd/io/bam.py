@@ -321,13 +321,14 @@ def _table_from_handle(lib, h, with_seq, threads=0):
 def read_bam(path, with_seq=False, threads=0, tids=None, index=None):
     """Decode a BAM file into an :class:`AlignmentTable` with the native multi-threaded decoder of libsvx.so
     (svx_bam_*); ``with_seq``: keep the 4-bit read bases (needed by --hash only).  ``tids`` (with a ``.bai`` next to
-    the file or given as ``index``): decode only the byte range holding those references' records -- one rank's
+    the file or given as ``index``, a ``.bai`` or a ``.csi``: io.csi.spans): decode only the byte range holding those references' records -- one rank's
     chromosome shard -- instead of the whole file."""
     from .. import _lib
     lib = _lib.load()
     flags = 1 if with_seq else 0                          # SVX_BAM_KEEP_SEQ
     if tids is not None:
-        spans = read_bai(index or (path + ".bai"))
+        from .csi import spans as index_spans
+        spans = index_spans(index or (path + ".bai"))
         have = [spans[t] for t in tids if t < len(spans) and spans[t] is not None]
         if have:
             h = lib.svx_bam_open_range(path.encode(), int(threads), flags, min(s[0] for s in have), max(s[1] for s in have))
@@ -392,15 +393,16 @@ def read_bam_header(path):
 
 
 def find_index(path):
-    """The .bai next to a BAM (``x.bam.bai`` or ``x.bai``), or None."""
-    return next((c for c in (path + ".bai", os.path.splitext(path)[0] + ".bai") if os.path.exists(c)), None)
+    """The index next to a BAM -- ``x.bam.bai``, ``x.bai``, then ``x.bam.csi``, ``x.csi`` --, or None."""
+    stem = os.path.splitext(path)[0]
+    return next((c for c in (path + ".bai", stem + ".bai", path + ".csi", stem + ".csi") if os.path.exists(c)), None)
 
 
 class BamStream:
     """Iterator over a BAM file's reference sequences: yields one :class:`AlignmentTable` per reference that has
     records (file order; all tables carry the whole reference dictionary and the file's ``tid`` numbering; QNAME ids
     count from 0 in every table), each as soon as it is decoded, while the native reader's own threads read and inflate
-    the next ones (svx_bam_stream_*).  ``tids`` + a ``.bai``: only those references' byte ranges are read (a rank's
+    the next ones (svx_bam_stream_*).  ``tids`` + a ``.bai`` or ``.csi``: only those references' byte ranges are read (a rank's
     chromosomes); ``tids`` without an index: the whole file is streamed and the other references are skipped.
 
     What the reference does window by window through pysam's ``fetch`` (run_collection.py:23-26)."""
@@ -414,7 +416,8 @@ class BamStream:
         if tids is not None and index is None:
             index = find_index(path)
         if tids is not None and index is not None:
-            spans = read_bai(index)
+            from .csi import spans as index_spans
+            spans = index_spans(index)
             have = sorted(spans[t] for t in self.keep if t < len(spans) and spans[t] is not None)
             voffs = np.asarray([v for span in have for v in span], np.uint64)
             if not have:                                       # nothing of this rank's in the file: an empty range

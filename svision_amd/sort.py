@@ -22,6 +22,8 @@ and a genome browser read --, with every record byte kept: qualities and aux tag
             the file
   index     svision_amd.io.bai.bai_bytes on the sorted fields, end = pos + max(span, 1), the virtual offsets from the records' stream
             offsets, the 0xFF00 cut and the prefix of the members' lengths; both files are renamed into place together
+            (``index_format="csi"`` / ``--csi`` / ``SVX_SORT_INDEX=csi``: io.csi.csi_bytes and ``.csi``; a record that reaches position
+            2^29 is refused under the default ``.bai``, and neither file is left)
 
 Device memory: the records' inflated bytes once -- or a span of them, see below -- (the stream is allocated before the pass, sized by
 the sum of the BGZF members' ISIZE fields, and every range's slice is copied straight into it), one range of the pass, 8 bytes of key + 20 of sort workspace a
@@ -445,16 +447,16 @@ class BgzfWriter:
         index.discard(self.tmp)
 
 
-def commit_pair(tmp_bam, out_path, bai_data):
-    """The written temporary file becomes ``out_path`` and ``bai_data`` its ``.bai``: the pair or nothing -- a failure leaves neither
-    file nor temporary, a sorted file that was already in place is removed again when its index cannot follow."""
-    f, tmp_bai = index.temp_beside(out_path + ".bai")
+def commit_pair(tmp_bam, out_path, bai_data, suffix=".bai"):
+    """The written temporary file becomes ``out_path`` and ``bai_data`` its ``.bai`` (``suffix=".csi"``: its ``.csi``): the pair or nothing
+    -- a failure leaves neither file nor temporary, a sorted file that was already in place is removed again when its index cannot follow."""
+    f, tmp_bai = index.temp_beside(out_path + suffix)
     try:
         with f:
             f.write(bai_data)
         index.into_place(tmp_bam, out_path)
         try:
-            index.into_place(tmp_bai, out_path + ".bai")
+            index.into_place(tmp_bai, out_path + suffix)
         except OSError:
             os.unlink(out_path)
             raise
@@ -1311,21 +1313,27 @@ SAM_SOURCE = Source("sam", _sam_key_pass, _sam_again, lambda dv, opened, kp: _sa
 PIPE_SOURCE = Source("pipe", _pipe_key_pass, _pipe_again, _pipe_fill)
 
 
-def _bai(opened, kp, od, written):
-    """index: the ``.bai`` of the written file, from the sorted fields and the writer's ledger -> its bytes."""
+def _bai(opened, kp, od, written, fmt="bai"):
+    """index: the ``.bai`` (``fmt="csi"``: the ``.csi``) of the written file, from the sorted fields and the writer's ledger -> its bytes."""
     from .io import bai
     voff = bai.virtual_offsets(written.dst, written.coff, (od.off_out + len(opened.header)).astype(np.uint64))
     order = od.order
     tid, pos, flag, span = kp.tid[order], kp.pos[order].astype(np.int64), kp.flag[order], kp.span[order].astype(np.int64)
     try:
-        return bai.bai_bytes(len(opened.head.references), tid, pos, pos + np.maximum(span, 1), flag, voff[:-1], voff[1:])
+        return index.index_bytes(fmt, 14, opened.head, tid, pos, pos + np.maximum(span, 1), flag, voff[:-1], voff[1:])
+    except bai.TooLong as exc:
+        raise SortWriteError("%s: %s" % (opened.path, index.too_long_message(exc, opened.head.references, "write a .csi instead: --csi "
+                                                                            "(SVX_SORT_INDEX=csi; sort_bam's index_format)"))) from None
     except ValueError as exc:
         raise SortWriteError("%s: %s" % (opened.path, exc)) from None
 
 
-def sort_bam(bam_path, out_path, device="cuda", range_bytes=None, chunk_bytes=None, stats=None, tables="fixed", memory_bytes=None):
+def sort_bam(bam_path, out_path, device="cuda", range_bytes=None, chunk_bytes=None, stats=None, tables="fixed", memory_bytes=None,
+             index_format="bai"):
     """Write the records of ``bam_path`` in coordinate order to ``out_path`` and its index to ``out_path + ".bai"`` (see the head of the
-    module); returns ``out_path``.  ``range_bytes``: compressed bytes a range of the pass (default: the device decoder's group size),
+    module); returns ``out_path``.  ``index_format="csi"``: the index is ``out_path + ".csi"`` and no ``.bai`` is written -- the sorted file's
+    bytes are the same.  Under "bai" a record that reaches position 2^29 is refused (SortWriteError, neither file written): a ``.bai``
+    cannot address it, and the format is never switched without being asked.  ``range_bytes``: compressed bytes a range of the pass (default: the device decoder's group size),
     ``chunk_bytes``: inflated bytes a chunk of the output (default DEFAULT_CHUNK_BYTES; whole blocks, at least one) -- tests pass small
     values.  ``tables``: "fixed" -- every block in the fixed Huffman code or stored -- or "dynamic": Huffman codes built per block where
     they are smaller; the inflated bytes and the index's records are the same.  ``memory_bytes``: the budget for the records' inflated
@@ -1350,6 +1358,8 @@ def sort_bam(bam_path, out_path, device="cuda", range_bytes=None, chunk_bytes=No
     torch, lib, dev, clock = index.on_device("sort_bam needs the GPU (svx_record_sort, svx_bgzf_deflate)", device, STAGES)
     if tables not in TABLES:
         raise ValueError("tables: %r is none of %s" % (tables, ", ".join(TABLES)))
+    if index_format not in index.FORMATS:
+        raise ValueError("index_format: %r is none of %s" % (index_format, ", ".join(index.FORMATS)))
     dv = _Dev(torch, lib, kernels, dev, clock)
     chunk_blocks = max(int(chunk_bytes or DEFAULT_CHUNK_BYTES) // BLOCK, 1)
     budget = None if memory_bytes is None else max(int(memory_bytes), 1)
@@ -1372,7 +1382,7 @@ def sort_bam(bam_path, out_path, device="cuda", range_bytes=None, chunk_bytes=No
                 writer.put(*piece)
                 del piece                                       # (the chunk's buffer goes before the generator allocates the next)
             written = writer.finish()
-            commit_pair(writer.tmp, out_path, _bai(opened, kp, od, written))
+            commit_pair(writer.tmp, out_path, _bai(opened, kp, od, written, index_format), "." + index_format)
             clock.lap("index", False)
             done = True
     except index.IndexBuildError as exc:
@@ -1421,7 +1431,9 @@ def main(argv=None):
     ap.add_argument("bam", nargs="+", help="an unsorted BAM or SAM text; several: their records merged into the one sorted file.  ``-`` (once) is "
                                            "standard input, and a path that is no regular file (a FIFO, /dev/fd/N) is read once like it: an aligner's "
                                            "output through a pipe")
-    ap.add_argument("-o", "--output", required=True, help="the sorted BAM to write (its index: OUTPUT + .bai)")
+    ap.add_argument("-o", "--output", required=True, help="the sorted BAM to write (its index: OUTPUT + .bai, with --csi OUTPUT + .csi)")
+    ap.add_argument("-c", "--csi", action="store_true", default=os.environ.get("SVX_SORT_INDEX") == "csi",
+                    help="write the index as a .csi: the format for references with positions from 2^29 on (default: $SVX_SORT_INDEX=csi)")
     ap.add_argument("--device", default="cuda")
     ap.add_argument("--chunk-bytes", type=int, default=None, help="inflated bytes a chunk of the output (default %d)" % DEFAULT_CHUNK_BYTES)
     ap.add_argument("--tables", choices=TABLES, default=os.environ.get("SVX_SORT_TABLES") or "fixed",
@@ -1433,10 +1445,12 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.tables not in TABLES:
         ap.error("SVX_SORT_TABLES=%s: fixed or dynamic" % args.tables)
+    if os.environ.get("SVX_SORT_INDEX") not in (None, "", "bai", "csi"):
+        ap.error("SVX_SORT_INDEX=%s: bai or csi" % os.environ["SVX_SORT_INDEX"])
     stats = {}
     try:
         path = sort_bam(args.bam[0] if len(args.bam) == 1 else args.bam, args.output, device=args.device, chunk_bytes=args.chunk_bytes, stats=stats, tables=args.tables,
-                        memory_bytes=args.memory)
+                        memory_bytes=args.memory, **(dict(index_format="csi") if args.csi else {}))
     except (SortWriteError, _lib.SvxError, OSError) as exc:
         print("svision_amd.sort: %s" % exc, file=sys.stderr)
         return 1
