@@ -33,10 +33,11 @@ between.  The pass then has a second form, for text:
 A BAM or gzip data on a pipe is refused (SVX_DEVICE_SORT=write takes a BAM there).  A failure closes the pipe's read end, so the
 aligner ends with SIGPIPE; the message names the input and the line.
 """
-import os
 import struct
 
 import numpy as np
+
+from . import textin
 
 STAGES = ("read", "upload", "inflate", "crc", "find_starts", "walk", "lines", "pack", "concat", "sort", "gather", "read_back", "names", "scan")
 
@@ -88,83 +89,44 @@ def _cat_offsets(torch, parts, totals, dev):
 
 
 class _Source:
-    """One input of :func:`load_sample`: ``kind`` ("bam", "sam": text in a regular file, "pipe": text read once), the path, the ``name``
-    messages call it (``<stdin>`` for ``-``), its own header -- ``references``, ``lengths``, ``text`` (a headerless SAM part: none) --,
-    ``bam_head`` (read_bam_header's, a BAM), ``first``: (the file offset, the lines) in front of the first alignment line of text,
-    ``reader``: the io.sam.StreamReader of a pipe, and ``remap``: a BAM part's old -> merged tid table among several inputs."""
-    bam_head = reader = remap = None
-    first = (0, 0)
+    """One input of :func:`load_sample`: the textin.TextInput -- its ``kind`` ("bam", "sam": text in a regular file, "pipe": text read
+    once), ``path`` and the ``name`` messages call it --, its own header -- ``references``, ``lengths``, ``text`` (a headerless SAM
+    part: none) --, ``bam_head`` (read_bam_header's, a BAM) and ``remap``: a BAM part's old -> merged tid table among several inputs."""
 
-    def __init__(self, kind, path, name):
-        self.kind, self.path, self.name = kind, path, name
-
-    def close(self, failed=False):
-        """The pipe's reader ended and its descriptor closed; ``failed``: standard input is pointed at the null device, so that the
-        writer of the pipe ends with EPIPE and does not block."""
-        if self.reader is None:
-            return
-        self.reader.close()
-        if failed and self.path == "-":
-            null = os.open(os.devnull, os.O_RDONLY)
-            os.dup2(null, 0)
-            os.close(null)
+    def __init__(self, inp, references, lengths, text, bam_head=None):
+        self.input, self.kind, self.path, self.name = inp, inp.kind, inp.path, inp.name
+        self.references, self.lengths, self.text, self.bam_head, self.remap = references, lengths, text, bam_head, None
 
 
 def _open_source(path, alone):
     """An input opened and its header read -> _Source.  SAM text without an @SQ line is fine as one of several inputs (not ``alone``)."""
-    from . import sort
     from .io import sam
     from .io.bam import read_bam_header
-    if sort.is_stream(path):
-        src = _Source("pipe", path, sam.STREAM_NAME if path == "-" else path)
-        try:
-            src.reader = sam.StreamReader(0 if path == "-" else os.open(path, os.O_RDONLY), own=path != "-")
-        except OSError as exc:
-            raise SortIngestError("%s: %s" % (src.name, exc)) from None
-        try:
-            kind = sam.stream_kind(src.reader.peek())
-            if kind == sam.STREAM_BAM:
-                raise SortIngestError("%s: a BAM on a pipe is not taken under SVX_DEVICE_SORT=1 -- SVX_DEVICE_SORT=write sorts it in one pass, "
-                                      "or give the aligner's SAM text" % src.name)
-            if kind == sam.STREAM_GZIP:
-                raise SortIngestError("%s: gzip-compressed data that is no BAM -- compressed SAM is not taken: decompress it in the pipe, "
-                                      "`pigz -dc x.sam.gz | ... -b -`" % src.name)
-            if kind != sam.STREAM_SAM:
-                raise SortIngestError("%s: %s" % (src.name, "no input" if kind == sam.STREAM_EMPTY else "neither SAM text nor a BAM"))
-            text = src.reader.header()
-        except BaseException:
-            src.close(failed=True)
-            raise
-    else:
-        try:
-            with open(path, "rb") as f:
-                start = f.read(1 << 20)
-        except OSError as exc:
-            raise SortIngestError("%s: %s" % (path, exc)) from None
-        if not sam.is_sam_text(start):
-            src = _Source("bam", path, path)
-            try:
-                src.bam_head = read_bam_header(path)
-            except ValueError as exc:                           # (the host reader inflates in front of the header's end: a corrupt block shows here)
-                raise SortIngestError(str(exc)) from None
-            src.references, src.lengths, src.text = src.bam_head.references, src.bam_head.lengths, src.bam_head.header_text
-            return src
-        src = _Source("sam", path, path)
-        try:
-            text = sam.header_end(path)
-        except (sam.SamError, OSError) as exc:
-            raise SortIngestError("%s: %s" % (path, exc)) from None
-    src.first = (len(text), text.count(b"\n"))
-    if not alone and not any(l.startswith(b"@SQ\t") for l in text.split(b"\n")):
-        src.references, src.lengths, src.text = [], [], text.decode("latin-1")
-        return src
     try:
-        head = sam.parse_header(text)
-    except sam.SamError as exc:
-        src.close(failed=True)
-        raise SortIngestError("%s: %s" % (src.name, exc)) from None
-    src.references, src.lengths, src.text = head.references, head.lengths, head.text
-    return src
+        inp = textin.open_input(path)
+    except (sam.SamError, OSError) as exc:
+        raise SortIngestError("%s: %s" % (textin.name_of(path), exc)) from None
+    if inp.kind == "bam":                                       # (gzip that is no BAM too: the reader says what the file lacks)
+        try:
+            head = read_bam_header(path)
+        except ValueError as exc:                               # (the host reader inflates in front of the header's end: a corrupt block shows here)
+            raise SortIngestError(str(exc)) from None
+        return _Source(inp, head.references, head.lengths, head.header_text, head)
+    refusal = {sam.STREAM_BAM: "a BAM on a pipe is not taken under SVX_DEVICE_SORT=1 -- SVX_DEVICE_SORT=write sorts it in one pass, or give "
+                               "the aligner's SAM text",
+               sam.STREAM_GZIP: "gzip-compressed data that is no BAM -- compressed SAM is not taken: decompress it in the pipe, "
+                                "`pigz -dc x.sam.gz | ... -b -`",
+               sam.STREAM_EMPTY: "no input", sam.STREAM_OTHER: "neither SAM text nor a BAM"}.get(inp.peek_kind)
+    if refusal is None:
+        if inp.headerless and not alone:
+            return _Source(inp, [], [], inp.text.decode("latin-1"))
+        try:
+            head = sam.parse_header(inp.text)
+            return _Source(inp, head.references, head.lengths, head.text)
+        except sam.SamError as exc:
+            refusal = str(exc)
+    inp.close(failed=True)
+    raise SortIngestError("%s: %s" % (inp.name, refusal))
 
 
 def _host_packed(line, tid_of):
@@ -185,36 +147,22 @@ def _host_packed(line, tid_of):
 
 class _TextPass:
     """What the chunks of one text input share: the device, the merged dictionary as the kernels' table and as the host's, the
-    buffers, the count of the lines the host took, and ``n_lines``: the lines of the chunk taken last."""
+    reader of the chunks with its pinned buffers (textin.ChunkReader), and the count of the lines the host took."""
 
     def __init__(self, torch, lib, kernels, dev, clock, references, with_seq):
         from . import index
         from .io import sam
-        self.torch, self.lib, self.kernels, self.dev, self.clock, self.with_seq = torch, lib, kernels, dev, clock, with_seq
+        self.torch, self.kernels, self.dev, self.clock, self.with_seq = torch, kernels, dev, clock, with_seq
         self.tid_of, self.table = sam.tid_table(references), kernels.sam_ref_table(references, dev)
-        self.pinned, self.host_lines, self.n_lines, self.Range = None, 0, 0, index.RecordRange
+        self.reader, self.host_lines, self.Range = textin.ChunkReader(torch, lib, clock), 0, index.RecordRange
 
-    def refuse(self, src, line, line_no, code):
-        """The error of a line, worded by the host statement of the rules."""
-        from .io import sam
-        try:
-            sam.encode_line(b"\t".join(line.split(b"\t")[:11]), self.tid_of)
-        except sam.SamError as exc:
-            return SortIngestError("%s: %s" % (src.name, exc.at(line_no)))
-        return SortIngestError("%s: line %d: not an alignment line (svx_sam_pack_count: %d)" % (src.name, line_no, code))
-
-    def chunk(self, src, data, pinned, n, line_no):
-        """A chunk of text -- ``data``: its bytes on the host, ``pinned``: the pinned tensor they lie in, ``line_no`` lines in front
-        of it -> the RecordRange of its records (None: no line), the text dropped."""
+    def chunk(self, src, chunk):
+        """A chunk of text (textin.Chunk: its bytes in pinned memory, ``line_no`` lines in front of it) -> the RecordRange of its
+        records (None: no line), the text dropped."""
         from .io import sam
         torch, kernels, dev, clock, with_seq = self.torch, self.kernels, self.dev, self.clock, self.with_seq
-        d_text = torch.empty(n + kernels.SAM_SLACK, dtype=torch.uint8, device=dev)
-        d_text[:n].copy_(pinned[:n], non_blocking=True)
-        d_text[n:] = 0
-        clock.lap("upload")
-        d_line_off, n_lines = kernels.sam_lines(d_text, n)
-        self.n_lines = n_lines
-        clock.lap("lines")
+        n, line_no = chunk.n, chunk.line_no
+        d_text, d_line_off, n_lines = textin.upload_lines(torch, kernels, dev, clock, chunk)
         if n_lines == 0:
             return None
         d_status, _d_fields, d_counts = kernels.sam_pack_count(d_text, n, d_line_off, n_lines, self.table, with_seq)
@@ -222,16 +170,14 @@ class _TextPass:
         host = {}
         if status.any():
             line_off = d_line_off[:n_lines + 1].cpu().numpy()
-
-            def line(i):
-                text = bytes(data[int(line_off[i]):int(line_off[i + 1])])
-                return text[:-1] if text.endswith(b"\n") else text
             bad = np.flatnonzero(status < kernels.SAM_HOST)
             if bad.size:
-                raise self.refuse(src, line(int(bad[0])), line_no + int(bad[0]) + 1, int(status[bad[0]]))
+                i = int(bad[0])                                 # (the error is worded of the line's 11 fields: the tags are never read here)
+                line = b"\t".join(textin.line_bytes(chunk.data, line_off, i).split(b"\t")[:11])
+                raise SortIngestError("%s: %s" % (src.name, textin.line_refusal(line, self.tid_of, line_no + i + 1, "svx_sam_pack_count", int(status[i]))))
             for i in np.flatnonzero(status == kernels.SAM_HOST):
                 try:
-                    host[int(i)] = _host_packed(line(int(i)), self.tid_of)
+                    host[int(i)] = _host_packed(textin.line_bytes(chunk.data, line_off, i), self.tid_of)
                 except sam.SamError as exc:
                     raise SortIngestError("%s: %s" % (src.name, exc.at(line_no + int(i) + 1))) from None
                 _fields, words, name, bases = host[int(i)]
@@ -269,31 +215,8 @@ class _TextPass:
 
     def parts(self, src, range_bytes):
         """Generator: the RecordRange of every chunk of the text input ``src``."""
-        from . import sort
-        from .io import sam
-        torch, clock = self.torch, self.clock
-        step = range_bytes or sort.DEFAULT_SAM_CHUNK_BYTES
-        if src.kind == "sam":
-            line_no = src.first[1]
-            for at, n in sam.chunk_places(src.path, src.first[0], step):
-                if self.pinned is None or self.pinned.numel() < n:
-                    self.pinned = torch.empty(n, dtype=torch.uint8, pin_memory=True)
-                if self.lib.svx_read_range(src.path.encode(), at, n, self.pinned.data_ptr(), sort.SAM_READ_THREADS) != 0:
-                    raise SortIngestError("%s: %s" % (src.path, self.lib.svx_bam_error().decode()))
-                clock.lap("read", False)
-                yield self.chunk(src, self.pinned[:n].numpy(), self.pinned, n, line_no)
-                line_no += self.n_lines                         # (svx_sam_lines' count of the chunk: no second count on the host)
-            return
-        pinned = {}
-
-        def alloc(n):                                           # a pinned buffer as the reader takes it: its NumPy view
-            t = torch.empty(n, dtype=torch.uint8, pin_memory=True)
-            a = t.numpy()
-            pinned[a.ctypes.data] = t
-            return a
-        for buf, n, line_no in src.reader.chunks(step, src.first[1], alloc):
-            clock.lap("read", False)
-            yield self.chunk(src, buf[:n], pinned[buf.ctypes.data], n, line_no)
+        for chunk in self.reader.chunks(src.input, range_bytes):
+            yield self.chunk(src, chunk)
 
 
 def _remapped(torch, src, d_tid, dev):
@@ -364,17 +287,17 @@ def load_sample(bam_path, fasta, min_sv, device="cuda", with_seq=False, range_by
                 if n == 0:
                     raise SortIngestError("%s holds no record" % label)
                 arrays = _sort_and_gather(torch, kernels, dev, clock, parts, fields, n, words, n_ref, lengths, with_seq)
-        except index.IndexBuildError as exc:
+        except (index.IndexBuildError, textin.ReadError) as exc:
             raise SortIngestError(str(exc)) from None
         except torch.cuda.OutOfMemoryError as exc:
             raise SortIngestError("%s: the device has no room for the file's packed records -- %d records and %d CIGAR words seen so far (%s)"
                                   % (label, n, words, str(exc).split("\n")[0])) from None
     except BaseException:
         for s in sources:
-            s.close(failed=True)
+            s.input.close(failed=True)
         raise
     for s in sources:
-        s.close()
+        s.input.close()
     del parts
     host, d_cigar, d_cig_off, d_pos, pos_bits = arrays
     # QNAME ids by first occurrence in the SORTED file (ingest_gpu.DeviceDecoder._make_finish is the pattern)

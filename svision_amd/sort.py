@@ -141,26 +141,25 @@ known; several inputs: :func:`merge_headers`) -> ``_key_passes`` (per input its 
 ``_pieces_in_core`` or ``_pieces_spanned``: generators of (device buffer, first byte, bytes), a chunk each -> :class:`BgzfWriter`,
 which owns the temporary file and the ledger of members and is handed its encoder (:class:`DeviceEncode`; zlib in the CPU tests) ->
 ``_bai`` -> :func:`commit_pair`.  Which records a chunk or a span takes is one rule, :func:`records_touching`; the 0xFF00 cut one
-function, :func:`block_cuts`.
+function, :func:`block_cuts`.  How an input is opened and classified, a pipe's reader owned and closed, and a chunk of text read into
+pinned memory and uploaded is svision_amd/textin.py's, shared with ingest_sort.load_sample; ``is_stream`` and ``input_paths`` live there.
 """
 import collections
 import os
-import stat
 import struct
 import sys
 import zlib
 
 import numpy as np
 
-from . import _lib, index
+from . import _lib, index, textin
+from .textin import DEFAULT_SAM_CHUNK_BYTES, SAM_READ_THREADS, input_paths, is_stream    # noqa: F401  (their names here are in use)
 
 BLOCK = 0xFF00                                                  # htslib's block size: inflated bytes a BGZF block of the output
 DEFAULT_CHUNK_BYTES = 1024 * BLOCK
 TABLES = ("fixed", "dynamic")                                   # the encoder: svx_bgzf_deflate / svx_bgzf_deflate_dyn
 STAGES = ("read", "upload", "inflate", "crc", "find_starts", "walk", "scan", "read_back", "keep", "join", "sort", "gather", "scatter", "deflate",
           "pack", "download", "write", "index", "lines", "measure", "encode", "host_lines", "retid", "spool")
-SAM_READ_THREADS = 8                                            # svx_read_range's threads for a chunk of text
-DEFAULT_SAM_CHUNK_BYTES = 64 << 20                              # text bytes a chunk of a SAM input (``range_bytes``); see profiles/sort_sam.txt
 
 
 class SortWriteError(ValueError):
@@ -599,7 +598,8 @@ class DeviceEncode:
 # ``remap``: None, or the int32 table of :func:`merge_headers` that takes the input's reference indices into the merged dictionary
 # (a BAM input of several whose table is not the identity: svx_record_retid).
 # ``pipe``: None, or the :class:`_Pipe` the input came through -- still to be read (PIPE_SOURCE) or already in its spool file.
-Opened = collections.namedtuple("Opened", "path head first header room source remap pipe", defaults=(None, None, None))
+# ``text``: None, or the textin.TextInput whose chunks a SAM_SOURCE or PIPE_SOURCE reads.
+Opened = collections.namedtuple("Opened", "path head first header room source remap pipe text", defaults=(None, None, None, None))
 # The input's kind, chosen at open: ``key_pass(dv, opened, range_bytes, kp, d_stream)``: the input's ranges -> ``kp`` (the input's own
 # KeyPass) filled, the records' bytes kept in ``d_stream`` from byte ``kp.base`` on where it is given; ``again(dv, opened, kp, need) ->
 # per range of ``need`` (k, records completed, device bytes, the records' offsets in them [n + 1])``, the ranges of the key pass read
@@ -610,16 +610,6 @@ Source = collections.namedtuple("Source", "name key_pass again fill")
 # the output's -- of one input: that input's own --, ``label`` names the inputs in a message.
 Inputs = collections.namedtuple("Inputs", "opened merged label")
 MergedHead = collections.namedtuple("MergedHead", "references lengths")
-
-
-def input_paths(bam_path):
-    """sort_bam's first argument -> the list of paths: a str is one input, a list or tuple several; none: ValueError."""
-    if isinstance(bam_path, (str, bytes, os.PathLike)):
-        return [os.fsdecode(bam_path)]
-    paths = [os.fsdecode(p) for p in bam_path]
-    if not paths:
-        raise ValueError("sort_bam: an empty list of inputs")
-    return paths
 
 
 # What the steps of one run share besides the device: where the output goes (a spool lies beside it), the output's chunk, the budget
@@ -639,15 +629,14 @@ def _open_all(paths, dv=None, run=None):
         return Inputs([opened], opened, opened.path if opened.pipe is None else opened.pipe.name)
     opened = [_open(p, alone=False, run=run) for p in paths]
     merged = merge_headers([(o.path, o.head.text if o.source in (SAM_SOURCE, PIPE_SOURCE) else o.head.header_text, o.head.references, o.head.lengths) for o in opened])
+    header = sam.bam_header_bytes(sam.SamHead(merged.references, merged.lengths, merged.text, "coordinate"))
     for i, o in enumerate(opened):
-        if o.source is PIPE_SOURCE:                             # a pipe among several: spooled from its first byte, in the merged numbering
-            opened[i] = _pipe_spooled(dv, o._replace(head=sam.SamHead(merged.references, merged.lengths, o.head.text, o.head.sort_order)),
-                                      sam.bam_header_bytes(sam.SamHead(merged.references, merged.lengths, merged.text, "coordinate")))
-        elif o.source is SAM_SOURCE:
-            opened[i] = o._replace(head=sam.SamHead(merged.references, merged.lengths, o.head.text, o.head.sort_order))
+        if o.source in (SAM_SOURCE, PIPE_SOURCE):               # text: measured and encoded against the merged names
+            opened[i] = o = o._replace(head=sam.SamHead(merged.references, merged.lengths, o.head.text, o.head.sort_order))
+            if o.source is PIPE_SOURCE:                         # a pipe among several: spooled from its first byte, under the merged header
+                opened[i] = _pipe_spooled(dv, o, header)
         elif not np.array_equal(merged.maps[i], np.arange(len(merged.maps[i]))):       # (a dictionary that opens the merged one: nothing to rewrite)
             opened[i] = o._replace(remap=merged.maps[i])
-    header = sam.bam_header_bytes(sam.SamHead(merged.references, merged.lengths, merged.text, "coordinate"))
     rooms = [o.room for o in opened]
     label = "%s (+ %d more)" % (paths[0], len(paths) - 1)
     return Inputs(opened, Opened(label, MergedHead(merged.references, merged.lengths), None, header,
@@ -658,39 +647,22 @@ _COMPRESSED_SAM = ("%s: gzip- or BGZF-compressed data that is no BAM -- compress
                    "`samtools view -b`; through a pipe it is: `pigz -dc x.sam.gz | python -m svision_amd.sort - -o sorted.bam`")
 
 
-def is_stream(path):
-    """Whether an input takes the one-pass road: ``-`` (standard input), or a path that is no regular file (a FIFO, /dev/fd/N) --
-    decided by os.stat, before a byte is read."""
-    if path == "-":
-        return True
-    try:
-        return not stat.S_ISREG(os.stat(path).st_mode)
-    except OSError:
-        return False                                            # (the file road names what is wrong with the path)
-
-
 def _open(bam_path, alone=True, run=None):
     """open: -> Opened(the path, read_bam_header's table, first_record's (file offset, entry, references), the header's bytes as the
     output takes them, ``room``: the records' inflated bytes by the members' ISIZE fields) -- one pass over the file's members.  SAM
-    text (a first byte ``@``, or a first line of 11 tab-separated fields): :func:`_open_sam`."""
+    text (a first byte ``@``, or a first line of 11 tab-separated fields): :func:`_open_sam`; read once: :func:`_open_pipe`."""
     from .io import sam
     from .io.bam import read_bam_header
-    if is_stream(bam_path):
-        return _open_pipe(bam_path, alone, run)
+    if run is None and is_stream(bam_path):
+        raise SortWriteError("%s: not a regular file" % bam_path)
     try:
-        with open(bam_path, "rb") as f:
-            start = f.read(1 << 20)
-    except OSError as exc:
-        raise SortWriteError("%s: %s" % (bam_path, exc)) from None
-    if sam.is_sam_text(start):
-        return _open_sam(bam_path, alone)
-    if start[:2] == b"\x1f\x8b":
-        try:
-            magic = zlib.decompressobj(31).decompress(start, 4)
-        except zlib.error:
-            magic = b"BAM\x01"                                   # (not for this check to report: the BAM road names what is broken)
-        if magic[:4] != b"BAM\x01":
-            raise SortWriteError(_COMPRESSED_SAM % bam_path)
+        inp = textin.open_input(bam_path)
+    except (sam.SamError, OSError) as exc:
+        raise SortWriteError("%s: %s" % (textin.name_of(bam_path), exc)) from None
+    if inp.kind != "bam":
+        return _open_sam(inp, alone) if inp.kind == "sam" else _open_pipe(inp, alone, run)
+    if inp.peek_kind == sam.STREAM_GZIP:
+        raise SortWriteError(_COMPRESSED_SAM % bam_path)
     try:
         head = read_bam_header(bam_path)
         members = index.bgzf_members(bam_path)
@@ -704,20 +676,19 @@ def _open(bam_path, alone=True, run=None):
     return Opened(bam_path, head, tuple(place[:3]), header, room, BAM_SOURCE)
 
 
-def _open_sam(path, alone=True):
-    """open, SAM text: -> Opened(the path, the header's references and lengths (io.sam.SamHead), the file offset of the first alignment
-    line, the output's header bytes, ``room`` None: the records' bytes are known behind the key pass).  One of several inputs
-    (``alone`` unset) may have no @SQ line: the other parts' dictionary serves it."""
+def _open_sam(inp, alone=True, pipe=None):
+    """open, SAM text -- a file's, or (``pipe``) what waits in a pipe behind its ``@`` lines: -> Opened(the input's name, the header's
+    references and lengths (io.sam.SamHead), (the bytes, the lines) in front of the first alignment line, the output's header bytes,
+    ``room`` None: the records' bytes are known behind the key pass).  One of several inputs (``alone`` unset) may have no @SQ line:
+    the other parts' dictionary serves it."""
     from .io import sam
+    bare = not alone and inp.headerless
     try:
-        text = sam.header_end(path)
-        if not alone and not any(l.startswith(b"@SQ\t") for l in text.split(b"\n")):
-            return Opened(path, sam.SamHead([], [], text.decode("latin-1"), None), (len(text), text.count(b"\n")), None, None, SAM_SOURCE)
-        head = sam.parse_header(text)
-        header = sorted_header_bytes(sam.bam_header_bytes(head))
-    except (sam.SamError, OSError) as exc:
-        raise SortWriteError("%s: %s" % (path, exc)) from None
-    return Opened(path, head, (len(text), text.count(b"\n")), header, None, SAM_SOURCE)
+        head = sam.SamHead([], [], inp.text.decode("latin-1"), None) if bare else sam.parse_header(inp.text)
+    except sam.SamError as exc:
+        raise SortWriteError("%s: %s" % (inp.name, exc)) from None
+    return Opened(inp.name, head, inp.first, None if bare else sorted_header_bytes(sam.bam_header_bytes(head)), None,
+                  SAM_SOURCE if pipe is None else PIPE_SOURCE, None, pipe, inp)
 
 
 class KeyPass:
@@ -726,11 +697,12 @@ class KeyPass:
     fields ``tid pos flag span``, the device keys ``d_tid d_pos`` (until the sort has taken them), the records' offsets in the joined
     stream ``off_in`` / ``d_off_in`` [n + 1], and ``d_stream``: the resident record stream, None in a spanned run.  SAM text besides:
     ``host_lens`` per chunk the lines' lengths as svx_sam_encode takes them (negative: the host's line), ``host_records`` {record
-    number: the bytes io.sam encoded}, ``sam_table``: the device's reference names, ``pinned``: the host buffer a chunk is read into."""
+    number: the bytes io.sam encoded}, ``tid_of`` / ``sam_table``: the host's and the device's reference names, ``reader``: the
+    textin.ChunkReader of the text, with the pinned memory a chunk is read into."""
 
     def __init__(self, base=0):
         self.range_records, self.places, self.seen, self.n = [], [], 0, 0
-        self.host_lens, self.host_records, self.sam_table, self.pinned = [], {}, None, None
+        self.host_lens, self.host_records, self.tid_of, self.sam_table, self.reader = [], {}, None, None, None
         self.tid = self.pos = self.flag = self.span = self.d_tid = self.d_pos = self.off_in = self.d_off_in = self.d_stream = None
         # Several inputs: the run's KeyPass holds the joined arrays and, in ``parts``, per input (its Opened, its own KeyPass, the
         # number of its first range and of its first record in the run); an input's own KeyPass has its ranges, what the join takes of
@@ -906,7 +878,7 @@ def _pieces_spanned(dv, opened, kp, od, chunk_blocks, counts):
     (``counts["span_range_reads"]`` of them in all; the source reads them again: :func:`_bam_again`, :func:`_sam_again`) and then
     given chunk by chunk -> as :func:`_pieces_in_core`."""
     torch, lib, kernels, dev, clock = dv
-    rec_base = np.concatenate([[0], np.cumsum(np.asarray(kp.range_records, np.int64))])
+    rec_base = _rec_base(kp)
     for sp in od.plan:
         d_span = torch.empty(sp.size, dtype=torch.uint8, device=dev)
         need = span_ranges(od.rank, kp.range_records, sp.r_lo, sp.r_hi)
@@ -934,6 +906,11 @@ def _pieces_spanned(dv, opened, kp, od, chunk_blocks, counts):
 
 
 # ---- the sources: a BAM's ranges, a SAM's chunks of text ----
+def _rec_base(kp):
+    """The number of the first record of every range of the key pass, and behind the last [ranges + 1]."""
+    return np.concatenate([[0], np.cumsum(np.asarray(kp.range_records, np.int64))])
+
+
 def _bam_again(dv, opened, kp, need):
     """The ranges ``need`` of a BAM read again: read, inflate, CRC, find_starts, the walk's counts and offsets; nothing is extracted.
     An input with a ``remap``: the range's records translated where they lie before they are handed on (:func:`_retid`)."""
@@ -955,7 +932,7 @@ def _bam_fill(dv, opened, kp):
     """in one piece, a BAM beside SAM text (``room`` was not known before the key passes): the ranges that completed a record read a
     second time, each range's records -- contiguous in the range and in the stream -- one copy."""
     need = np.flatnonzero(np.asarray(kp.range_records, np.int64))
-    rec_base = np.concatenate([[0], np.cumsum(np.asarray(kp.range_records, np.int64))])
+    rec_base = _rec_base(kp)
     for k, n_rec, d_raw, d_src_off in _bam_again(dv, opened, kp, need) if need.size else ():
         ends = [int(v) for v in d_src_off[[0, n_rec]].cpu()] if n_rec == kp.range_records[k] else None
         at, end = int(kp.off_in[rec_base[k]]), int(kp.off_in[rec_base[k + 1]])
@@ -967,95 +944,78 @@ def _bam_fill(dv, opened, kp):
         del d_raw, d_src_off
 
 
-def _sam_chunk(dv, opened, kp, place, again=False):
-    """A chunk of the text: read into pinned memory (svx_read_range), uploaded with the kernels' slack behind it, its line table ->
-    (the bytes on the host: a NumPy view that the next chunk overwrites, d_text, d_line_off, the number of lines)."""
-    torch, kernels, dev, clock = dv.torch, dv.kernels, dv.dev, dv.clock
-    n = place[1]
-    if kp.pinned is None or kp.pinned.numel() < n:
-        kp.pinned = torch.empty(n, dtype=torch.uint8, pin_memory=True)
-    if dv.lib.svx_read_range(opened.path.encode(), place[0], n, kp.pinned.data_ptr(), SAM_READ_THREADS) != 0:
-        raise SortWriteError(("%s changed while it was sorted: %s" if again else "%s: %s") % (opened.path, dv.lib.svx_bam_error().decode()))
-    clock.lap("read", False)
-    d_text = torch.empty(n + kernels.SAM_SLACK, dtype=torch.uint8, device=dev)
-    d_text[:n].copy_(kp.pinned[:n], non_blocking=True)
-    d_text[n:] = 0
-    clock.lap("upload")
-    d_line_off, n_lines = kernels.sam_lines(d_text, n)
-    clock.lap("lines")
-    return kp.pinned[:n].numpy(), d_text, d_line_off, n_lines
+Measured = collections.namedtuple("Measured", "first length kernel_len tid pos flag span d_tid d_pos")
 
 
-def _sam_refuse(opened, tid_of, data, line_off, i, line_no, code):
-    """The error of line i of a chunk, worded by the host statement of the rules."""
+def _sam_measured(dv, opened, kp, chunk, d_text, d_line_off, n_lines):
+    """A chunk's lines measured (svx_sam_measure) and read back -> Measured(the number of the chunk's first record, the records' lengths
+    with the host's lines patched in, the lengths as svx_sam_encode takes them, tid, pos, flag, span on the host, the keys on the device).
+    An error code raises with the line's number -- ``chunk.line_no`` lines lie in front of the chunk --; a line the kernels leave to the
+    host is encoded by io.sam.encode_line and kept in ``kp.host_records`` by record number.  A pass's first call sets ``kp``'s names."""
     from .io import sam
-    line = data[int(line_off[i]):int(line_off[i + 1])].tobytes()
-    try:
-        sam.encode_line(line[:-1] if line.endswith(b"\n") else line, tid_of)
-    except sam.SamError as exc:
-        return SortWriteError("%s: %s" % (opened.path, exc.at(line_no)))
-    return SortWriteError("%s: line %d: not an alignment line (svx_sam_measure: %d)" % (opened.path, line_no, code))
-
-
-def _sam_measured(dv, opened, kp, tid_of, data, d_text, d_line_off, n_lines, line_no, seen):
-    """A chunk's lines measured (svx_sam_measure) and read back -> (the records' lengths with the host's lines patched in, the lengths
-    as svx_sam_encode takes them, tid, pos, flag, span on the host, the keys d_tid and d_pos on the device).  An error code raises
-    with the line's number -- ``line_no`` lines lie in front of the chunk --; a line the kernels leave to the host is encoded by
-    io.sam.encode_line and kept in ``kp.host_records`` by record number, ``seen`` records lying in front of the chunk."""
-    from .io import sam
+    if kp.sam_table is None:
+        kp.tid_of, kp.sam_table = sam.tid_table(opened.head.references), dv.kernels.sam_ref_table(opened.head.references, dv.dev)
     torch, kernels, dev, clock = dv.torch, dv.kernels, dv.dev, dv.clock
-    d_len, d_tid, d_pos, d_flag, d_span = kernels.sam_measure(d_text, len(data), d_line_off, n_lines, kp.sam_table)
+    d_len, d_tid, d_pos, d_flag, d_span = kernels.sam_measure(d_text, chunk.n, d_line_off, n_lines, kp.sam_table)
     clock.lap("measure")
     length, tid, pos, flag, span = (t.cpu().numpy() for t in (d_len, d_tid, d_pos, d_flag, d_span))
     line_off = d_line_off[:n_lines + 1].cpu().numpy()
     clock.lap("read_back")
     bad = np.flatnonzero(length < kernels.SAM_HOST)
     if bad.size:
-        raise _sam_refuse(opened, tid_of, data, line_off, int(bad[0]), line_no + int(bad[0]) + 1, int(length[bad[0]]))
-    kernel_len = length.copy()
+        i = int(bad[0])
+        raise SortWriteError("%s: %s" % (opened.path, textin.line_refusal(textin.line_bytes(chunk.data, line_off, i), kp.tid_of, chunk.line_no + i + 1,
+                                                                      "svx_sam_measure", int(length[i]))))
+    kernel_len, first = length.copy(), sum(kp.range_records)
     left = np.flatnonzero(length == kernels.SAM_HOST)
     for i in left:
-        line = data[int(line_off[i]):int(line_off[i + 1])].tobytes()
-        line = line[:-1] if line.endswith(b"\n") else line
+        line = textin.line_bytes(chunk.data, line_off, i)
         try:
-            rec = sam.encode_line(line, tid_of)
-            tid[i], pos[i], flag[i], span[i] = sam.fields_of(line, tid_of)
+            rec = sam.encode_line(line, kp.tid_of)
+            tid[i], pos[i], flag[i], span[i] = sam.fields_of(line, kp.tid_of)
         except sam.SamError as exc:
-            raise SortWriteError("%s: %s" % (opened.path, exc.at(line_no + int(i) + 1))) from None
+            raise SortWriteError("%s: %s" % (opened.path, exc.at(chunk.line_no + int(i) + 1))) from None
         length[i] = len(rec)
-        kp.host_records[seen + int(i)] = rec
+        kp.host_records[first + int(i)] = rec
     if left.size:
         d_tid, d_pos = torch.from_numpy(tid).to(dev), torch.from_numpy(pos).to(dev)
     clock.lap("host_lines", False)
-    return length, kernel_len, tid, pos, flag, span, d_tid, d_pos
+    return Measured(first, length.astype(np.int64), kernel_len, tid, pos, flag.astype(np.uint16), span, d_tid, d_pos)
+
+
+def _keep_measured(kp, place, m, keys=True):
+    """A measured chunk into the input's KeyPass; ``keys`` unset (its records go to a spool): without what the join takes of it."""
+    kp.range_records.append(m.length.size)
+    kp.places.append(place)
+    kp.host_lens.append(m.kernel_len)
+    if keys and m.length.size:
+        kp.host.append((m.tid, m.pos, m.flag, m.span))
+        kp.lens.append(m.length)
+        kp.d_keys.append((m.d_tid, m.d_pos))
+    kp.seen += int(m.length.sum())
+
+
+def _place_host_records(torch, take, kernel_len, first, off, d_out):
+    """A chunk's records that the host encoded (``kernel_len`` < 0), ``take(first + i)`` each, copied to ``off[i]`` in ``d_out`` -> how many."""
+    left = np.flatnonzero(kernel_len < 0)
+    for i in left:
+        rec = take(first + int(i))
+        d_out[int(off[i]):int(off[i]) + len(rec)].copy_(torch.frombuffer(bytearray(rec), dtype=torch.uint8))
+    return left.size
 
 
 def _sam_key_pass(dv, opened, range_bytes, kp, d_stream=None):
-    """key pass of SAM text: one pass over the chunks (io.sam.chunk_places: ``range_bytes`` of text, cut at line ends): svx_sam_lines,
+    """key pass of SAM text: one pass over the chunks (textin.ChunkReader.chunks: ``range_bytes`` of text, cut at line ends): svx_sam_lines,
     svx_sam_measure, the lengths and fields read back.  An error code raises with the file's line number; a line the kernels leave to the
     host (SVX_SAM_HOST) is encoded by io.sam at once -- its bytes kept in ``kp.host_records`` by record number, its length, key and
     fields patched in.  No byte is kept: ``room`` is exact behind the pass, and a run in one piece then reads the text once more
     (:func:`_sam_fill`)."""
-    from .io import sam
-    torch, kernels, dev, clock = dv.torch, dv.kernels, dv.dev, dv.clock
-    tid_of, kp.sam_table = sam.tid_table(opened.head.references), kernels.sam_ref_table(opened.head.references, dev)
-    host, d_keys, lens = kp.host, kp.d_keys, kp.lens
-    line_no, seen = opened.first[1], 0
-    for place in sam.chunk_places(opened.path, opened.first[0], range_bytes or DEFAULT_SAM_CHUNK_BYTES):
-        data, d_text, d_line_off, n_lines = _sam_chunk(dv, opened, kp, place)
-        length, kernel_len, tid, pos, flag, span, d_tid, d_pos = _sam_measured(dv, opened, kp, tid_of, data, d_text, d_line_off, n_lines, line_no, seen)
-        kp.range_records.append(n_lines)
-        kp.places.append(place)
-        kp.host_lens.append(kernel_len)
-        if n_lines:
-            host.append((tid, pos, flag.astype(np.uint16), span))
-            lens.append(length.astype(np.int64))
-            d_keys.append((d_tid, d_pos))
-        kp.seen += int(length.sum())
-        seen += n_lines
-        line_no += n_lines
+    kp.reader = textin.ChunkReader(dv.torch, dv.lib, dv.clock)
+    for chunk in kp.reader.chunks(opened.text, range_bytes):
+        d_text, d_line_off, n_lines = textin.upload_lines(dv.torch, dv.kernels, dv.dev, dv.clock, chunk)
+        _keep_measured(kp, chunk.place, _sam_measured(dv, opened, kp, chunk, d_text, d_line_off, n_lines))
         del d_text, d_line_off
-        clock.lap("keep")
+        dv.clock.lap("keep")
 
 
 def _sam_encode_chunk(dv, opened, kp, k, first, base, d_out, d_status):
@@ -1063,36 +1023,30 @@ def _sam_encode_chunk(dv, opened, kp, k, first, base, d_out, d_status):
     at byte off_in[r] - base; the host's encodings copied to their offsets.  ``first``: the number of the chunk's first record.
     -> the lines the chunk has now (another number than in the key pass: nothing is written)."""
     torch, kernels = dv.torch, dv.kernels
-    data, d_text, d_line_off, n_lines = _sam_chunk(dv, opened, kp, kp.places[k], again=True)
+    try:
+        chunk = kp.reader.at(opened.text, kp.places[k])
+    except textin.ReadError as exc:
+        raise SortWriteError("%s changed while it was sorted: %s" % (exc.path, exc.what)) from None
+    d_text, d_line_off, n_lines = textin.upload_lines(torch, kernels, dv.dev, dv.clock, chunk)
     if n_lines != kp.range_records[k]:
         return n_lines
     d_len = torch.from_numpy(kp.host_lens[k]).to(dv.dev)
-    kernels.sam_encode(d_text, len(data), d_line_off, n_lines, kp.sam_table, d_len, kp.d_off_in[first:first + n_lines], base, d_out, d_status)
+    kernels.sam_encode(d_text, chunk.n, d_line_off, n_lines, kp.sam_table, d_len, kp.d_off_in[first:first + n_lines], base, d_out, d_status)
     dv.clock.lap("encode")
-    for i in np.flatnonzero(kp.host_lens[k] < 0):
-        rec = kp.host_records[first + int(i)]
-        at = int(kp.off_in[first + int(i)]) - base
-        d_out[at:at + len(rec)].copy_(torch.frombuffer(bytearray(rec), dtype=torch.uint8))
+    _place_host_records(torch, kp.host_records.__getitem__, kp.host_lens[k], first, kp.off_in[first:first + n_lines] - base, d_out)
     dv.clock.lap("host_lines")
     return n_lines
-
-
-def _sam_changed(opened, kp, k, n_lines):
-    return SortWriteError("%s changed while it was sorted: %d lines complete in the chunk at file offset %d, %d did in the first pass"
-                          % (opened.path, n_lines, kp.places[k][0], kp.range_records[k]))
 
 
 def _sam_fill(dv, opened, kp):
     """in one piece, SAM text: the second read of the text -- in the page cache for a file that fits the device --, every chunk encoded
     straight into the resident stream (``kp.d_stream``) at its records' offsets."""
-    torch, dev = dv.torch, dv.dev
-    d_status = torch.zeros(1, dtype=torch.int32, device=dev)
-    first = 0
-    for k, n_rec in enumerate(kp.range_records):
-        n_lines = _sam_encode_chunk(dv, opened, kp, k, first, 0, kp.d_stream, d_status)
-        if n_lines != n_rec:
-            raise _sam_changed(opened, kp, k, n_lines)
-        first += n_rec
+    d_status = dv.torch.zeros(1, dtype=dv.torch.int32, device=dv.dev)
+    for k, first in enumerate(_rec_base(kp)[:-1]):
+        n_lines = _sam_encode_chunk(dv, opened, kp, k, int(first), 0, kp.d_stream, d_status)
+        if n_lines != kp.range_records[k]:
+            raise SortWriteError("%s changed while it was sorted: %d lines complete in the chunk at file offset %d, %d did in the first pass"
+                                 % (opened.path, n_lines, kp.places[k][0], kp.range_records[k]))
     if int(d_status.item()):
         raise SortWriteError("%s changed while it was sorted: a line's record is not of the length the first pass saw" % opened.path)
 
@@ -1101,7 +1055,7 @@ def _sam_again(dv, opened, kp, need):
     """The chunks ``need`` of SAM text read again for a span: each encoded into a chunk-local buffer (+ the 4 readable bytes the
     scatter's aligned loads want) whose record offsets are the key pass's."""
     torch, dev = dv.torch, dv.dev
-    rec_base = np.concatenate([[0], np.cumsum(np.asarray(kp.range_records, np.int64))])
+    rec_base = _rec_base(kp)
     for k in need:
         first, n_rec = int(rec_base[k]), int(kp.range_records[k])
         base = int(kp.off_in[first])
@@ -1117,25 +1071,15 @@ def _sam_again(dv, opened, kp, need):
 
 # ---- a pipe: SAM text that is seen once ----
 class _Pipe:
-    """An input that is read once -- standard input, a FIFO, /dev/fd/N: its name in messages (``<stdin>`` for ``-``), the
-    io.sam.StreamReader over its descriptor, ``mode`` ("in_core", "spooled", "bam_spooled"), the ledger of its record buffers on the
-    device, its segments (a chunk's records each) while it is kept in core, its :class:`Spool` beyond the budget, and what the
-    statistics report.  :meth:`close` ends the reader and closes the descriptor; ``failed``: standard input's descriptor is
-    pointed at the null device, so that the writer of the pipe ends with EPIPE and does not block; :meth:`discard` removes the spool."""
+    """An input that is read once -- standard input, a FIFO, /dev/fd/N -- as the sort keeps it: the textin.TextInput that owns its
+    reader, its name in messages (``<stdin>`` for ``-``), ``mode`` ("in_core", "spooled", "bam_spooled"), the ledger of its record
+    buffers on the device, its segments (a chunk's records each) while it is kept in core, its :class:`Spool` beyond the budget, and
+    what the statistics report.  :meth:`discard` removes the spool; closing is the input's (textin.TextInput.close)."""
 
-    def __init__(self, path, run):
-        from .io import sam
-        self.name, self.run, self.stdin, self.number = sam.STREAM_NAME if path == "-" else path, run, path == "-", len(run.pipes)
+    def __init__(self, inp, run):
+        self.input, self.name, self.run, self.number = inp, inp.name, run, len(run.pipes)
         self.mode, self.ledger, self.segments, self.spool, self.spool_file = "in_core", StreamLedger(), [], None, None
-        self.spool_bytes = self.host_lines = self.records = 0
-        self.reader = sam.StreamReader(0 if self.stdin else os.open(path, os.O_RDONLY), own=not self.stdin)
-
-    def close(self, failed=False):
-        self.reader.close()
-        if failed and self.stdin:
-            null = os.open(os.devnull, os.O_RDONLY)
-            os.dup2(null, 0)
-            os.close(null)
+        self.spool_bytes = self.host_lines = 0
 
     def discard(self):
         self.segments = []
@@ -1144,44 +1088,29 @@ class _Pipe:
         index.discard(self.spool_file)
 
     def stats(self):
-        return dict(mode=self.mode, grows=self.ledger.grows, spool_bytes=self.spool_bytes, text_bytes=self.reader.text_bytes,
-                    reader_wait_pipe_s=round(self.reader.wait_pipe, 6), reader_wait_buffer_s=round(self.reader.wait_buffer, 6))
+        reader = self.input.reader
+        return dict(mode=self.mode, grows=self.ledger.grows, spool_bytes=self.spool_bytes, text_bytes=reader.text_bytes,
+                    reader_wait_pipe_s=round(reader.wait_pipe, 6), reader_wait_buffer_s=round(reader.wait_buffer, 6))
 
 
-def _open_pipe(path, alone, run):
-    """open, an input that is read once: its first bytes say what it holds (io.sam.stream_kind).  SAM text: the ``@`` lines are read
-    -> an Opened as :func:`_open_sam` gives, its source PIPE_SOURCE; the text behind them waits in the pipe.  A BAM: its bytes are
-    copied as they are into the spool file, and that file is opened as any BAM.  Compressed SAM, no byte, anything else: refused."""
+def _open_pipe(inp, alone, run):
+    """open, an input that is read once, by what its first bytes hold.  SAM text: :func:`_open_sam`'s Opened, its source PIPE_SOURCE,
+    the text waiting in the pipe.  A BAM: copied as it is into the spool file, which is opened as any BAM.  Anything else: refused."""
     from .io import sam
-    if run is None:
-        raise SortWriteError("%s: not a regular file" % path)
-    try:
-        pipe = _Pipe(path, run)
-    except OSError as exc:
-        raise SortWriteError("%s: %s" % (path, exc)) from None
+    pipe = _Pipe(inp, run)
     run.pipes.append(pipe)
-    name = pipe.name
+    refusal = {sam.STREAM_EMPTY: "%s: no input", sam.STREAM_GZIP: _COMPRESSED_SAM, sam.STREAM_OTHER: "%s: neither SAM text nor a BAM"}
+    if inp.peek_kind in refusal:
+        raise SortWriteError(refusal[inp.peek_kind] % inp.name)
+    if inp.peek_kind == sam.STREAM_SAM:
+        return _open_sam(inp, alone, pipe)
+    pipe.mode = "bam_spooled"
     try:
-        kind = sam.stream_kind(pipe.reader.peek())
-        if kind == sam.STREAM_EMPTY:
-            raise SortWriteError("%s: no input" % name)
-        if kind == sam.STREAM_GZIP:
-            raise SortWriteError(_COMPRESSED_SAM % name)
-        if kind == sam.STREAM_OTHER:
-            raise SortWriteError("%s: neither SAM text nor a BAM" % name)
-        if kind == sam.STREAM_BAM:
-            pipe.mode = "bam_spooled"
-            pipe.spool_file, pipe.spool_bytes = spool_copy(pipe.reader, run.out_path, run.clock, pipe.number)
-            pipe.close()
-            return _open(pipe.spool_file, alone)._replace(pipe=pipe)
-        text = pipe.reader.header()
-        first = (len(text), text.count(b"\n"))
-        if not alone and not any(l.startswith(b"@SQ\t") for l in text.split(b"\n")):
-            return Opened(name, sam.SamHead([], [], text.decode("latin-1"), None), first, None, None, PIPE_SOURCE, None, pipe)
-        head = sam.parse_header(text)
-        return Opened(name, head, first, sorted_header_bytes(sam.bam_header_bytes(head)), None, PIPE_SOURCE, None, pipe)
-    except (sam.SamError, OSError) as exc:
-        raise SortWriteError("%s: %s" % (name, exc)) from None
+        pipe.spool_file, pipe.spool_bytes = spool_copy(inp.reader, run.out_path, run.clock, pipe.number)
+    except OSError as exc:
+        raise SortWriteError("%s: %s" % (inp.name, exc)) from None
+    inp.close()
+    return _open(pipe.spool_file, alone)._replace(pipe=pipe)
 
 
 def _pipe_join(dv, pipe, d_out, at=0):
@@ -1216,75 +1145,45 @@ def _pipe_to_spool(dv, opened, kp, header):
 
 
 def _pipe_key_pass(dv, opened, range_bytes, kp, d_stream=None, spool_header=None):
-    """key pass of a pipe, the ONLY pass over its text: per chunk of io.sam.StreamReader.chunks -- read on a thread of its own into
-    pinned buffers while the device works on the chunk before -- upload, svx_sam_lines, svx_sam_measure, the read-back and the host's
-    lines as :func:`_sam_key_pass` has them, and AT ONCE svx_sam_encode: the chunk's records into a segment of exactly their bytes,
-    their offsets the exclusive sum of the lengths behind the bytes kept so far; the host's encodings copied to theirs.  Keys, fields,
-    lengths, ``range_records`` and ``host_lens`` are kept as for a SAM file.  The segments are joined by :func:`_pipe_fill`.
+    """key pass of a pipe, the ONLY pass over its text: per chunk -- read by the reader's thread while the device works on the chunk
+    before -- upload, svx_sam_lines, svx_sam_measure, the read-back and the host's lines as :func:`_sam_key_pass` has them, and AT ONCE
+    svx_sam_encode: the chunk's records into a segment of exactly their bytes, their offsets the exclusive sum of the lengths behind
+    the bytes kept so far; the host's encodings copied to theirs.  What is kept is a SAM file's; :func:`_pipe_fill` joins the segments.
     A chunk that :func:`keeps_in_core` refuses (``spool_header`` given: the first) opens the spool: from then on every chunk's
     records are appended to it in arrival order and nothing is kept; ``opened.pipe.mode`` says so to the caller."""
     from .io import sam
     torch, kernels, dev, clock, pipe = dv.torch, dv.kernels, dv.dev, dv.clock, opened.pipe
-    tid_of, kp.sam_table = sam.tid_table(opened.head.references), kernels.sam_ref_table(opened.head.references, dev)
-    pinned = {}
-
-    def alloc(n):                                               # a pinned buffer as the reader takes it: its NumPy view
-        t = torch.empty(n, dtype=torch.uint8, pin_memory=True)
-        a = t.numpy()
-        pinned[a.ctypes.data] = t
-        return a
+    kp.reader = textin.ChunkReader(torch, dv.lib, clock)
     if spool_header is not None:
         _pipe_to_spool(dv, opened, kp, spool_header)
-    seen, at = 0, opened.first[0]
     d_status = torch.zeros(1, dtype=torch.int32, device=dev)
-    for buf, n, line_no in pipe.reader.chunks(range_bytes or DEFAULT_SAM_CHUNK_BYTES, opened.first[1], alloc):
-        clock.lap("read", False)
-        data = buf[:n]
-        d_text = torch.empty(n + kernels.SAM_SLACK, dtype=torch.uint8, device=dev)
-        d_text[:n].copy_(pinned[buf.ctypes.data][:n], non_blocking=True)
-        d_text[n:] = 0
-        clock.lap("upload")
-        d_line_off, n_lines = kernels.sam_lines(d_text, n)
-        clock.lap("lines")
-        length, kernel_len, tid, pos, flag, span, d_tid, d_pos = _sam_measured(dv, opened, kp, tid_of, data, d_text, d_line_off, n_lines, line_no, seen)
-        length = length.astype(np.int64)
-        need = int(length.sum())
+    for chunk in kp.reader.chunks(opened.text, range_bytes):
+        d_text, d_line_off, n_lines = textin.upload_lines(torch, kernels, dev, clock, chunk)
+        m = _sam_measured(dv, opened, kp, chunk, d_text, d_line_off, n_lines)
+        need = int(m.length.sum())
         if pipe.spool is None and need and not keeps_in_core(kp.seen, need, pipe.run.budget):
             _pipe_to_spool(dv, opened, kp, sam.bam_header_bytes(opened.head))
         # ---- the chunk's records: a segment of their bytes (kept), or a buffer with the encoder's slack (spooled at once)
-        off = np.cumsum(length) - length + kp.seen
+        off = np.cumsum(m.length) - m.length
         d_seg = torch.empty(need + (STREAM_SLACK if pipe.spool is not None else 0), dtype=torch.uint8, device=dev)
         d_seg[need:] = 0
         if n_lines:
-            kernels.sam_encode(d_text, n, d_line_off, n_lines, kp.sam_table, torch.from_numpy(kernel_len).to(dev), torch.from_numpy(off).to(dev),
-                               kp.seen, d_seg, d_status)
+            kernels.sam_encode(d_text, chunk.n, d_line_off, n_lines, kp.sam_table, torch.from_numpy(m.kernel_len).to(dev),
+                               torch.from_numpy(off + kp.seen).to(dev), kp.seen, d_seg, d_status)
         clock.lap("encode")
-        for i in np.flatnonzero(kernel_len < 0):
-            rec = kp.host_records.pop(seen + int(i))
-            d_seg[int(off[i]) - kp.seen:int(off[i]) - kp.seen + len(rec)].copy_(torch.frombuffer(bytearray(rec), dtype=torch.uint8))
-            pipe.host_lines += 1
+        pipe.host_lines += _place_host_records(torch, kp.host_records.pop, m.kernel_len, m.first, off, d_seg)
         clock.lap("host_lines")
         if int(d_status.item()):
             raise SortWriteError("%s: a line's record is not of the length svx_sam_measure gave it" % opened.path)
         if pipe.spool is not None:
             pipe.spool.put(d_seg, need, pipe.run.chunk_blocks * BLOCK)
-        else:
-            if need:
-                pipe.segments.append(d_seg)
-                pipe.ledger.add(need)
-            if n_lines:
-                kp.host.append((tid, pos, flag.astype(np.uint16), span))
-                kp.lens.append(length)
-                kp.d_keys.append((d_tid, d_pos))
-        kp.range_records.append(n_lines)
-        kp.places.append((at, n))
-        kp.host_lens.append(kernel_len)
-        kp.seen += need
-        pipe.records += n_lines
-        seen, at = seen + n_lines, at + n
+        elif need:
+            pipe.segments.append(d_seg)
+            pipe.ledger.add(need)
+        _keep_measured(kp, chunk.place, m, keys=pipe.spool is None)
         del d_text, d_line_off, d_seg
         clock.lap("keep")
-    pipe.close()
+    opened.text.close()
     if pipe.spool is not None:
         pipe.spool_file = pipe.spool.finish()
         pipe.spool_bytes = pipe.spool.bytes
@@ -1292,9 +1191,8 @@ def _pipe_key_pass(dv, opened, range_bytes, kp, d_stream=None, spool_header=None
 
 def _pipe_fill(dv, opened, kp):
     """in one piece, a pipe: its segments joined into the resident stream (``kp.d_stream``) -- both copies exist while they are."""
-    pipe = opened.pipe
-    pipe.ledger.add(kp.d_stream.numel())
-    _pipe_join(dv, pipe, kp.d_stream, int(kp.off_in[0]) if kp.n else kp.base)
+    opened.pipe.ledger.add(kp.d_stream.numel())
+    _pipe_join(dv, opened.pipe, kp.d_stream, int(kp.off_in[0]) if kp.n else kp.base)
 
 
 def _pipe_again(dv, opened, kp, need):
@@ -1350,7 +1248,7 @@ def sort_bam(bam_path, out_path, device="cuda", range_bytes=None, chunk_bytes=No
     is read once (see "A pipe" at the head of the module): stats also has ``pipe`` -- mode, grows, spool_bytes, text_bytes and the
     reader thread's waits; ``pipes``: the same of every such input in list order, with its name --, input="sam" as for a SAM file, and
     stream_bytes is the largest total of the pipe's record buffers.  A side effect on the calling PROCESS: when the call fails while
-    ``-`` is among the inputs, descriptor 0 is pointed at the null device (``os.dup2``) before the error is raised -- that closes the
+    ``-`` is among the inputs, descriptor 0 is pointed at the null device (textin.TextInput.close) before the error is raised -- that closes the
     pipe's read end, so that its writer ends with EPIPE and does not block; a caller that needs standard input afterwards hands the
     stream in as a path (/dev/fd/N of a duplicate) instead, whose descriptor is the call's own."""
     from . import ingest_sort, kernels
@@ -1364,8 +1262,7 @@ def sort_bam(bam_path, out_path, device="cuda", range_bytes=None, chunk_bytes=No
     chunk_blocks = max(int(chunk_bytes or DEFAULT_CHUNK_BYTES) // BLOCK, 1)
     budget = None if memory_bytes is None else max(int(memory_bytes), 1)
     ins, opened, kp, writer, counts, pipes, done = None, None, KeyPass(), None, {"span_range_reads": 0}, [], False
-    from .io.sam import STREAM_NAME
-    first_name = STREAM_NAME if paths[0] == "-" else paths[0]
+    first_name = textin.name_of(paths[0])
     bam_path = first_name if len(paths) == 1 else "%s (+ %d more)" % (first_name, len(paths) - 1)       # (the inputs' name in a message)
     try:
         with torch.cuda.device(dev):
@@ -1394,11 +1291,13 @@ def sort_bam(bam_path, out_path, device="cuda", range_bytes=None, chunk_bytes=No
                                              str(exc).split("\n")[0])) from None
     except _lib.SvxError as exc:
         raise SortWriteError("%s: %s" % (kp.reading or bam_path, exc)) from None
+    except textin.ReadError as exc:
+        raise SortWriteError(str(exc)) from None
     except OSError as exc:
         raise SortWriteError("%s: writing %s failed (%s)" % (bam_path, out_path, exc)) from None
     finally:
         for pipe in pipes:                                      # the read end first: the pipe's writer must not block on it
-            pipe.close(failed=not done)
+            pipe.input.close(failed=not done)
         if writer is not None:
             writer.discard()
         for pipe in pipes:
@@ -1463,7 +1362,7 @@ def main(argv=None):
              stats["inflated_bytes"], stats["compressed_bytes"], stats["ranges"], stats["chunks"], sum(stats["seconds"].values())))
     if "pipe" in stats:
         pipe = stats["pipe"]
-        name = next(("<stdin>" if b == "-" else b for b in args.bam if is_stream(b)), "<stdin>")
+        name = next((textin.name_of(b) for b in args.bam if is_stream(b)), "<stdin>")
         print("%s: %s (%d bytes) %s" % (path, name, pipe["text_bytes"],
                                         "kept in core: its records grew %d time(s) on the device" % pipe["grows"] if pipe["mode"] == "in_core" else
                                         "spooled: %d bytes of unsorted BAM beside the output, sorted from there%s"
