@@ -33,7 +33,8 @@ def parse_arguments(arguments=None):
     g = p.add_argument_group("Input/Output parameters")
     g.add_argument("-o", dest="out_path", type=os.path.abspath, required=True, help="Absolute path to output")
     g.add_argument("-b", dest="bam_path", type=_bam_arg, required=True, help="Absolute path to bam file; SVX_DEVICE_SORT=write or =1: ``-`` is "
-                   "an aligner's output on standard input")
+                   "an aligner's output on standard input -- SAM text; a BAM there (dorado aligner, pbmm2) is copied into a file first under "
+                   "=write and refused under =1, unless SVX_PIPE_BAM=stream takes it in one pass")
     g.add_argument("-m", dest="model_path", type=os.path.abspath, required=True, help="Absolute path to CNN predict model")
     g.add_argument("-g", dest="genome", type=os.path.abspath, required=True, help="Absolute path to your reference genome")
     g.add_argument("-n", dest="sample", type=str, required=True, help="Name of the BAM sample name")
@@ -202,7 +203,7 @@ def load_rank_table(options, rank, ws):
 def _load_unsorted(options, several=None):
     """SVX_DEVICE_SORT=1 and a header that does not say ``SO:coordinate``, an aligner's SAM text, ``-b -`` or a list of inputs
     (``several``): everything taken apart and the records sorted on the device (svision_amd/ingest_sort.py) -> the resident Sample the
-    run goes on with.  No alignment file is written."""
+    run goes on with.  No alignment file is written.  load_sample reads ``SVX_PIPE_BAM`` itself: "stream" takes a BAM on a pipe."""
     import time
     import torch
     from .ingest_sort import SortIngestError, load_sample
@@ -218,8 +219,8 @@ def _load_unsorted(options, several=None):
         raise SystemExit(1)
     kinds = stats.get("inputs", ["bam"])
     logging.info("%s is %s: %d records sorted on the device in %.2f s (%d range(s), %d radix passes)", options.bam_path,
-                 "%d inputs" % len(kinds) if len(kinds) > 1 else "not coordinate sorted" if kinds[0] == "bam" else "SAM text", stats["records"],
-                 time.perf_counter() - t0, stats["ranges"], stats["passes"])
+                 "%d inputs" % len(kinds) if len(kinds) > 1 else "not coordinate sorted" if kinds[0] == "bam" else "a BAM on a pipe" if kinds[0] == "bam_pipe" else "SAM text",
+                 stats["records"], time.perf_counter() - t0, stats["ranges"], stats["passes"])
     return sample
 
 

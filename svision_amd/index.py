@@ -204,14 +204,19 @@ class RecordRange:
 
 
 def _inflate_range(lib, torch, kernels, dev, pinned, blocks, entry, d_ref_len, n_ref, clock):
-    """A range's blocks inflated and checked, the record starts found -> RecordRange with d_raw, dst, total, exit_off and starts."""
+    """A range's blocks inflated and checked, the record starts found -> RecordRange with d_raw, dst, total, exit_off and starts.
+    ``pinned``: the range's compressed bytes, or a list of host tensors that hold them end to end (:func:`stream_ranges`: the carried
+    blocks, then the chunk)."""
     n, used = blocks.k, blocks.used
     st = kernels._stream_ptr(dev)
     dst = np.zeros(n + 1, np.uint64)
     dst[1:] = np.cumsum(blocks.isize.astype(np.uint64))
     total = int(dst[n])
     d_comp = torch.empty((used + 31) // 16 * 16, dtype=torch.uint8, device=dev)
-    d_comp[:used].copy_(pinned[:used], non_blocking=True)
+    at = 0
+    for piece in pinned if isinstance(pinned, (list, tuple)) else [pinned[:used]]:
+        d_comp[at:at + piece.numel()].copy_(piece, non_blocking=True)
+        at += piece.numel()
     d_src = torch.from_numpy(_as_i64(blocks.src_off)).to(dev)
     d_len = torch.from_numpy(np.ascontiguousarray(blocks.src_len, np.uint32).view(np.int32)).to(dev)
     d_dst = torch.from_numpy(dst.view(np.int64)).to(dev)
@@ -382,6 +387,127 @@ def record_ranges(bam_path, head, dev, clock, range_bytes=None, with_seq=False, 
         else:                                                   # the block the cut record starts in opens the next range
             b = int(np.searchsorted(rng.dst[:blocks.k], np.uint64(exit_off), "right")) - 1
             file_at, entry = int(blocks.coff[b]), exit_off - int(rng.dst[b])
+
+
+def range_work(head, n_ref, dev, clock, with_seq=False, extract=True):
+    """The device work of one range of :func:`stream_ranges` -> ``work(pieces, blocks, entry)``: the compressed bytes -- host uint8
+    arrays that lie end to end --, their block table and the chain's entry offset through :func:`_inflate_range` and
+    :func:`_walk_range` -> the RecordRange: ``exit_off``, ``total``, ``dst`` and the records that complete."""
+    import torch
+    from . import kernels
+    lib = _lib.load()
+    d_ref_len = torch.from_numpy(np.asarray(list(head.lengths) + [0], np.int32)).to(dev)
+
+    def work(pieces, blocks, entry):
+        rng = _inflate_range(lib, torch, kernels, dev, [torch.from_numpy(p) for p in pieces], blocks, entry, d_ref_len, n_ref, clock)
+        if rng.exit_off != entry:                               # (no record completes: nothing to walk, as in record_ranges)
+            _walk_range(lib, torch, kernels, dev, rng, with_seq, clock, extract)
+        return rng
+    return work
+
+
+def _carried(pieces, blocks, range_at, b):
+    """The compressed blocks of a range from block ``b`` on, copied out of ``pieces`` -> (their bytes as one array of its own, their
+    block table with the payloads' offsets counted from that array's first byte)."""
+    cut = int(blocks.coff[b]) - range_at
+    out, at = np.empty(blocks.used - cut, np.uint8), 0
+    for piece in pieces:
+        skip = min(cut, piece.size)
+        out[at:at + piece.size - skip] = piece[skip:]
+        at, cut = at + piece.size - skip, cut - skip
+    return out, type(blocks)(blocks.k - b, blocks.src_off[b:] - np.uint64(blocks.used - out.size), blocks.src_len[b:], blocks.isize[b:],
+                             blocks.coff[b:], out.size)
+
+
+def stream_ranges(chunks, head, first, dev=None, clock=None, with_seq=False, extract=True, work=None, name="the stream", stats=None):
+    """:func:`record_ranges` for a BAM that is seen ONCE.  ``chunks``: the stream from the member its first record starts in on, as
+    (buffer, n_bytes, stream offset) of whole BGZF members each -- io.sam.StreamReader.member_chunks; a buffer is this generator's
+    until it asks for the next chunk.  ``first``: (that member's stream offset, the record's offset in its inflated bytes, the number
+    of references), with ``head`` what StreamReader.bam_header gave.  -> one :class:`RecordRange` a range, whose records are those that
+    complete in it, in stream order; ``at_end`` is set on the last one -- a range is therefore handed on when the chunk behind it
+    has arrived, or the stream's end --; ``place``: (the stream offset of the range's first byte, its compressed bytes, the entry
+    offset), for messages: no place of a stream can be read again.
+
+    What a file's pass does by seeking is done by carrying.  A record the range's end cuts (``exit_off < total``): the compressed
+    blocks from the one it starts in on are copied out of the chunk's buffer before the next chunk is asked for; they open the next
+    range, ``entry`` the record's offset in the first of them -- at most one record's blocks are inflated twice.  A range in which no
+    record completes is that case with every block carried: the next chunk extends it, nothing is read twice and nothing is lost --
+    but every carried block is inflated again with each chunk that extends the range: growth by a chunk where the file road doubles.
+    At the default chunk a record is far smaller than a chunk and this never repeats; at a small ``range_bytes`` under long reads the
+    inflate work is quadratic in the record's blocks, and "inflated twice" above does not hold.
+    The host holds one chunk and one carried record's blocks (``stats``: ``held_peak``, the largest sum of the two; ``carry_peak``;
+    ``grown``: the ranges that completed no record; ``ranges``), besides the reader's buffers.
+
+    ``work(pieces, blocks, entry)``: the per-range device work (default :func:`range_work` over ``dev`` and ``clock``: inflate, CRC,
+    find-starts, the walk) -- handed in, the carrying runs without a device (tests/test_pipe_bam_cpu.py).  Raises IndexBuildError as
+    :func:`record_ranges` does for the same bytes as a file, its words with the stream offset where those have the file offset."""
+    from . import ingest_gpu
+    from .io import sam
+    lib = _lib.load()
+    expect, entry, n_ref = first
+    if n_ref != len(head.references):
+        raise IndexBuildError("%s: the header names %d references, its dictionary %d" % (name, len(head.references), n_ref))
+    if work is None:
+        work = range_work(head, n_ref, dev, clock, with_seq, extract)
+    lap = (lambda: None) if clock is None else (lambda: clock.lap("read", False))
+    carry = carry_blocks = pending = None
+    counts = dict(held_peak=0, carry_peak=0, grown=0, ranges=0)
+    chunks = iter(chunks)
+    try:
+        lap()
+        for buf, n, at in chunks:
+            if pending is not None:
+                yield pending
+                pending = None
+            before = None if clock is None else dict(clock.times)
+            if at != expect:
+                raise IndexBuildError("%s: a chunk at stream offset %d where the one at %d was due" % (name, at, expect))
+            expect = at + n
+            data = np.frombuffer(buf, np.uint8)[:n]
+            blocks = ingest_gpu._index_blocks(lib, data.ctypes.data, n, at)
+            if blocks.k <= 0 or blocks.used != n:
+                raise IndexBuildError("%s: no whole BGZF block at stream offset %d" % (name, at + max(blocks.used, 0)))
+            lap()
+            pieces = [data]
+            if carry is not None:                               # the carried blocks open the range: the chunk's payloads lie behind them
+                pieces = [carry, data]
+                blocks = type(blocks)(carry_blocks.k + blocks.k, *(np.concatenate([a, b]) for a, b in
+                                      ((carry_blocks.src_off, blocks.src_off + np.uint64(carry.size)), (carry_blocks.src_len, blocks.src_len),
+                                       (carry_blocks.isize, blocks.isize), (carry_blocks.coff, blocks.coff))), carry.size + n)
+            range_at = int(blocks.coff[0])
+            counts["held_peak"], counts["ranges"] = max(counts["held_peak"], blocks.used), counts["ranges"] + 1
+            rng = work(pieces, blocks, entry)
+            exit_off, total = int(rng.exit_off), int(rng.total)
+            grown = exit_off == entry and exit_off < total      # no record completes: the range goes on with the next chunk
+            if not grown:
+                rng.before, rng.at_end, rng.place = before, False, (range_at, blocks.used, entry)
+                pending = rng
+            counts["grown"] += grown
+            carry = carry_blocks = None
+            entry = 0
+            if exit_off < total:                                # the block the cut record starts in, and all behind it, are kept
+                b = int(np.searchsorted(rng.dst[:blocks.k], np.uint64(exit_off), "right")) - 1
+                carry, carry_blocks = _carried(pieces, blocks, range_at, b)
+                entry = exit_off - int(rng.dst[b])
+                counts["carry_peak"] = max(counts["carry_peak"], carry.size)
+            del data, pieces, rng, buf
+        if not counts["ranges"]:
+            raise IndexBuildError("%s ends without a whole BGZF block behind stream offset %d" % (name, expect))
+        if carry is not None:
+            raise IndexBuildError("%s is cut inside a record: its last record starts %d bytes before the end of the data and does not fit"
+                                  % (name, total - exit_off))
+        if pending is not None:
+            pending.at_end = True
+            yield pending
+    except sam.BgzfStreamError as exc:
+        raise IndexBuildError("%s: %s" % (name, exc)) from None
+    except IndexBuildError as exc:
+        raise IndexBuildError(str(exc).replace("file offset", "stream offset")) from None
+    finally:
+        if stats is not None:
+            stats.update(counts)
+        if hasattr(chunks, "close"):
+            chunks.close()
 
 
 def walk_offsets(lib, torch, kernels, dev, rng, closed=False):

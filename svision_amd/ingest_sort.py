@@ -30,8 +30,13 @@ between.  The pass then has a second form, for text:
   several   the header is sort.merge_headers over the inputs; SAM parts resolve their names against the merged dictionary (a part
             without header is fine), a BAM part's tids go through its old -> merged table; the parts follow each other in list
             order, so the stable sort leaves ties in list order, then file order.  At most one input is ``-``
-A BAM or gzip data on a pipe is refused (SVX_DEVICE_SORT=write takes a BAM there).  A failure closes the pipe's read end, so the
-aligner ends with SIGPIPE; the message names the input and the line.
+  a BAM on a pipe  what ``dorado aligner`` and ``pbmm2`` write.  Refused by default (SVX_DEVICE_SORT=write takes a BAM there).
+            ``pipe_bam="stream"`` / ``SVX_PIPE_BAM=stream`` (off by default: DESIGN section 9): a source of kind "bam_pipe" -- its
+            header through zlib from the stream (io.sam.StreamReader.bam_header), its BGZF members in chunks of ``range_bytes``
+            compressed bytes read once into pinned buffers, and the BAM pass above over index.stream_ranges, which carries a cut
+            record's blocks forward where a file's pass seeks back.  Alone or one of several inputs
+Gzip data that is no BAM is refused on a pipe.  A failure closes the pipe's read end, so the aligner ends with SIGPIPE; the message names
+the input and the line, or the stream offset.
 """
 import struct
 
@@ -90,16 +95,18 @@ def _cat_offsets(torch, parts, totals, dev):
 
 class _Source:
     """One input of :func:`load_sample`: the textin.TextInput -- its ``kind`` ("bam", "sam": text in a regular file, "pipe": text read
-    once), ``path`` and the ``name`` messages call it --, its own header -- ``references``, ``lengths``, ``text`` (a headerless SAM
-    part: none) --, ``bam_head`` (read_bam_header's, a BAM) and ``remap``: a BAM part's old -> merged tid table among several inputs."""
+    once, "bam_pipe": a BAM read once), ``path`` and the ``name`` messages call it --, its own header -- ``references``, ``lengths``,
+    ``text`` (a headerless SAM part: none) --, ``bam_head`` (read_bam_header's, a BAM), ``first`` (a BAM read once: where its first
+    record starts, StreamReader.bam_header's) and ``remap``: a BAM part's old -> merged tid table among several inputs."""
 
-    def __init__(self, inp, references, lengths, text, bam_head=None):
-        self.input, self.kind, self.path, self.name = inp, inp.kind, inp.path, inp.name
-        self.references, self.lengths, self.text, self.bam_head, self.remap = references, lengths, text, bam_head, None
+    def __init__(self, inp, references, lengths, text, bam_head=None, first=None):
+        self.input, self.kind, self.path, self.name = inp, "bam_pipe" if first is not None else inp.kind, inp.path, inp.name
+        self.references, self.lengths, self.text, self.bam_head, self.first, self.remap = references, lengths, text, bam_head, first, None
 
 
-def _open_source(path, alone):
-    """An input opened and its header read -> _Source.  SAM text without an @SQ line is fine as one of several inputs (not ``alone``)."""
+def _open_source(path, alone, stream_bam=False):
+    """An input opened and its header read -> _Source.  SAM text without an @SQ line is fine as one of several inputs (not ``alone``).
+    ``stream_bam``: a BAM on a pipe is taken (its header read from the stream), not refused."""
     from .io import sam
     from .io.bam import read_bam_header
     try:
@@ -112,8 +119,16 @@ def _open_source(path, alone):
         except ValueError as exc:                               # (the host reader inflates in front of the header's end: a corrupt block shows here)
             raise SortIngestError(str(exc)) from None
         return _Source(inp, head.references, head.lengths, head.header_text, head)
+    if inp.peek_kind == sam.STREAM_BAM and stream_bam:
+        try:
+            got = inp.reader.bam_header()
+        except sam.BgzfStreamError as exc:
+            inp.close(failed=True)
+            raise SortIngestError("%s: %s" % (inp.name, exc)) from None
+        return _Source(inp, got.table.references, got.table.lengths, got.table.header_text, got.table, got.first)
     refusal = {sam.STREAM_BAM: "a BAM on a pipe is not taken under SVX_DEVICE_SORT=1 -- SVX_DEVICE_SORT=write sorts it in one pass, or give "
-                               "the aligner's SAM text",
+                               "the aligner's SAM text; SVX_PIPE_BAM=stream (load_sample's pipe_bam) takes it as it arrives, a switch that "
+                               "is off by default",
                sam.STREAM_GZIP: "gzip-compressed data that is no BAM -- compressed SAM is not taken: decompress it in the pipe, "
                                 "`pigz -dc x.sam.gz | ... -b -`",
                sam.STREAM_EMPTY: "no input", sam.STREAM_OTHER: "neither SAM text nor a BAM"}.get(inp.peek_kind)
@@ -229,18 +244,25 @@ def _remapped(torch, src, d_tid, dev):
     return torch.where(d_tid < 0, d_tid, d_map[d_tid.clamp(min=0).long()])
 
 
-def load_sample(bam_path, fasta, min_sv, device="cuda", with_seq=False, range_bytes=None, stats=None):
+def load_sample(bam_path, fasta, min_sv, device="cuda", with_seq=False, range_bytes=None, stats=None, pipe_bam=None):
     """The :class:`svision_amd.sample.Sample` of records that come in any order (see the head of the module).  ``bam_path``: a BAM, SAM
     text, ``-`` or another path that is no regular file (text read once), or a list of those.  ``with_seq``: the table carries the
     read bases (--hash / --graph).  ``range_bytes``: compressed bytes a range of a BAM (default: the device decoder's group size),
-    text bytes a chunk of SAM text (default: sort.DEFAULT_SAM_CHUNK_BYTES); tests.  ``stats``: a dict that receives the number of
-    ranges and records, the CIGAR words, the inputs' kinds, the lines the host took and the seconds per stage."""
+    text bytes a chunk of SAM text (default: sort.DEFAULT_SAM_CHUNK_BYTES), compressed bytes a chunk of a BAM on a pipe (default:
+    textin.DEFAULT_PIPE_BAM_BYTES); tests.  ``stats``: a dict that receives the number of ranges and records, the CIGAR words, the
+    inputs' kinds, the lines the host took, the seconds per stage and, per input that was read once, its reader's bytes and waits
+    (``pipes``).  ``pipe_bam``: "stream" takes a BAM on a pipe in one pass (kind "bam_pipe"); "spool", "0" or unset refuse it as before;
+    None: ``SVX_PIPE_BAM`` of the environment."""
     from . import index, kernels, sort
     from .io import sam
     from .io.bam import AlignmentTable
     from .sample import Sample
     torch, lib, dev, clock = index.on_device("load_sample needs the GPU (svx_record_sort)", device, STAGES)
     paths = sort.input_paths(bam_path)
+    try:
+        stream_bam = textin.pipe_bam_setting(pipe_bam, "load_sample")
+    except ValueError as exc:
+        raise SortIngestError(str(exc)) from None
     label = paths[0] if len(paths) == 1 else "%s (+ %d more)" % (paths[0], len(paths) - 1)
     if paths.count("-") > 1:
         raise SortIngestError("%s is named twice: standard input is one stream" % sam.STREAM_NAME)
@@ -248,7 +270,7 @@ def load_sample(bam_path, fasta, min_sv, device="cuda", with_seq=False, range_by
     parts, n, words, name_bytes, seq_bytes, ranges, host_lines, sources = [], 0, 0, 0, 0, 0, 0, []
     try:
         for p in paths:
-            sources.append(_open_source(p, len(paths) == 1))
+            sources.append(_open_source(p, len(paths) == 1, stream_bam))
         if len(sources) == 1:
             references, lengths, header_text = sources[0].references, sources[0].lengths, sources[0].text
             label = sources[0].name
@@ -259,13 +281,17 @@ def load_sample(bam_path, fasta, min_sv, device="cuda", with_seq=False, range_by
                 raise SortIngestError(str(exc)) from None
             references, lengths, header_text = merged.references, merged.lengths, merged.text
             for s, table in zip(sources, merged.maps):
-                s.remap = table if s.kind == "bam" else None
+                s.remap = table if s.bam_head is not None else None
         n_ref = len(references)
         try:
             with torch.cuda.device(dev):
                 for src in sources:
+                    text_pass = None
                     if src.kind == "bam":
                         ranges_of = index.record_ranges(src.path, src.bam_head, dev, clock, range_bytes, with_seq=with_seq)
+                    elif src.kind == "bam_pipe":
+                        ranges_of = index.stream_ranges(textin.member_chunks(torch, src.input, range_bytes), src.bam_head, src.first, dev, clock,
+                                                        with_seq=with_seq, name=src.name)
                     else:
                         text_pass = _TextPass(torch, lib, kernels, dev, clock, references, with_seq)
                         ranges_of = text_pass.parts(src, range_bytes)
@@ -279,7 +305,7 @@ def load_sample(bam_path, fasta, min_sv, device="cuda", with_seq=False, range_by
                                 rng.d_tid = _remapped(torch, src, rng.d_tid, dev)
                             parts.append(rng)
                             n, words, name_bytes, seq_bytes = n + rng.n_rec, words + rng.words, name_bytes + rng.name_bytes, seq_bytes + rng.seq_bytes
-                    if src.kind != "bam":
+                    if text_pass is not None:
                         host_lines += text_pass.host_lines
                         del text_pass
                 if n > 0xFFFFFFFF:
@@ -317,7 +343,9 @@ def load_sample(bam_path, fasta, min_sv, device="cuda", with_seq=False, range_by
     clock.lap("scan")
     if stats is not None:
         stats.update(ranges=ranges, records=n, cigar_words=words, pos_bits=pos_bits, passes=len(digit_plan(n_ref, pos_bits)),
-                     inputs=[s.kind for s in sources], host_lines=host_lines, seconds={k: round(v, 6) for k, v in clock.times.items()})
+                     inputs=[s.kind for s in sources], host_lines=host_lines, seconds={k: round(v, 6) for k, v in clock.times.items()},
+                     pipes=[dict(name=s.name, bytes=s.input.reader.text_bytes, reader_wait_pipe_s=round(s.input.reader.wait_pipe, 6),
+                                 reader_wait_buffer_s=round(s.input.reader.wait_buffer, 6)) for s in sources if s.input.reader is not None])
     return sample
 
 

@@ -1,7 +1,9 @@
 """SAM text -> the BAM record bytes htslib writes for it (``sam_parse1`` + ``bam_write1``): the host statement of the rules the
 device parser (svision_amd/csrc/svx_sam_core.hpp) follows, the road of every line that parser hands back (``SVX_SAM_HOST``), and the
 yardstick of its CPU model (tools/hostwave/sam_main.cpp).  Pure Python + ``struct``.  At the end of the file: :class:`StreamReader`,
-the text of a pipe read once -- its first bytes, its header, its chunks filled by a thread of their own (host only, no torch).
+the text of a pipe read once -- its first bytes, its header, its chunks filled by a thread of their own (host only, no torch) --, and
+the same for a BAM that arrives there: its header through zlib (:meth:`StreamReader.bam_header`) and its bytes in chunks of whole BGZF
+members (:meth:`StreamReader.member_chunks`).
 
 The header.  The ``@`` lines in front of the first record are the BAM header's text, byte for byte; the reference dictionary is
 the ``@SQ`` lines' ``SN`` / ``LN`` in order.  No ``@SQ`` line: SamError.  An ``@`` line behind a record: SamError.
@@ -343,14 +345,15 @@ class StreamReader:
     they return stays there for :meth:`chunks`.  A descriptor is polled in front of every read, so :meth:`close` ends a reading thread
     within ``POLL_S`` although the writer is silent; ``close`` closes a descriptor the reader owns (``own``), so that the writer ends
     with EPIPE and does not block on a full pipe.  ``wait_pipe`` / ``wait_buffer``: the seconds the thread of :meth:`chunks` waited for
-    the stream and for a free buffer; ``text_bytes``: the bytes read so far."""
+    the stream and for a free buffer; ``text_bytes``: the bytes read so far (of a BAM: its compressed bytes); ``buf_at``: the stream
+    offset of the buffer's first byte once :meth:`bam_header` dropped the members in front of the first record's."""
     POLL_S = 0.05
     PEEK = 1 << 16
 
     def __init__(self, src, own=False):
         self.fd = src if isinstance(src, int) else None
         self.obj = None if isinstance(src, int) else src
-        self.own, self.buf, self.eof, self.text_bytes = own, bytearray(), False, 0
+        self.own, self.buf, self.eof, self.text_bytes, self.buf_at = own, bytearray(), False, 0, 0
         self.wait_pipe = self.wait_buffer = 0.0
         self._stop, self._thread, self._closed = threading.Event(), None, False
         self._poll = None
@@ -473,6 +476,12 @@ class StreamReader:
             except BaseException as exc:                        # (handed to the caller, raised there)
                 ready.put(exc)
 
+        return self._served(fill, free, ready)
+
+    def _served(self, fill, free, ready):
+        """What both chunk generators do with their filling thread: it is started, its chunks are handed on as they get ready -- a
+        chunk's buffer goes back to it when the caller asks for the next --, its exception is raised here, and the reader is closed
+        when the generator ends or is dropped."""
         self._thread = threading.Thread(target=fill, name="svx-sam-stream", daemon=True)
         self._free = free
         self._thread.start()
@@ -487,6 +496,113 @@ class StreamReader:
                 free.put(item[0])
         finally:
             self.close()
+
+    # -- a BAM on the stream: its header through zlib, then its bytes in chunks of whole BGZF members
+    def bam_header(self, limit=1 << 30):
+        """The header of a BAM read from the stream: the leading BGZF members inflated with zlib until the text and the reference
+        dictionary are complete -> BamStreamHead(``table``: what io.bam.read_bam_header gives for the same bytes as a file; ``first``:
+        (the stream offset of the member the first record starts in, the record's offset in that member's inflated bytes, the number
+        of references) -- index.first_record's triple; ``head``: the inflated bytes in front of the first record).  The members in
+        front of that one are dropped; it and everything read behind it stay in the buffer for :meth:`member_chunks`, and ``buf_at``
+        is its stream offset.  A header that fills its members exactly: the first record opens the next one, which need not have
+        arrived.  BgzfStreamError: no BGZF member, one that does not inflate, no BAM, a stream that ends inside the header."""
+        from .bam import AlignmentTable
+        import numpy as np
+        head, at, size = bytearray(), 0, _BamHeaderSize()
+        while True:
+            bsize, xlen = _member_at(self.buf, at, len(self.buf), self.buf_at)
+            while not bsize or at + bsize > len(self.buf):
+                if not self._more():
+                    raise BgzfStreamError("no BGZF block at stream offset %d (the BAM header is cut)" % (self.buf_at + len(self.buf))
+                                          if at == len(self.buf) else "no whole BGZF block at stream offset %d" % (self.buf_at + at), self.buf_at + at)
+                bsize, xlen = _member_at(self.buf, at, len(self.buf), self.buf_at)
+            try:
+                data = zlib.decompress(bytes(self.buf[at + 12 + xlen:at + bsize - 8]), -15)
+            except zlib.error as exc:
+                raise BgzfStreamError("the block at stream offset %d does not inflate (%s)" % (self.buf_at + at, exc), self.buf_at + at) from None
+            base = len(head)
+            head += data
+            need = size(head)
+            if need is not None:
+                break
+            if len(head) > limit:
+                raise BgzfStreamError("a BAM header of more than %d bytes" % limit, self.buf_at + at)
+            at += bsize
+        if need == len(head):                                   # the header fills its member: the first record opens the next one
+            at, entry = at + bsize, 0
+        else:
+            at, entry = at, need - base
+        del self.buf[:at]
+        self.buf_at += at
+        head = bytes(head[:need])
+        l_text = struct.unpack_from("<i", head, 4)[0]
+        text = head[8:8 + l_text].split(b"\0", 1)[0].decode()   # (the native reader's rule: the text ends at its first NUL)
+        n_ref, p = struct.unpack_from("<i", head, 8 + l_text)[0], 12 + l_text
+        references, lengths = [], []
+        for _ in range(n_ref):
+            l_name = struct.unpack_from("<i", head, p)[0]
+            references.append(head[p + 4:p + 4 + max(l_name - 1, 0)].decode())
+            lengths.append(struct.unpack_from("<i", head, p + 4 + l_name)[0])
+            p += 8 + l_name
+        none = np.empty(0, np.int32)
+        table = AlignmentTable(references, lengths, none, none, none, none, none, none, [], none, np.zeros(1, np.int64), text)
+        return BamStreamHead(table, (self.buf_at, entry, n_ref), head)
+
+    def member_chunks(self, range_bytes, alloc=None, buffers=2):
+        """The rest of a BGZF stream -> (buffer, n_bytes, the stream offset of the chunk's first byte) per chunk: ``buffer[:n_bytes]``
+        is WHOLE BGZF members, found by hopping over the BSIZE fields from the chunk's first byte -- as many as end within
+        ``range_bytes``, and at least one; the partial member behind them is carried into the next buffer.  The chunks cover the stream
+        once, in order, from what :meth:`peek` and :meth:`bam_header` left in the buffer on, whatever the reads return; none is empty.
+        Thread, buffers and :meth:`close` as in :meth:`chunks`; a buffer holds at least one member of the largest size (65,536).
+        BgzfStreamError, with the stream offset: a member whose header is not BGZF's (plain gzip has no BC field), a BSIZE too small
+        for header and trailer (below 25), a stream that ends inside a member."""
+        range_bytes = max(int(range_bytes), 1)
+        room = max(range_bytes, MAX_MEMBER)
+        alloc = alloc or bytearray
+        free, ready = queue.Queue(), queue.Queue()
+        for _ in range(max(int(buffers), 2)):
+            free.put(alloc(room))
+
+        def fill():
+            tail, offset = bytes(self.buf), self.buf_at
+            self.buf = bytearray()
+            try:
+                while not self._stop.is_set() and (tail or not self.eof):
+                    t0 = time.perf_counter()
+                    buf = free.get()
+                    self.wait_buffer += time.perf_counter() - t0
+                    if buf is None:
+                        return
+                    view = memoryview(buf).cast("B")
+                    if len(tail) > len(view):                   # (the header's read-ahead beyond a buffer: the larger one takes
+                        buf = alloc(len(tail) + MAX_MEMBER)     # its place in the ring for good, so at most ``buffers`` such allocations)
+                        view = memoryview(buf).cast("B")
+                    n = len(tail)
+                    view[:n] = tail
+                    cut, at = _member_cut(view, n, range_bytes, self.eof, 0, offset)
+                    while not cut and not self.eof:
+                        t0 = time.perf_counter()
+                        got = self.read_into(view[n:])          # (never full here: a buffer holds the largest member)
+                        self.wait_pipe += time.perf_counter() - t0
+                        if got <= 0:
+                            self.eof = True
+                        else:
+                            self.text_bytes += got
+                            n += got
+                        cut, at = _member_cut(view, n, range_bytes, self.eof, at, offset)
+                    if self._stop.is_set():
+                        return
+                    tail = bytes(view[cut:n])
+                    if cut:
+                        ready.put((buf, cut, offset))
+                        offset += cut
+                    else:
+                        free.put(buf)
+                ready.put(None)
+            except BaseException as exc:                        # (handed to the caller, raised there)
+                ready.put(exc)
+
+        return self._served(fill, free, ready)
 
     def close(self):
         """The reading thread ended and the descriptor, where the reader owns it, closed; what was not read is dropped."""
@@ -538,3 +654,102 @@ def _chunk_cut(view, n, range_bytes, eof, scanned):
 def _count_newlines(view, n):
     import numpy as np
     return int(np.count_nonzero(np.frombuffer(view[:n], np.uint8) == 10))
+
+
+# ---- a BGZF stream: its members, hopped over from header to header ----
+MAX_MEMBER = 1 << 16                                            # BSIZE is 16 bits: no BGZF member is longer
+BamStreamHead = collections.namedtuple("BamStreamHead", "table first head")
+
+
+class BgzfStreamError(ValueError):
+    """A stream that is no chain of whole BGZF members -- ``offset``: the stream offset the message names."""
+
+    def __init__(self, message, offset):
+        ValueError.__init__(self, message)
+        self.offset = offset
+
+
+class _BamHeaderSize:
+    """``size(head)``, called as the inflated bytes at the start of a BAM grow -> the bytes in front of the first record -- magic, text,
+    reference dictionary -- once they are all there, None before.  It goes on where the call before stopped."""
+
+    def __init__(self):
+        self.p, self.left = None, None                          # where the next field to read starts, the references still to hop over
+
+    def __call__(self, head):
+        if self.p is None:
+            if len(head) < 8:
+                return None
+            if bytes(head[:4]) != b"BAM\x01":
+                raise BgzfStreamError("not a BAM: its inflated bytes do not start with the BAM magic", 0)
+            l_text = struct.unpack_from("<i", head, 4)[0]
+            if l_text < 0:
+                raise BgzfStreamError("a malformed BAM header: a text of %d bytes" % l_text, 0)
+            self.p = 8 + l_text
+        if self.left is None:
+            if len(head) < self.p + 4:
+                return None
+            self.left, self.p = struct.unpack_from("<i", head, self.p)[0], self.p + 4
+        while self.left > 0:
+            if len(head) < self.p + 4:
+                return None
+            l_name = struct.unpack_from("<i", head, self.p)[0]
+            if l_name < 0:
+                raise BgzfStreamError("a malformed BAM header: a reference name of %d bytes" % l_name, 0)
+            if len(head) < self.p + 8 + l_name:
+                return None
+            self.p, self.left = self.p + 8 + l_name, self.left - 1
+        return self.p
+
+
+def _member_at(view, at, n, base=0):
+    """The BGZF member whose header starts at view[at], of the n bytes in hand -> (its length by BSIZE, its XLEN); (0, 0): the bytes
+    end inside its header.  ``base``: the stream offset of view[0], for the refusal of a header that is not BGZF's -- other magic or
+    flags, no BC subfield (plain gzip) -- or whose BSIZE does not hold header and trailer."""
+    if n - at < 12:
+        if bytes(view[at:min(n, at + 4)]) != b"\x1f\x8b\x08\x04"[:max(n - at, 0)]:
+            raise BgzfStreamError("no BGZF block at stream offset %d" % (base + at), base + at)
+        return 0, 0
+    fixed = bytes(view[at:at + 12])
+    if fixed[:3] == b"\x1f\x8b\x08" and not fixed[3] & 4:
+        raise BgzfStreamError("no BGZF block at stream offset %d: a gzip member without an extra field (plain gzip is not BGZF)" % (base + at), base + at)
+    if fixed[:4] != b"\x1f\x8b\x08\x04":
+        raise BgzfStreamError("no BGZF block at stream offset %d" % (base + at), base + at)
+    xlen = struct.unpack_from("<H", fixed, 10)[0]
+    if n - at < 12 + xlen:
+        return 0, 0
+    extra, bsize, q = bytes(view[at + 12:at + 12 + xlen]), None, 0
+    while q + 4 <= xlen:
+        slen = struct.unpack_from("<H", extra, q + 2)[0]
+        if extra[q:q + 2] == b"BC" and slen == 2 and q + 6 <= xlen:
+            bsize = struct.unpack_from("<H", extra, q + 4)[0] + 1
+        q += 4 + slen
+    if bsize is None:
+        raise BgzfStreamError("no BGZF block at stream offset %d: a gzip member without the BC field (plain gzip is not BGZF)" % (base + at), base + at)
+    if bsize < 12 + xlen + 8:
+        raise BgzfStreamError("no whole BGZF block at stream offset %d: a BSIZE of %d does not hold its header and trailer" % (base + at, bsize - 1),
+                              base + at)
+    return bsize, xlen
+
+
+def _member_cut(view, n, range_bytes, eof, at, base):
+    """Where the chunk at the front of view[:n] ends: behind the last member that ends within its first ``range_bytes``; none does:
+    behind the first one.  ``at``: 0 for a new chunk, then what the call before returned -- the members up to there are whole and are
+    not hopped over again.  -> (the cut, 0: more bytes are needed; ``at``).  The stream's end closes the last chunk, and raises
+    BgzfStreamError where it falls inside a member."""
+    while True:
+        bsize = _member_at(view, at, n, base)[0] if at < n else 0
+        if bsize and at + bsize <= n:                           # a whole member
+            if at + bsize > range_bytes and at:
+                return at, at
+            at += bsize
+            if at >= range_bytes:
+                return at, at
+            continue
+        if at and n >= range_bytes and at < n:                  # the next member ends behind the bytes in hand, so behind range_bytes
+            return at, at
+        if eof:
+            if at < n:
+                raise BgzfStreamError("no whole BGZF block at stream offset %d: the stream ends inside it" % (base + at), base + at)
+            return at, at
+        return 0, at

@@ -98,15 +98,25 @@ before a byte is read.  The text is seen ONCE, and the two files are those of th
             again), against the merged names and under the merged header, and is that file from ``_open_all`` on; its place in the
             list decides ties; without @SQ lines it is usable beside parts that have them.  ``-`` may appear once; further pipes of a run (FIFOs) spool to
             ``.spool.<pid>.<number>.bam`` and ``stats["pipes"]`` lists them all
-  a BAM on a pipe  (``samtools view -b``, ``dorado aligner``, ``pbmm2``): BGZF or gzip magic whose inflated head is ``BAM\\1``.  No
-            one-pass road is built for it: the bytes are copied as they are into the spool file and the BAM road sorts that file --
-            one behaviour for the user at the price of one write and one read of compressed BAM
+  a BAM on a pipe  (``samtools view -b``, ``dorado aligner``, ``pbmm2``): BGZF or gzip magic whose inflated head is ``BAM\\1``.  By
+            default the bytes are copied as they are into the spool file and the BAM road sorts that file -- one write and one read
+            of compressed BAM more, room for it beside the output, and nothing runs on the device until the aligner has ended
+  a BAM on a pipe, streamed  ``pipe_bam="stream"`` (``--pipe-bam stream``, ``SVX_PIPE_BAM=stream``; off by default: measured, it wins in
+            core and loses once it spools, profiles/pipe_bam.txt and DESIGN section 9) takes a LONE such pipe in one pass (``BAM_PIPE_SOURCE``, :func:`_bam_pipe_key_pass`): the header
+            through zlib from the stream (io.sam.StreamReader.bam_header), the BGZF members in chunks of ``range_bytes`` compressed
+            bytes (textin.member_chunks: the reader's thread, pinned buffers), and per range the BAM key pass over index.stream_ranges,
+            which carries a cut record's compressed blocks into the next range where a file's pass seeks back.  A range's records
+            ``d_raw[first:exit_off]`` are a segment of exactly their size; :func:`keeps_in_core`, the spool beyond the budget (the
+            kept records first, then every range's), the join and the statistics are the text pipe's.  In core no spool file exists
+            at any moment.  Among several inputs a BAM pipe keeps the copy as it is under either setting: it would be spooled from its
+            first byte anyway, and the copy is the cheapest form of that
   refused   other gzip data (compressed SAM: ``pigz -dc x.sam.gz | ... -`` is the road), no byte at all (``<stdin>: no input``)
 On any failure the read end is closed BEFORE the error is raised -- standard input is pointed at the null device --, so that the
 pipe's writer ends with EPIPE / SIGPIPE and does not block on a full pipe; no output, no temporary and no spool is left.  An early
 end of the writer is no error by itself: what arrived is the input, and a cut last line fails by the parser's rules with its number.
-``stats["pipe"]``: mode ("in_core", "spooled", "bam_spooled"), grows (segments + the join), spool_bytes, text_bytes, and the seconds the
-reader's thread waited for the pipe and for a free buffer.
+``stats["pipe"]``: mode ("in_core", "spooled", "bam_spooled"), holds ("sam", "bam": what the pipe held), grows (segments + the join),
+spool_bytes, text_bytes (the bytes read: of a BAM its compressed bytes, ``compressed_bytes`` too), and the seconds the reader's
+thread waited for the pipe and for a free buffer.
 
 Several inputs.  ``sort_bam([a.bam, b.sam, c.bam], out)`` -- ``python -m svision_amd.sort a.bam b.sam c.bam -o out.bam`` -- writes ONE sorted
 BAM of all their records, what ``samtools merge`` in front of the sort would have given: one BAM per SMRT cell, one SAM per FASTQ batch.
@@ -614,7 +624,8 @@ MergedHead = collections.namedtuple("MergedHead", "references lengths")
 
 # What the steps of one run share besides the device: where the output goes (a spool lies beside it), the output's chunk, the budget
 # for the records' bytes, ``pipes``: every :class:`_Pipe` the run opened, for sort_bam to close and to clean up behind, and the clock.
-_Run = collections.namedtuple("_Run", "out_path chunk_blocks budget range_bytes pipes clock")
+# ``stream_bam``: a lone BAM on a pipe is taken in one pass (``pipe_bam="stream"``), not copied into a file first.
+_Run = collections.namedtuple("_Run", "out_path chunk_blocks budget range_bytes pipes clock stream_bam", defaults=(False,))
 
 
 def _open_all(paths, dv=None, run=None):
@@ -771,7 +782,7 @@ def _key_passes(dv, ins, budget, range_bytes):
         kp.parts.append((opened, part, ranges, records))
         kp.reading = opened.path
         opened.source.key_pass(dv, opened, range_bytes, part, kp.d_stream)
-        if opened.source is PIPE_SOURCE and opened.pipe.mode == "spooled":
+        if (opened.source is PIPE_SOURCE or opened.source is BAM_PIPE_SOURCE) and opened.pipe.mode == "spooled":
             # the pipe did not fit: what its pass kept is dropped, the input becomes its spool file and takes the road of a BAM
             again = _open(opened.pipe.spool_file)._replace(pipe=opened.pipe)
             del part, kp
@@ -1080,6 +1091,7 @@ class _Pipe:
         self.input, self.name, self.run, self.number = inp, inp.name, run, len(run.pipes)
         self.mode, self.ledger, self.segments, self.spool, self.spool_file = "in_core", StreamLedger(), [], None, None
         self.spool_bytes = self.host_lines = 0
+        self.holds, self.bam_header = "sam", None               # what the pipe held; a streamed BAM: the bytes in front of its first record
 
     def discard(self):
         self.segments = []
@@ -1089,13 +1101,15 @@ class _Pipe:
 
     def stats(self):
         reader = self.input.reader
-        return dict(mode=self.mode, grows=self.ledger.grows, spool_bytes=self.spool_bytes, text_bytes=reader.text_bytes,
-                    reader_wait_pipe_s=round(reader.wait_pipe, 6), reader_wait_buffer_s=round(reader.wait_buffer, 6))
+        return dict(mode=self.mode, holds=self.holds, grows=self.ledger.grows, spool_bytes=self.spool_bytes, text_bytes=reader.text_bytes,
+                    reader_wait_pipe_s=round(reader.wait_pipe, 6), reader_wait_buffer_s=round(reader.wait_buffer, 6),
+                    **(dict(compressed_bytes=reader.text_bytes) if self.holds == "bam" else {}))
 
 
 def _open_pipe(inp, alone, run):
     """open, an input that is read once, by what its first bytes hold.  SAM text: :func:`_open_sam`'s Opened, its source PIPE_SOURCE,
-    the text waiting in the pipe.  A BAM: copied as it is into the spool file, which is opened as any BAM.  Anything else: refused."""
+    the text waiting in the pipe.  A BAM: copied as it is into the spool file, which is opened as any BAM -- or, alone and under
+    ``run.stream_bam``, its header read from the stream and the rest left waiting for BAM_PIPE_SOURCE.  Anything else: refused."""
     from .io import sam
     pipe = _Pipe(inp, run)
     run.pipes.append(pipe)
@@ -1104,6 +1118,14 @@ def _open_pipe(inp, alone, run):
         raise SortWriteError(refusal[inp.peek_kind] % inp.name)
     if inp.peek_kind == sam.STREAM_SAM:
         return _open_sam(inp, alone, pipe)
+    pipe.holds = "bam"
+    if alone and run.stream_bam:
+        try:
+            got = inp.reader.bam_header()
+            pipe.bam_header = got.head
+            return Opened(inp.name, got.table, got.first, sorted_header_bytes(got.head), None, BAM_PIPE_SOURCE, None, pipe, inp)
+        except (sam.BgzfStreamError, ValueError, struct.error) as exc:
+            raise SortWriteError("%s: %s" % (inp.name, exc)) from None
     pipe.mode = "bam_spooled"
     try:
         pipe.spool_file, pipe.spool_bytes = spool_copy(inp.reader, run.out_path, run.clock, pipe.number)
@@ -1206,7 +1228,50 @@ def _pipe_spooled(dv, opened, header):
     return _open(opened.pipe.spool_file, alone=False)._replace(pipe=opened.pipe)
 
 
+def _bam_pipe_key_pass(dv, opened, range_bytes, kp, d_stream=None):
+    """key pass of a BAM on a pipe, the ONLY pass over it: :func:`_key_pass`'s body per range of index.stream_ranges -- the fields, the
+    lengths, the keys, :func:`_retid` where there is a remap -- and the range's record bytes ``d_raw[first:exit_off]`` AT ONCE into a
+    segment of exactly their size, as :func:`_pipe_key_pass` keeps a chunk's.  The first range :func:`keeps_in_core` refuses opens the
+    spool under the stream's own header, the kept records first (:func:`_pipe_to_spool`); from then on every range's records are
+    appended to it and nothing is kept; ``opened.pipe.mode`` says so to the caller."""
+    torch, dev, clock, pipe = dv.torch, dv.dev, dv.clock, opened.pipe
+    chunks = textin.member_chunks(torch, opened.text, range_bytes)
+    for rng in index.stream_ranges(chunks, opened.head, opened.first, dev, clock, name=opened.path):
+        kp.range_records.append(int(rng.n_rec))
+        kp.places.append(rng.place)
+        if rng.n_rec:
+            tid, pos, flag, span, rec_off = index._index_fields(dv.lib, torch, dv.kernels, dev, rng, clock)
+            first, last = int(rec_off[0]), int(rng.exit_off)
+            need = last - first
+            if opened.remap is not None:
+                _retid(dv, opened, kp, rng.d_raw, rng.d_rec_off, rng.d_tid)
+                tid = np.where(tid >= 0, opened.remap[np.maximum(tid, 0)], tid).astype(np.int32)
+            if pipe.spool is None and not keeps_in_core(kp.seen, need, pipe.run.budget):
+                _pipe_to_spool(dv, opened, kp, pipe.bam_header)
+            d_seg = torch.empty(need + (STREAM_SLACK if pipe.spool is not None else 0), dtype=torch.uint8, device=dev)
+            d_seg[:need].copy_(rng.d_raw[first:last])           # the records that complete in the range: contiguous there
+            d_seg[need:] = 0
+            if pipe.spool is not None:
+                pipe.spool.put(d_seg, need, pipe.run.chunk_blocks * BLOCK)
+            else:
+                pipe.segments.append(d_seg)
+                pipe.ledger.add(need)
+                kp.host.append((tid, pos, flag, span))
+                kp.lens.append(np.diff(np.append(rec_off, np.uint64(last)).astype(np.int64)))
+                kp.d_keys.append((rng.d_tid, rng.d_pos))
+            kp.seen += need
+            del d_seg
+        rng.d_raw = rng.d_starts = rng.d_base = rng.d_cigar = rng.d_cig_off = rng.d_names = rng.d_name_off = rng.d_rec_off = None
+        del rng
+        clock.lap("keep")
+    opened.text.close()
+    if pipe.spool is not None:
+        pipe.spool_file = pipe.spool.finish()
+        pipe.spool_bytes = pipe.spool.bytes
+
+
 BAM_SOURCE = Source("bam", _key_pass, _bam_again, lambda dv, opened, kp: _bam_fill(dv, opened, kp))
+BAM_PIPE_SOURCE = Source("bam_pipe", _bam_pipe_key_pass, _pipe_again, _pipe_fill)
 SAM_SOURCE = Source("sam", _sam_key_pass, _sam_again, lambda dv, opened, kp: _sam_fill(dv, opened, kp))     # (looked up at the call: tests replace it)
 PIPE_SOURCE = Source("pipe", _pipe_key_pass, _pipe_again, _pipe_fill)
 
@@ -1227,7 +1292,7 @@ def _bai(opened, kp, od, written, fmt="bai"):
 
 
 def sort_bam(bam_path, out_path, device="cuda", range_bytes=None, chunk_bytes=None, stats=None, tables="fixed", memory_bytes=None,
-             index_format="bai"):
+             index_format="bai", pipe_bam=None):
     """Write the records of ``bam_path`` in coordinate order to ``out_path`` and its index to ``out_path + ".bai"`` (see the head of the
     module); returns ``out_path``.  ``index_format="csi"``: the index is ``out_path + ".csi"`` and no ``.bai`` is written -- the sorted file's
     bytes are the same.  Under "bai" a record that reaches position 2^29 is refused (SortWriteError, neither file written): a ``.bai``
@@ -1250,7 +1315,10 @@ def sort_bam(bam_path, out_path, device="cuda", range_bytes=None, chunk_bytes=No
     stream_bytes is the largest total of the pipe's record buffers.  A side effect on the calling PROCESS: when the call fails while
     ``-`` is among the inputs, descriptor 0 is pointed at the null device (textin.TextInput.close) before the error is raised -- that closes the
     pipe's read end, so that its writer ends with EPIPE and does not block; a caller that needs standard input afterwards hands the
-    stream in as a path (/dev/fd/N of a duplicate) instead, whose descriptor is the call's own."""
+    stream in as a path (/dev/fd/N of a duplicate) instead, whose descriptor is the call's own.  ``pipe_bam``: what becomes of a BAM
+    that arrives on a pipe -- "spool" (the default): copied as it is into a file beside the output and sorted from there; "stream": a
+    lone such pipe is taken in one pass, ``range_bytes`` compressed bytes a chunk (default textin.DEFAULT_PIPE_BAM_BYTES), and
+    ``stats["pipe"]`` has mode "in_core" or "spooled", holds="bam" and compressed_bytes; None: ``SVX_PIPE_BAM`` of the environment."""
     from . import ingest_sort, kernels
     paths = input_paths(bam_path)
     torch, lib, dev, clock = index.on_device("sort_bam needs the GPU (svx_record_sort, svx_bgzf_deflate)", device, STAGES)
@@ -1258,6 +1326,7 @@ def sort_bam(bam_path, out_path, device="cuda", range_bytes=None, chunk_bytes=No
         raise ValueError("tables: %r is none of %s" % (tables, ", ".join(TABLES)))
     if index_format not in index.FORMATS:
         raise ValueError("index_format: %r is none of %s" % (index_format, ", ".join(index.FORMATS)))
+    stream_bam = textin.pipe_bam_setting(pipe_bam, "sort_bam")
     dv = _Dev(torch, lib, kernels, dev, clock)
     chunk_blocks = max(int(chunk_bytes or DEFAULT_CHUNK_BYTES) // BLOCK, 1)
     budget = None if memory_bytes is None else max(int(memory_bytes), 1)
@@ -1268,7 +1337,7 @@ def sort_bam(bam_path, out_path, device="cuda", range_bytes=None, chunk_bytes=No
         with torch.cuda.device(dev):
             if budget is None:                                  # half of what is free: the rest is for a range, its inflate workspace, keys and chunks
                 budget = max(int(torch.cuda.mem_get_info(dev)[0]) // 2, 1)
-            ins = _open_all(paths, dv, _Run(out_path, chunk_blocks, budget, range_bytes, pipes, clock))
+            ins = _open_all(paths, dv, _Run(out_path, chunk_blocks, budget, range_bytes, pipes, clock, stream_bam))
             opened = ins.merged
             opened, kp, spanned = _key_passes(dv, ins, budget, range_bytes)
             od = _order(dv, opened, kp, spanned, budget)
@@ -1303,7 +1372,7 @@ def sort_bam(bam_path, out_path, device="cuda", range_bytes=None, chunk_bytes=No
         for pipe in pipes:
             pipe.discard()
     if stats is not None:
-        was_text = lambda o: o.source is SAM_SOURCE or o.pipe is not None and o.pipe.mode != "bam_spooled"
+        was_text = lambda o: o.source is SAM_SOURCE or o.pipe is not None and o.pipe.holds == "sam"
         sam_parts = [(o, part) for o, part, _r, _n in kp.parts if was_text(o)]
         if sam_parts:
             stats.update(host_lines=sum(len(part.host_records) if o.pipe is None else o.pipe.host_lines for o, part in sam_parts))
@@ -1340,16 +1409,21 @@ def main(argv=None):
     ap.add_argument("--memory", type=parse_memory, default=os.environ.get("SVX_SORT_MEMORY") or None, metavar="BYTES",
                     help="device memory for the records' inflated bytes, with an optional K, M or G; a file with more is written in spans, a "
                          "pass over the input for each (default: $SVX_SORT_MEMORY, or half of the device memory that is free)")
+    ap.add_argument("--pipe-bam", choices=textin.PIPE_BAM, default=os.environ.get("SVX_PIPE_BAM") or "spool",
+                    help="a BAM that arrives on a pipe (dorado aligner, pbmm2): spool -- copied into a file beside the output, then sorted -- or "
+                         "stream -- a lone one taken in one pass, no file in between (default: $SVX_PIPE_BAM, or spool)")
     ap.add_argument("--stats-json", default=None, help="also write the statistics to this file")
     args = ap.parse_args(argv)
     if args.tables not in TABLES:
         ap.error("SVX_SORT_TABLES=%s: fixed or dynamic" % args.tables)
+    if args.pipe_bam not in textin.PIPE_BAM + ("0",):
+        ap.error("SVX_PIPE_BAM=%s: spool or stream" % args.pipe_bam)
     if os.environ.get("SVX_SORT_INDEX") not in (None, "", "bai", "csi"):
         ap.error("SVX_SORT_INDEX=%s: bai or csi" % os.environ["SVX_SORT_INDEX"])
     stats = {}
     try:
         path = sort_bam(args.bam[0] if len(args.bam) == 1 else args.bam, args.output, device=args.device, chunk_bytes=args.chunk_bytes, stats=stats, tables=args.tables,
-                        memory_bytes=args.memory, **(dict(index_format="csi") if args.csi else {}))
+                        memory_bytes=args.memory, pipe_bam=args.pipe_bam, **(dict(index_format="csi") if args.csi else {}))
     except (SortWriteError, _lib.SvxError, OSError) as exc:
         print("svision_amd.sort: %s" % exc, file=sys.stderr)
         return 1
@@ -1363,7 +1437,7 @@ def main(argv=None):
     if "pipe" in stats:
         pipe = stats["pipe"]
         name = next((textin.name_of(b) for b in args.bam if is_stream(b)), "<stdin>")
-        print("%s: %s (%d bytes) %s" % (path, name, pipe["text_bytes"],
+        print("%s: %s (%d bytes%s) %s" % (path, name, pipe["text_bytes"], " of BAM, taken in one pass" if pipe["holds"] == "bam" and pipe["mode"] != "bam_spooled" else "",
                                         "kept in core: its records grew %d time(s) on the device" % pipe["grows"] if pipe["mode"] == "in_core" else
                                         "spooled: %d bytes of unsorted BAM beside the output, sorted from there%s"
                                         % (pipe["spool_bytes"], " (a BAM on a pipe is copied as it is)" if pipe["mode"] == "bam_spooled" else "")))

@@ -2,7 +2,10 @@
 ``ingest_sort.load_sample`` (``SVX_DEVICE_SORT=1``: the sample, no file).  What both do the same way stands here once: how an input is
 opened and classified (:func:`open_input`), who owns a pipe's reader and how it is closed (:class:`TextInput`), how a chunk of SAM text
 gets into pinned memory (:class:`ChunkReader`) and onto the device (:func:`upload_lines`) -- and nothing of what either does with a
-chunk.  No refusal is worded here: a BAM on a pipe is spooled by the one consumer and refused by the other.
+chunk.  No refusal is worded here: a BAM on a pipe is spooled by the one consumer and refused by the other -- unless the switch both
+read the same way says "stream" (:func:`pipe_bam_setting`: ``pipe_bam`` / ``SVX_PIPE_BAM``, off by default): then either takes it in one
+pass, its header by io.sam.StreamReader.bam_header and its BGZF members by :func:`member_chunks`, the pinned buffers index.stream_ranges
+drives the device from.
 """
 import os
 import stat
@@ -148,6 +151,29 @@ class ChunkReader:
             self.clock.lap("read", False)
             yield Chunk(buf[:n], pinned[buf.ctypes.data], n, line_no, (at, n))
             at += n
+
+
+PIPE_BAM = ("spool", "stream")                                  # SVX_PIPE_BAM / ``pipe_bam``: a BAM on a pipe copied into a file first, or taken in one pass
+# Compressed bytes a chunk of a BAM on a pipe: the text chunk's size, not a file range's (ingest_gpu.LARGE_GROUP_BYTES) -- two pinned
+# buffers of it are held, and the device starts on the aligner's output a chunk behind it.  The one size measured: profiles/pipe_bam.txt
+DEFAULT_PIPE_BAM_BYTES = 64 << 20
+
+
+def pipe_bam_setting(pipe_bam, consumer):
+    """``pipe_bam`` as a consumer was handed it (None: ``SVX_PIPE_BAM`` of the environment) -> whether a BAM on a pipe is streamed.  Unset,
+    empty, "0" or "spool": the consumer's road of today; anything but those and "stream": ValueError."""
+    value = os.environ.get("SVX_PIPE_BAM") if pipe_bam is None else pipe_bam
+    if value in (None, "", "0") or value in PIPE_BAM:
+        return value == "stream"
+    raise ValueError("%s: pipe_bam (SVX_PIPE_BAM) is %r, none of %s" % (consumer, value, ", ".join(PIPE_BAM)))
+
+
+def member_chunks(torch, inp, range_bytes=None):
+    """The BGZF members of a BAM pipe behind its header (io.sam.StreamReader.bam_header has run) in chunks of ``range_bytes``
+    compressed bytes (default DEFAULT_PIPE_BAM_BYTES), read by the reader's thread into pinned buffers -> what index.stream_ranges takes."""
+    def alloc(n):                                               # (the NumPy view keeps its pinned tensor alive)
+        return torch.empty(n, dtype=torch.uint8, pin_memory=True).numpy()
+    return inp.reader.member_chunks(range_bytes or DEFAULT_PIPE_BAM_BYTES, alloc)
 
 
 def upload_lines(torch, kernels, dev, clock, chunk):
