@@ -27,7 +27,7 @@ between.  The pass then has a second form, for text:
             arrays a range of a BAM leaves (no BAM record in between, the tags are never read), and the text is dropped.  A line whose
             CIGAR is the placeholder ``<l_seq>S<n>N`` (SVX_SAM_HOST) is encoded by io.sam.encode_line; its counts and bytes go into
             the line's own slots, so the chunk's records stay in file order
-  several   the header is sort.merge_headers over the inputs; SAM parts resolve their names against the merged dictionary (a part
+  several   the header is sort_header.merge_headers over the inputs; SAM parts resolve their names against the merged dictionary (a part
             without header is fine), a BAM part's tids go through its old -> merged table; the parts follow each other in list
             order, so the stable sort leaves ties in list order, then file order.  At most one input is ``-``
   a BAM on a pipe  what ``dorado aligner`` and ``pbmm2`` write.  Refused by default (SVX_DEVICE_SORT=write takes a BAM there).
@@ -248,17 +248,17 @@ def load_sample(bam_path, fasta, min_sv, device="cuda", with_seq=False, range_by
     """The :class:`svision_amd.sample.Sample` of records that come in any order (see the head of the module).  ``bam_path``: a BAM, SAM
     text, ``-`` or another path that is no regular file (text read once), or a list of those.  ``with_seq``: the table carries the
     read bases (--hash / --graph).  ``range_bytes``: compressed bytes a range of a BAM (default: the device decoder's group size),
-    text bytes a chunk of SAM text (default: sort.DEFAULT_SAM_CHUNK_BYTES), compressed bytes a chunk of a BAM on a pipe (default:
+    text bytes a chunk of SAM text (default: textin.DEFAULT_SAM_CHUNK_BYTES), compressed bytes a chunk of a BAM on a pipe (default:
     textin.DEFAULT_PIPE_BAM_BYTES); tests.  ``stats``: a dict that receives the number of ranges and records, the CIGAR words, the
     inputs' kinds, the lines the host took, the seconds per stage and, per input that was read once, its reader's bytes and waits
     (``pipes``).  ``pipe_bam``: "stream" takes a BAM on a pipe in one pass (kind "bam_pipe"); "spool", "0" or unset refuse it as before;
     None: ``SVX_PIPE_BAM`` of the environment."""
-    from . import index, kernels, sort
+    from . import index, kernels, sort_header
     from .io import sam
     from .io.bam import AlignmentTable
     from .sample import Sample
     torch, lib, dev, clock = index.on_device("load_sample needs the GPU (svx_record_sort)", device, STAGES)
-    paths = sort.input_paths(bam_path)
+    paths = textin.input_paths(bam_path)
     try:
         stream_bam = textin.pipe_bam_setting(pipe_bam, "load_sample")
     except ValueError as exc:
@@ -276,8 +276,8 @@ def load_sample(bam_path, fasta, min_sv, device="cuda", with_seq=False, range_by
             label = sources[0].name
         else:
             try:
-                merged = sort.merge_headers([(s.name, s.text, s.references, s.lengths) for s in sources])
-            except sort.SortWriteError as exc:
+                merged = sort_header.merge_headers([(s.name, s.text, s.references, s.lengths) for s in sources])
+            except sort_header.SortWriteError as exc:
                 raise SortIngestError(str(exc)) from None
             references, lengths, header_text = merged.references, merged.lengths, merged.text
             for s, table in zip(sources, merged.maps):

@@ -1,4 +1,4 @@
-"""sort_bam on a BAM that arrives through a pipe, taken in one pass (svision_amd/sort.py: BAM_PIPE_SOURCE over index.stream_ranges, under
+"""sort_bam on a BAM that arrives through a pipe, taken in one pass (svision_amd/sort_sources.py: BamPipeSource over index.stream_ranges, under
 ``pipe_bam="stream"``): the two files written must be, byte for byte, those of the same bytes read from a regular file -- in core with
 no spool file at any moment, beyond the budget through the spool, among several inputs through the copy as it is -- and a failure leaves
 nothing and ends the writer.  The cases are those of tests/pipebam_cases.py; in-process tests read a FIFO fed by a daemon thread, the

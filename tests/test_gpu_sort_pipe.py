@@ -1,4 +1,4 @@
-"""sort_bam on an aligner's output that arrives through a pipe (svision_amd/sort.py: PIPE_SOURCE over io.sam.StreamReader): the text is
+"""sort_bam on an aligner's output that arrives through a pipe (svision_amd/sort_sources.py: PipeSource over io.sam.StreamReader): the text is
 seen ONCE -- measured and encoded chunk by chunk into a record stream that grows on the device, or, beyond the budget, spooled as an
 unsorted BAM beside the output -- and the two files written must be, byte for byte, those of the same bytes read from a regular file.
 The sets are the shuffled HiFi- and ONT-shaped ones of tests/test_gpu_sort_sam.py (a few hundred records) and the case list of

@@ -156,14 +156,14 @@ def test_a_text_that_changes_between_the_passes(sets, tmp_path, monkeypatch, spa
         cols[9], cols[10] = cols[9][:-1], cols[10][:-1]
         lines[k] = b"\t".join(cols)
     changed = b"\n".join(lines)
-    step = "_pieces_spanned" if spanned else "_sam_fill"
-    real = getattr(sort, step)
+    owner, step = (sort, "_pieces_spanned") if spanned else (sort.SamSource, "fill")
+    real = getattr(owner, step)
 
     def rewrite_then(*a, **kw):
         with open(path, "wb") as f:
             f.write(changed)
         return real(*a, **kw)
-    monkeypatch.setattr(sort, step, rewrite_then)
+    monkeypatch.setattr(owner, step, rewrite_then)
     before = sorted(os.listdir(str(tmp_path)))
     with pytest.raises(sort.SortWriteError, match="changed while it was sorted"):
         sort.sort_bam(path, str(tmp_path / "never.bam"), device=DEV, memory_bytes=s["room"] // 4 if spanned else None, range_bytes=50_000)

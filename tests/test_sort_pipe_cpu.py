@@ -1,6 +1,6 @@
 """The host pieces of the sort's one-pass road, without a GPU: the stream reader of svision_amd/io/sam.py on an ``os.pipe()`` that a
 thread feeds in writes of every size, the spool file over the BGZF writer with a zlib encoder and NumPy buffers (as
-tests/test_sort_steps_cpu.py runs the writer), and the growth rule of a pipe's record stream replayed over crafted chunk sizes.
+tests/test_sort_steps_cpu.py runs the writer), and the store of a pipe's records (sort.PipeStore) driven over crafted chunk sizes.
 Expected values come from the text itself, gzip, svision_amd.io.bam and tests/htslike.py."""
 import gzip
 import os
@@ -12,7 +12,7 @@ import pytest
 from svision_amd import index, sort
 from svision_amd.io import bam, sam
 from tests import htslike, samtext
-from tests.test_sort_steps_cpu import host_clock, zlib_encode
+from tests.test_sort_steps_cpu import HostClock, host_clock, zlib_encode
 
 REFS = [("chrA", 100_000), ("chrB", 50_000)]
 HEADER = samtext.header_text(REFS).encode()
@@ -260,35 +260,50 @@ def test_bam_bytes_are_copied_as_they_are(tmp_path):
 
 
 # ---- the growth rule ----
-def replay(chunks, budget):
-    """The rule as sort._pipe_key_pass and sort._pipe_fill apply it, on a ledger alone: a segment a kept chunk, the join at the end
-    -> (mode, the ledger, the totals after every step with the record bytes seen and the chunk at that step)."""
-    ledger, kept, seen, steps, spooled = sort.StreamLedger(), 0, 0, [], False
-    for c in chunks:
-        seen += c
-        if not spooled and not sort.keeps_in_core(kept, c, budget):
-            spooled = True
-            if kept:                                            # the kept records joined for the spool, then gone
-                ledger.add(kept + sort.STREAM_SLACK)
-                steps.append((ledger.now, seen - c, c))
-                ledger.drop(2 * kept + sort.STREAM_SLACK)
-            kept = 0
-        if not spooled:
-            ledger.add(c)
-            kept += c
-        steps.append((ledger.now, seen, c))
-    if not spooled:
-        ledger.add(kept + sort.STREAM_SLACK)
-        steps.append((ledger.now, seen, chunks[-1] if chunks else 0))
-    return "spooled" if spooled else "in_core", ledger, steps
+STORE_HEADER = sam.bam_header_bytes(sam.parse_header(HEADER))
+
+
+def drive(chunks, budget, out):
+    """sort.PipeStore itself over chunks of ``chunks`` bytes, chunk k filled with the byte value k % 251 + 1, as the key passes of a
+    pipe drive it -- admit, buffer, keep per chunk, then the spool's finish or the join into the stream --, handed NumPy buffers and
+    the zlib encoder -> (the store, the ledger's totals at every step with the record bytes seen and the chunk at that step, the
+    joined stream or None).  A total is taken at every allocation's first use: when a buffer was kept, and at every copy of a join."""
+    steps, at = [], {"seen": 0, "chunk": 0}
+    store = sort.PipeStore(out, budget, 2 * sort.BLOCK, HostClock(), "<stdin>")
+
+    def copy(dst, seg):
+        steps.append((store.ledger.now, at["seen"], at["chunk"]))
+        np.copyto(dst, seg)
+    store.on(lambda: STORE_HEADER, lambda n_bytes: np.empty(n_bytes, np.uint8), copy, zlib_encode, lambda b: np.frombuffer(b, np.uint8))
+    for k, c in enumerate(chunks):
+        at["chunk"] = c
+        store.admit(c)                                          # (a join for the spool is counted against the bytes seen before this chunk)
+        at["seen"] += c
+        buf = store.buffer(c)
+        assert buf.size == c + (sort.STREAM_SLACK if store.spool is not None else 0) and not buf[c:].any()
+        buf[:c] = k % 251 + 1
+        store.keep(buf, c)
+        del buf
+        steps.append((store.ledger.now, at["seen"], c))
+    store.finish()
+    stream = None
+    if store.mode == "in_core":
+        stream = np.zeros(sum(chunks) + sort.STREAM_SLACK, np.uint8)
+        store.fill(stream, 0)
+    return store, steps, stream
+
+
+def _chunk_bytes(chunks):
+    return b"".join(bytes([k % 251 + 1]) * c for k, c in enumerate(chunks))
 
 
 @pytest.mark.parametrize("chunks", [[100], [100] * 50, [1000, 10, 10, 5000, 36], [36] * 3 + [1 << 20], list(range(40, 4000, 37))],
                          ids=["one", "even", "mixed", "late_large", "rising"])
-def test_the_growth_rule_keeps_both_conditions(chunks):
-    total = sum(chunks)
+def test_the_growth_rule_keeps_both_conditions(chunks, tmp_path):
+    total, out = sum(chunks), str(tmp_path / "sorted.bam")
     for budget in (1, chunks[0] - 1, chunks[0], 2 * chunks[0] + 3, 2 * chunks[0] + 4, total, 2 * total + 3, 2 * total + 4, 1 << 40):
-        mode, ledger, steps = replay(chunks, budget)
+        store, steps, stream = drive(chunks, budget, out)
+        mode, ledger = store.mode, store.ledger
         assert mode == ("in_core" if 2 * total + sort.STREAM_SLACK <= budget else "spooled"), (budget, mode)
         for now, seen, chunk in steps:
             assert now <= budget or now == 0, (now, budget)                    # (a)
@@ -296,9 +311,30 @@ def test_the_growth_rule_keeps_both_conditions(chunks):
         assert ledger.peak == max(now for now, _seen, _chunk in steps)
         if mode == "in_core":
             assert ledger.peak == 2 * total + sort.STREAM_SLACK and ledger.grows == len(chunks) + 1
+            assert stream[:total].tobytes() == _chunk_bytes(chunks) and not stream[total:].any() and ledger.now == stream.size
+            assert store.spool_file is None and os.listdir(str(tmp_path)) == []
+        else:
+            assert store.spool_file == sort.spool_path(out) and store.spool_bytes == os.path.getsize(store.spool_file)
+            assert gzip.decompress(open(store.spool_file, "rb").read()) == STORE_HEADER + _chunk_bytes(chunks)
+        store.discard()
+        assert os.listdir(str(tmp_path)) == []
     # a budget smaller than the first chunk spools at once: nothing was ever kept
-    mode, ledger, _steps = replay(chunks, chunks[0] // 2)
-    assert mode == "spooled" and ledger.peak == 0
+    store, _steps, _stream = drive(chunks, chunks[0] // 2, out)
+    assert store.mode == "spooled" and store.ledger.peak == 0
+    store.discard()
+
+
+def test_a_chunk_refused_mid_way_spools_the_kept_records_first(tmp_path):
+    """Chunks of distinct byte values, a few hundred bytes each, and a budget that keeps the first three: the spool's inflated bytes are
+    the header, then every chunk's bytes in arrival order -- the kept ones, joined, in front of the one that was refused."""
+    chunks = [300, 410, 250, 520, 330, 280]
+    budget = 2 * sum(chunks[:3]) + sort.STREAM_SLACK
+    store, steps, stream = drive(chunks, budget, str(tmp_path / "sorted.bam"))
+    assert store.mode == "spooled" and stream is None and not store.segments
+    assert store.ledger.grows == 3 + 1 and store.ledger.peak == budget and store.ledger.now == 0     # three segments and their join for the spool
+    assert gzip.decompress(open(store.spool_file, "rb").read()) == STORE_HEADER + _chunk_bytes(chunks)
+    store.discard()
+    assert os.listdir(str(tmp_path)) == []
 
 
 def test_which_inputs_take_the_one_pass_road(tmp_path):

@@ -66,6 +66,16 @@ def host_clock():
     return index._Clock(None, None, sort.STAGES)                # (the writer laps without device work: no torch is touched)
 
 
+class HostClock(index._Clock):
+    """The clock of a step whose buffers are NumPy arrays: no lap has device work to wait for."""
+
+    def __init__(self):
+        index._Clock.__init__(self, None, None, sort.STAGES)
+
+    def lap(self, stage, device_work=True):
+        index._Clock.lap(self, stage, False)
+
+
 @pytest.mark.parametrize("mode", ["one", "two", "span"])
 @pytest.mark.parametrize("n_stream", [0, 1, BLOCK, BLOCK + 1, 3 * BLOCK + 7])
 @pytest.mark.parametrize("n_head", [100, BLOCK, BLOCK + 1])
@@ -301,3 +311,45 @@ def test_commit_modes_follow_the_umask(tmp_path):
     assert sorted(os.listdir(str(tmp_path))) == ["alone.bai", "sorted.bam", "sorted.bam.bai"]
     assert open(out, "rb").read() == b"the sorted file" and open(out + ".bai", "rb").read() == b"the index"
     assert all(os.stat(str(tmp_path / n)).st_mode & 0o777 == 0o640 for n in os.listdir(str(tmp_path)))
+
+
+# ---- the join: the run's arrays and every input's own ----
+def test_the_join_leaves_every_input_views_of_the_runs_offsets():
+    """Three inputs of 3 + 0 + 2 records (the first in two ranges, the second a range that completed nothing) through sort._join with
+    NumPy standing in for the device: the run's arrays are the inputs' end to end, and an input's pass holds no array of its own --
+    its offsets are views into the run's, at its first record's number -- and nothing of what the join took."""
+    from svision_amd import sort_sources
+    lens = [[np.asarray([40, 50], np.int64), np.asarray([60], np.int64)], [], [np.asarray([70, 80], np.int64)]]
+    records = [[2, 1], [0], [2]]
+    kp, ranges, first, value = sort.RunPass(), 0, 0, 0
+    for k, (own, n_recs) in enumerate(zip(lens, records)):
+        part = sort_sources.InputPass(kp.seen)
+        part.range_records, part.places, part.lens = list(n_recs), [(k, r) for r in range(len(n_recs))], own
+        for l in own:
+            v = np.arange(value, value + l.size, dtype=np.int32)
+            part.host.append((v, v + 100, (v + 200).astype(np.uint16), v + 300))
+            part.d_keys.append((v + 400, v + 500))
+            value += l.size
+        part.seen = int(sum(l.sum() for l in own))
+        kp.parts.append(sort.Part(sort_sources.Opened("input%d" % k, None, None, None, None, None), part, ranges, first))
+        kp.seen, ranges, first = kp.seen + part.seen, ranges + len(n_recs), first + sum(n_recs)
+    dv = sort._Dev(None, None, None, None, HostClock())
+    assert sort._join(dv, kp.parts[0].opened, kp, cat=np.concatenate, to_device=lambda a: a) is kp
+    assert kp.n == 5 and kp.range_records == [2, 1, 0, 2] and kp.places == [(0, 0), (0, 1), (1, 0), (2, 0)]
+    assert kp.off_in.tolist() == [0, 40, 90, 150, 220, 300] and kp.d_off_in is kp.off_in and kp.seen == 300
+    for i, name in enumerate(("tid", "pos", "flag", "span", "d_tid", "d_pos")):
+        assert getattr(kp, name).tolist() == [v + 100 * i for v in range(5)], name
+    assert kp.flag.dtype == np.uint16
+    for p, n, base in zip(kp.parts, (3, 0, 2), (0, 150, 150)):
+        part = p.part
+        assert part.n == n and part.base == base and (part.host, part.d_keys, part.lens) == ([], [], [])
+        assert part.off_in.tolist() == kp.off_in[p.first_record:p.first_record + n + 1].tolist() and part.off_in[0] == base
+        for own in (part.off_in, part.d_off_in):                # a view at the right record, not a copy
+            assert own.base is kp.off_in and own.size == n + 1
+            assert own.__array_interface__["data"][0] == kp.off_in.__array_interface__["data"][0] + 8 * p.first_record
+    # no record at all: empty arrays of the right types, one offset
+    empty = sort.RunPass()
+    empty.parts.append(sort.Part(kp.parts[0].opened, sort_sources.InputPass(), 0, 0))
+    sort._join(dv, kp.parts[0].opened, empty, cat=np.concatenate, to_device=lambda a: a)
+    assert empty.n == 0 and empty.off_in.tolist() == [0] and empty.d_tid.dtype == np.int32 and empty.flag.dtype == np.uint16
+    assert empty.parts[0].part.off_in.tolist() == [0]
