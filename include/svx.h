@@ -498,6 +498,29 @@ int            svx_bam_walk_offsets(const uint8_t* d_raw, const uint64_t* d_star
  *                       NULL): the records' sort keys, translated by the same rule.  A lane per record in a grid-stride loop,
  *                       byte loads and stores: only bytes 4..7 and 24..27 of a record are touched, nothing is read behind
  *                       d_off[n - 1] + 28.  n = 0 launches nothing; n_in = 0: every field other than -1 is reported
+ *   svx_record_retag_measure / svx_record_retag_write   the value of a record's RG:Z and PG:Z field replaced through a table
+ *                       (svision_amd/sort.py under retag: the @RG / @PG IDs of several inputs that collide were renamed in the
+ *                       merged header, and the records follow).  Record r = the bytes d_bytes[d_off[r] .. d_off[r + 1]), d_off
+ *                       [n + 1], at any byte offset.  The table: m entries, entry e = a 2-byte tag, the old value and the new
+ *                       one packed in d_table with the int32 offsets d_table_off [2m + 1]: the tag at d_table_off[2e], the old
+ *                       value behind it up to d_table_off[2e + 1], the new one from there up to d_table_off[2e + 2]; values
+ *                       carry no NUL; only entries of the tags RG and PG are looked for.  A wave per record walks the optional
+ *                       fields behind qual (l_read_name, n_cigar_op and l_seq of the fixed part say where): A c C 1 byte, s S 2,
+ *                       i I f 4, Z H up to their NUL (found 64 bytes a ballot), B = subtype + uint32 count + count elements,
+ *                       skipped in one step.  The FIRST RG field of type Z whose value equals an RG entry's old value -- same
+ *                       length, same bytes -- takes that entry's new value, and likewise PG; a field of the tag with another
+ *                       type or a value the table does not hold is left alone, and so is everything else, byte for byte and in
+ *                       order.  block_size becomes the new length - 4.  measure: d_new_len[r] (int64) = the new length.  write:
+ *                       exactly that many bytes at d_dst + d_new_off[r], d_new_off [n + 1] the exclusive sum of d_new_len, in
+ *                       up to five copies (prefix, value, middle, value, rest) by the scatter's copy routine; nothing else of
+ *                       d_dst is written.  A MALFORMED record -- shorter than 36 bytes, block_size + 4 not its extent, name +
+ *                       CIGAR + seq + qual longer than it, a field header cut by its end, an unknown type or B subtype, a value
+ *                       or a B array past the end, a Z / H without NUL -- keeps its length, is copied as it is, and d_status[0] is
+ *                       set to 1 (a plain store of the one value; the caller zeroes it); write also sets it, and copies
+ *                       nothing of that record, where d_new_off does not give a record the length measure computes.  measure
+ *                       reads the records byte by byte and nothing outside d_bytes[d_off[0] .. d_off[n]); write reads d_bytes
+ *                       and d_table in aligned dwords as svx_record_scatter_segments reads d_src: both 4-byte aligned and
+ *                       readable up to the next multiple of 4 behind their last byte.  n = 0 or m = 0 launches nothing
  * No atomics in any of them: the output is a pure function of the input.  n = 0 is fine everywhere (d_off_out[0] = 0). */
 #define SVX_RECORD_SORT_TILE 2048u
 size_t         svx_record_sort_ws_bytes(uint32_t n);
@@ -515,6 +538,10 @@ int            svx_record_scatter_segments(const void* d_src, const int64_t* d_s
                                            int32_t* d_status, void* stream);
 int            svx_record_retid(void* d_bytes, const int64_t* d_off, uint32_t n, const int32_t* d_map, int32_t n_in, int32_t* d_tid_key,
                                 int32_t* d_status, void* stream);
+int            svx_record_retag_measure(const void* d_bytes, const int64_t* d_off, uint32_t n, const void* d_table, const int32_t* d_table_off,
+                                        int32_t m, int64_t* d_new_len, int32_t* d_status, void* stream);
+int            svx_record_retag_write(const void* d_bytes, const int64_t* d_off, uint32_t n, const void* d_table, const int32_t* d_table_off,
+                                      int32_t m, const int64_t* d_new_off, void* d_dst, int32_t* d_status, void* stream);
 /* BGZF members FROM inflated bytes (svx_deflate.hip; ABI 420, additive): the encoder of svision_amd/sort.py, which writes the
  * device-sorted BAM.
  *   svx_bgzf_deflate    block b = the bytes d_in[d_in_off[b] .. d_in_off[b + 1]) -- any offsets, no alignment, 0 .. 0xFF00 bytes a block --

@@ -28,6 +28,9 @@
 //                               svx_recsort_core.hpp (the gather's alignment rule); the other waves leave at once
 //   svx_record_retid            a LANE per record rewrites its refID and next_refID through a table (several inputs merged into one
 //                               file, svision_amd/sort.py: each input's indices into the merged dictionary), byte by byte in place
+//   svx_record_retag_measure    a WAVE per record walks the optional fields behind qual and finds the first RG:Z / PG:Z value that a
+//   svx_record_retag_write      table renames (the IDs of several inputs that collide, svision_amd/sort.py): the new length, then the
+//                               record with the value replaced and block_size set, in up to five copies (svx_recsort_core.hpp)
 // No atomics, no cross-workgroup dependency inside a launch: the output is a pure function of the input, identical in every run.
 // A counter in LDS is written by ONE lane a round (the leader of its digit, in the wave's own row) with a barrier behind it.
 #include <hip/hip_runtime.h>
@@ -342,6 +345,27 @@ void record_retid_kernel(uint8_t* __restrict__ bytes, const int64_t* __restrict_
         svx_recsort::retid_record(bytes, off, map, n_in, tid_key, r, status);
 }
 
+// A wave per record (svx_recsort_core.hpp): the field chain is followed by every lane alike, a Z / H value's NUL is found 64 bytes a
+// ballot, a B array is skipped from its count.  Long-read records carry arrays of tens of kilobytes; a lane per record would walk
+// them alone.
+__global__ __launch_bounds__(WAVE * SEG_WAVES)
+void record_retag_measure_kernel(const uint8_t* __restrict__ bytes, const int64_t* __restrict__ off, uint32_t n, svx_recsort::RetagTable table,
+                                 int64_t* __restrict__ new_len, int32_t* __restrict__ status)
+{
+    const uint64_t r = (uint64_t)blockIdx.x * SEG_WAVES + (threadIdx.x >> 6);
+    if (r >= n) return;                                         // (whole waves: no barrier in this kernel)
+    svx_recsort::retag_measure_record(bytes, off, table, new_len, r, threadIdx.x & 63u, status);
+}
+
+__global__ __launch_bounds__(WAVE * SEG_WAVES)
+void record_retag_write_kernel(const uint8_t* __restrict__ bytes, const int64_t* __restrict__ off, uint32_t n, svx_recsort::RetagTable table,
+                               const int64_t* __restrict__ new_off, uint8_t* __restrict__ dst, int32_t* __restrict__ status)
+{
+    const uint64_t r = (uint64_t)blockIdx.x * SEG_WAVES + (threadIdx.x >> 6);
+    if (r >= n) return;
+    svx_recsort::retag_write_record(bytes, off, table, new_off, dst, r, threadIdx.x & 63u, status);
+}
+
 struct SortWs {
     uint64_t* key[2];
     uint32_t* idx;
@@ -481,5 +505,32 @@ extern "C" int svx_record_retid(void* d_bytes, const int64_t* d_off, uint32_t n,
     const uint64_t blocks = ((uint64_t)n + 255) / 256;
     hipLaunchKernelGGL(record_retid_kernel, dim3((uint32_t)(blocks < RETID_MAX_BLOCKS ? blocks : RETID_MAX_BLOCKS)), dim3(256), 0,
                        static_cast<hipStream_t>(stream), static_cast<uint8_t*>(d_bytes), d_off, n, d_map, n_in, d_tid_key, d_status);
+    return hipGetLastError() == hipSuccess ? SVX_OK : SVX_ELAUNCH;
+}
+
+extern "C" int svx_record_retag_measure(const void* d_bytes, const int64_t* d_off, uint32_t n, const void* d_table, const int32_t* d_table_off,
+                                        int32_t m, int64_t* d_new_len, int32_t* d_status, void* stream)
+{
+    if (m < 0) return SVX_EINVAL;
+    if (n == 0 || m == 0) return SVX_OK;
+    if (!d_bytes || !d_off || !d_table || !d_table_off || !d_new_len || !d_status) return SVX_EINVAL;
+    const svx_recsort::RetagTable table{static_cast<const uint8_t*>(d_table), d_table_off, m};
+    const dim3 grid((uint32_t)(((uint64_t)n + SEG_WAVES - 1) / SEG_WAVES));
+    hipLaunchKernelGGL(record_retag_measure_kernel, grid, dim3(WAVE * SEG_WAVES), 0, static_cast<hipStream_t>(stream),
+                       static_cast<const uint8_t*>(d_bytes), d_off, n, table, d_new_len, d_status);
+    return hipGetLastError() == hipSuccess ? SVX_OK : SVX_ELAUNCH;
+}
+
+extern "C" int svx_record_retag_write(const void* d_bytes, const int64_t* d_off, uint32_t n, const void* d_table, const int32_t* d_table_off,
+                                      int32_t m, const int64_t* d_new_off, void* d_dst, int32_t* d_status, void* stream)
+{
+    if (m < 0) return SVX_EINVAL;
+    if (n == 0 || m == 0) return SVX_OK;
+    if (!d_bytes || !d_off || !d_table || !d_table_off || !d_new_off || !d_dst || !d_status) return SVX_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(d_bytes) | reinterpret_cast<uintptr_t>(d_table)) & 3u) return SVX_EINVAL;
+    const svx_recsort::RetagTable table{static_cast<const uint8_t*>(d_table), d_table_off, m};
+    const dim3 grid((uint32_t)(((uint64_t)n + SEG_WAVES - 1) / SEG_WAVES));
+    hipLaunchKernelGGL(record_retag_write_kernel, grid, dim3(WAVE * SEG_WAVES), 0, static_cast<hipStream_t>(stream),
+                       static_cast<const uint8_t*>(d_bytes), d_off, n, table, d_new_off, static_cast<uint8_t*>(d_dst), d_status);
     return hipGetLastError() == hipSuccess ? SVX_OK : SVX_ELAUNCH;
 }

@@ -1,6 +1,6 @@
-// svx_recsort_core.hpp -- a lane's share of scatter_segments_kernel and of record_retid_kernel (svx_recsort.hip), host- and
-// device-compilable: the host programs tools/hostwave/scatter_main.cpp and retid_main.cpp run this very code, lane by lane, under
-// AddressSanitizer.
+// svx_recsort_core.hpp -- a lane's share of scatter_segments_kernel, of record_retid_kernel and of the two record_retag kernels
+// (svx_recsort.hip), host- and device-compilable: the host programs tools/hostwave/scatter_main.cpp, retid_main.cpp and
+// retag_main.cpp run this very code, lane by lane, under AddressSanitizer.
 //
 // A wave of 64 lanes copies one segment.  The DESTINATION decides the alignment, as in gather_segments_kernel: single bytes up to
 // its first dword boundary, whole dwords -- each assembled from the one or two aligned source dwords that hold its bytes --,
@@ -97,6 +97,185 @@ SVX_RS_HD void retid_record(uint8_t* bytes, const int64_t* off, const int32_t* m
         if (retid_value(tid_key[r], map, n_in, &key)) tid_key[r] = key;
         else *status = 1;
     }
+}
+
+// ---- record_retag_measure_kernel's and record_retag_write_kernel's share of one record (tools/hostwave/retag_main.cpp) ----
+// A WAVE per record.  The optional fields behind qual are a chain: every lane follows it with the same loads and takes the same
+// turns; only the search for the NUL of a Z / H value is shared out, 64 bytes a step, and only the copies of retag_write.
+//
+// The table: m entries, entry e = a 2-byte tag, an old value and a new one, packed in `bytes` with 2m + 1 offsets:
+// tag = bytes[off[2e]], bytes[off[2e] + 1]; old = bytes[off[2e] + 2 .. off[2e + 1]); new = bytes[off[2e + 1] .. off[2e + 2]).
+// Values carry no NUL.  Only the tags RG and PG are looked for.
+struct RetagTable {
+    const uint8_t* bytes;
+    const int32_t* off;
+    int32_t m;
+};
+
+// What a record needs: `n` replacements (0 .. 2) in the order they lie in the record -- the value at bytes [at, at + old_len) of
+// the record becomes table entry `entry`'s new value --, the record's new length, and whether the record is malformed (then n = 0
+// and new_len is the old length).  The same in every lane.
+struct RetagPlan {
+    uint32_t n;
+    uint64_t at[2], old_len[2];
+    int32_t entry[2];
+    uint64_t new_len;
+    bool bad;
+};
+
+// The bits of the lanes l < count whose byte p[l] is 0 (count <= 64); on the host a loop over the lanes.
+SVX_RS_HD uint64_t ballot_nul(const uint8_t* p, uint64_t count, uint32_t lane)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __ballot(lane < count && p[lane] == 0);
+#else
+    (void)lane;
+    uint64_t mask = 0;
+    for (uint32_t l = 0; l < WAVE; ++l)
+        if (l < count && p[l] == 0) mask |= 1ull << l;
+    return mask;
+#endif
+}
+
+SVX_RS_HD uint32_t lowest_bit(uint64_t mask)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return (uint32_t)__ffsll((unsigned long long)mask) - 1u;
+#else
+    uint32_t b = 0;
+    while (!(mask & 1)) { mask >>= 1; ++b; }
+    return b;
+#endif
+}
+
+// 1, 2, 4: the bytes of a value of type t (A c C, s S, i I f); 0: no fixed-size type.
+SVX_RS_HD uint32_t retag_fixed_size(uint8_t t)
+{
+    if (t == 'A' || t == 'c' || t == 'C') return 1;
+    if (t == 's' || t == 'S') return 2;
+    if (t == 'i' || t == 'I' || t == 'f') return 4;
+    return 0;
+}
+
+// The entry whose tag is (t0, t1) and whose old value is value[0 .. len), or -1.
+SVX_RS_HD int32_t retag_lookup(const RetagTable& tb, uint8_t t0, uint8_t t1, const uint8_t* value, uint64_t len)
+{
+    for (int32_t e = 0; e < tb.m; ++e) {
+        const uint8_t* ent = tb.bytes + tb.off[2 * e];
+        if (ent[0] != t0 || ent[1] != t1 || (uint64_t)(tb.off[2 * e + 1] - tb.off[2 * e] - 2) != len) continue;
+        uint64_t k = 0;
+        while (k < len && ent[2 + k] == value[k]) ++k;
+        if (k == len) return e;
+    }
+    return -1;
+}
+
+// The plan of the record rec[0 .. len): nothing outside those bytes is read, byte by byte.  Malformed: shorter than 36 bytes,
+// block_size + 4 != len, the fixed part with name, CIGAR, seq and qual longer than the record, a field header cut by the end, an
+// unknown type or B subtype, a value or a B array past the end, a Z / H without NUL.
+SVX_RS_HD RetagPlan retag_plan(const uint8_t* rec, int64_t len, const RetagTable& tb, uint32_t lane)
+{
+    RetagPlan plan;
+    plan.n = 0;
+    plan.new_len = len < 0 ? 0 : (uint64_t)len;
+    plan.bad = true;
+    plan.at[0] = plan.at[1] = plan.old_len[0] = plan.old_len[1] = 0;
+    plan.entry[0] = plan.entry[1] = -1;
+    if (len < 36 || (int64_t)load_le32(rec) + 4 != len) return plan;
+    const uint64_t end = (uint64_t)len;
+    const uint64_t l_name = rec[12], n_cigar = (uint64_t)rec[16] | (uint64_t)rec[17] << 8, l_seq = (uint32_t)load_le32(rec + 20);
+    uint64_t p = 36 + l_name + 4 * n_cigar + (l_seq + 1) / 2 + l_seq;
+    if (p > end) return plan;
+    bool done_rg = false, done_pg = false;
+    uint32_t n = 0;
+    int64_t grow = 0;
+    while (p < end) {
+        if (p + 3 > end) return plan;
+        const uint8_t t0 = rec[p], t1 = rec[p + 1], type = rec[p + 2];
+        const uint64_t v = p + 3;
+        const uint32_t fixed = retag_fixed_size(type);
+        if (fixed) {
+            if (v + fixed > end) return plan;
+            p = v + fixed;
+        } else if (type == 'Z' || type == 'H') {
+            uint64_t nul = end;
+            for (uint64_t q = v; q < end; q += WAVE) {          // 64 bytes a step: the lowest lane that holds a NUL
+                const uint64_t mask = ballot_nul(rec + q, end - q < WAVE ? end - q : WAVE, lane);
+                if (mask) { nul = q + lowest_bit(mask); break; }
+            }
+            if (nul == end) return plan;
+            const bool rg = t0 == 'R' && t1 == 'G', pg = t0 == 'P' && t1 == 'G';
+            if (type == 'Z' && ((rg && !done_rg) || (pg && !done_pg))) {
+                const int32_t e = retag_lookup(tb, t0, t1, rec + v, nul - v);
+                if (e >= 0) {
+                    plan.at[n] = v; plan.old_len[n] = nul - v; plan.entry[n] = e;
+                    grow += (int64_t)(tb.off[2 * e + 2] - tb.off[2 * e + 1]) - (int64_t)(nul - v);
+                    ++n;
+                    if (rg) done_rg = true; else done_pg = true;
+                }
+            }
+            p = nul + 1;
+        } else if (type == 'B') {
+            if (v + 5 > end) return plan;
+            const uint32_t elem = retag_fixed_size(rec[v]);
+            if (!elem || rec[v] == 'A') return plan;
+            const uint64_t count = (uint32_t)load_le32(rec + v + 1);
+            if (count * elem > end - (v + 5)) return plan;
+            p = v + 5 + count * elem;                           // skipped in one step from its count
+        } else {
+            return plan;
+        }
+    }
+    plan.n = n;
+    plan.new_len = (uint64_t)((int64_t)end + grow);
+    plan.bad = false;
+    return plan;
+}
+
+// Lane `lane` of the wave of record r, measure: new_len[r] = the record's length with its values replaced; a malformed record keeps
+// its length and sets *status (a plain store of the one value).
+SVX_RS_HD void retag_measure_record(const uint8_t* bytes, const int64_t* off, const RetagTable& tb, int64_t* new_len, uint64_t r, uint32_t lane,
+                                    int32_t* status)
+{
+    const RetagPlan plan = retag_plan(bytes + off[r], off[r + 1] - off[r], tb, lane);
+    if (lane == 0) {
+        new_len[r] = (int64_t)plan.new_len;
+        if (plan.bad) *status = 1;
+    }
+}
+
+// Lane `lane` of the wave of record r, write: the record with its values replaced and its block_size set goes to
+// dst[new_off[r] .. new_off[r + 1]), in up to five pieces (copy_segment: any skew of source and destination); a malformed record
+// is copied as it is and sets *status.  Where new_off does not give the record the length of its plan, nothing is written and
+// *status is set.  The table's bytes are read like a record's: in the aligned dwords that hold a value.
+SVX_RS_HD void retag_write_record(const uint8_t* bytes, const int64_t* off, const RetagTable& tb, const int64_t* new_off, uint8_t* dst, uint64_t r,
+                                  uint32_t lane, int32_t* status)
+{
+    const uint8_t* rec = bytes + off[r];
+    const int64_t len = off[r + 1] - off[r];
+    const RetagPlan plan = retag_plan(rec, len, tb, lane);
+    if (plan.bad && lane == 0) *status = 1;
+    if (new_off[r + 1] - new_off[r] != (int64_t)plan.new_len) {
+        if (lane == 0) *status = 1;
+        return;
+    }
+    uint8_t* out = dst + new_off[r];
+    if (plan.n == 0) {
+        copy_segment(rec, out, plan.new_len, lane);
+        return;
+    }
+    if (lane < 4) out[lane] = (uint8_t)((uint32_t)(plan.new_len - 4) >> (8 * lane));        // block_size
+    uint64_t from = 4, to = 4;
+    for (uint32_t k = 0; k < plan.n; ++k) {
+        const int32_t e = plan.entry[k];
+        const uint64_t value_len = (uint64_t)(tb.off[2 * e + 2] - tb.off[2 * e + 1]);
+        copy_segment(rec + from, out + to, plan.at[k] - from, lane);
+        to += plan.at[k] - from;
+        copy_segment(tb.bytes + tb.off[2 * e + 1], out + to, value_len, lane);
+        to += value_len;
+        from = plan.at[k] + plan.old_len[k];
+    }
+    copy_segment(rec + from, out + to, (uint64_t)len - from, lane);
 }
 
 }  // namespace svx_recsort

@@ -929,6 +929,81 @@ def record_retid(d_bytes, d_off, d_map, d_tid_key, status):
     return d_bytes
 
 
+RetagTable = collections.namedtuple("RetagTable", "d_bytes d_off m")
+
+
+def retag_pack(renames):
+    """{(tag, old): new} -- tag "RG" / "PG" or its bytes, the values bytes -- -> (uint8 bytes, int32 offsets [2m + 1], m) as
+    svx_record_retag_measure takes them, on the host: per entry the tag, the old value, the new one, in the mapping's order."""
+    flat, off = bytearray(), [0]
+    for (tag, old), new in renames.items():
+        tag = tag.encode("latin-1") if isinstance(tag, str) else bytes(tag)
+        old, new = bytes(old), bytes(new)
+        if len(tag) != 2 or b"\0" in old or b"\0" in new:
+            raise _lib.SvxError("a rename is a 2-byte tag and two values without NUL: %r" % ((tag, old, new),))
+        flat += tag + old
+        off.append(len(flat))
+        flat += new
+        off.append(len(flat))
+    if len(flat) > 0x7FFFFFFF:
+        raise _lib.SvxError("the renames' bytes exceed 2^31 - 1")
+    return np.frombuffer(bytes(flat) or b"\0", np.uint8), np.asarray(off, np.int32), len(renames)
+
+
+def retag_table(renames, device):
+    """:func:`retag_pack` on the device -> RetagTable."""
+    flat, off, m = retag_pack(renames)
+    return RetagTable(torch.from_numpy(flat.copy()).to(device), torch.from_numpy(off).to(device), m)
+
+
+def _require_retag(d_bytes, d_off, table, status):
+    for t, name in ((d_bytes, "d_bytes"), (d_off, "d_off"), (table.d_bytes, "table.d_bytes"), (table.d_off, "table.d_off"), (status, "status")):
+        _require_cuda(t, name)
+    if d_bytes.dtype != torch.uint8 or d_off.dtype != torch.int64 or d_off.dim() != 1 or d_off.shape[0] < 1 or status.dtype != torch.int32 \
+            or status.numel() < 1:
+        raise _lib.SvxError("d_bytes must be uint8, d_off int64 [n + 1], status int32 [1]")
+    if table.d_bytes.dtype != torch.uint8 or table.d_off.dtype != torch.int32 or table.d_off.dim() != 1 or table.d_off.shape[0] != 2 * table.m + 1:
+        raise _lib.SvxError("a table is uint8 bytes and int32 offsets [2m + 1]")
+    n = int(d_off.shape[0]) - 1
+    if n > 0xFFFFFFFF:
+        raise _lib.SvxError("svx_record_retag takes up to 2^32 - 1 records")
+    return n
+
+
+def record_retag_measure(d_bytes, d_off, table, status):
+    """The n BAM records d_bytes[d_off[r]:d_off[r + 1]] (uint8; int64 [n + 1], any byte offsets) -> int64 [n]: every record's length
+    once the first RG:Z and the first PG:Z value that ``table`` (:func:`retag_table`) renames are replaced.  ``status``: int32 [1],
+    set to 1 where a record is malformed (it keeps its length).  An empty table: the lengths as they are, no launch.
+    See include/svx.h svx_record_retag_measure."""
+    lib = _lib.load()
+    n = _require_retag(d_bytes, d_off, table, status)
+    if table.m == 0:
+        return d_off[1:] - d_off[:-1]
+    d_new_len = torch.empty(n, dtype=torch.int64, device=d_bytes.device)
+    _lib.check(lib.svx_record_retag_measure(d_bytes.data_ptr(), d_off.data_ptr(), n, table.d_bytes.data_ptr(), table.d_off.data_ptr(), table.m,
+                                            d_new_len.data_ptr(), status.data_ptr(), _stream_ptr(d_bytes.device)), "svx_record_retag_measure")
+    return d_new_len
+
+
+def record_retag_write(d_bytes, d_off, table, d_new_off, out, status):
+    """The records of :func:`record_retag_measure` rewritten -> ``out`` (uint8), record r at byte d_new_off[r] (int64 [n + 1], the
+    exclusive sum of measure's lengths; ``out`` holds at least d_new_off[n] bytes, nothing else of it is written), block_size set.
+    ``status``: set to 1 where a record is malformed (copied as it is) or d_new_off gives it another length than measure (not
+    copied).  ``d_bytes``: readable up to the next multiple of 4 bytes behind its end.  See include/svx.h svx_record_retag_write."""
+    lib = _lib.load()
+    n = _require_retag(d_bytes, d_off, table, status)
+    for t, name in ((d_new_off, "d_new_off"), (out, "out")):
+        _require_cuda(t, name)
+    if d_new_off.dtype != torch.int64 or d_new_off.shape != d_off.shape or out.dtype != torch.uint8 or out.dim() != 1:
+        raise _lib.SvxError("d_new_off must be int64 [n + 1], out uint8")
+    if table.m == 0:
+        raise _lib.SvxError("svx_record_retag_write: an empty table rewrites nothing")
+    _lib.check(lib.svx_record_retag_write(d_bytes.data_ptr(), d_off.data_ptr(), n, table.d_bytes.data_ptr(), table.d_off.data_ptr(), table.m,
+                                          d_new_off.data_ptr(), out.data_ptr(), status.data_ptr(), _stream_ptr(d_bytes.device)),
+               "svx_record_retag_write")
+    return out
+
+
 # ---- BGZF members from inflated bytes (svx_deflate.hip; the writer: svision_amd/sort.py) ----
 BGZF_SLOT = 65536                    # SVX_BGZF_SLOT: bytes of a member's slot in svx_bgzf_deflate's output
 BGZF_BLOCK_MAX = 0xFF00              # SVX_BGZF_BLOCK_MAX: the largest block the encoder takes (htslib's block size)

@@ -52,6 +52,9 @@ the stability of the one svx_record_sort over the inputs' keys end to end.
             renumbered where its records lie, SAM text is measured against the merged names (sort_sources.BamSource, SamSource)
   join      ranges, keys and offsets of all inputs end to end: ``ranges`` and ``range_records`` of the statistics run over all of them
   spans     a span's ranges are read again input by input (the source's ``again``), a BAM's records translated again before the scatter
+  retag     (``retag``, off by default) @RG / @PG IDs that collide are renamed in the merged header and the RG:Z / PG:Z values of that
+            input's records rewritten, a wave a record (sort_sources._retag); its record bytes are then known only behind its key
+            pass, so the run takes the road of a mixed run below and reads its BAM inputs twice
   room      all inputs BAM: the sum of their ISIZE-derived rooms is known before the passes, the stream is allocated once, as for one
             file.  With SAM text among them the records' bytes are known only behind the key passes; they keep no byte, and a run
             that fits then fills the stream input by input (the source's ``fill``; :func:`_key_passes`)
@@ -82,7 +85,7 @@ from .textin import DEFAULT_SAM_CHUNK_BYTES, SAM_READ_THREADS, input_paths, is_s
 
 TABLES = ("fixed", "dynamic")                                   # the encoder: svx_bgzf_deflate / svx_bgzf_deflate_dyn
 STAGES = ("read", "upload", "inflate", "crc", "find_starts", "walk", "scan", "read_back", "keep", "join", "sort", "gather", "scatter", "deflate",
-          "pack", "download", "write", "index", "lines", "measure", "encode", "host_lines", "retid", "spool")
+          "pack", "download", "write", "index", "lines", "measure", "encode", "host_lines", "retid", "spool", "retag")
 
 
 # ---- the plan of a sort in spans (host, NumPy) ----
@@ -164,7 +167,10 @@ class RunPass:
 def _open_all(paths, dv=None, run=None):
     """open, every input: -> Inputs.  One input: as it is opened.  Several: the headers merged (:func:`merge_headers`) -- a SAM part
     takes the merged dictionary for its own, so its records are encoded in the merged numbering and a part without header is
-    usable; a BAM part whose table is not the identity carries it as ``remap`` --, ``room`` the sum where every part's is known."""
+    usable; a BAM part whose table is not the identity carries it as ``remap`` --, ``room`` the sum where every part's is known.
+    Under ``run.retag`` a BAM part whose @RG / @PG IDs were renamed carries its table as ``retag``: its records change their length, so
+    the run's ``room`` is None -- the road of a mixed BAM + SAM run; the part's own ``room`` stays its ISIZE sum, for the check of the
+    bytes as read.  A part read as text that would need a rename is refused."""
     from .io import sam
     if paths.count("-") > 1:
         raise SortWriteError("%s is named twice: standard input is one stream" % sam.STREAM_NAME)
@@ -172,7 +178,14 @@ def _open_all(paths, dv=None, run=None):
         opened = _open(paths[0], run=run)
         return Inputs([opened], opened, opened.path if opened.pipe is None else opened.pipe.name)
     opened = [_open(p, alone=False, run=run) for p in paths]
-    merged = merge_headers([(o.path, o.head.text if o.source.from_text else o.head.header_text, o.head.references, o.head.lengths) for o in opened])
+    merged = merge_headers([(o.path, o.head.text if o.source.from_text else o.head.header_text, o.head.references, o.head.lengths) for o in opened],
+                           retag=bool(run is not None and run.retag))
+    for o, table in zip(opened, merged.renames):
+        if table and o.source.from_text:                        # (before a pipe among them is spooled)
+            (tag, old), new = next(iter(table.items()))
+            raise SortWriteError("%s: its @%s ID %s is on another line in an earlier input and would become %s, but the input is read as SAM "
+                                 "text, whose records' %s:Z tags are not rewritten -- list %s first: the first input to bring an ID keeps "
+                                 "it (or convert it to BAM)" % (o.path, tag, old.decode("latin-1"), new.decode("latin-1"), tag, o.path))
     header = sam.bam_header_bytes(sam.SamHead(merged.references, merged.lengths, merged.text, "coordinate"))
     for i, o in enumerate(opened):
         if o.source.from_text:                                  # text: measured and encoded against the merged names
@@ -180,8 +193,11 @@ def _open_all(paths, dv=None, run=None):
             if o.source.reads_once:                             # a pipe among several: spooled from its first byte, under the merged header
                 opened[i] = _pipe_spooled(dv, o, header)
         elif not np.array_equal(merged.maps[i], np.arange(len(merged.maps[i]))):       # (a dictionary that opens the merged one: nothing to rewrite)
-            opened[i] = o._replace(remap=merged.maps[i])
-    rooms = [o.room for o in opened]
+            opened[i] = o = o._replace(remap=merged.maps[i])
+        if merged.renames[i]:                                   # (a BAM: text was refused above)
+            opened[i] = o._replace(retag=merged.renames[i])
+    # an input whose records are rewritten has its record bytes only behind its key pass: the run's room is not known before
+    rooms = [None if o.retag else o.room for o in opened]
     label = "%s (+ %d more)" % (paths[0], len(paths) - 1)
     return Inputs(opened, Opened(label, MergedHead(merged.references, merged.lengths), None, header,
                                  None if None in rooms else sum(rooms), None), label)
@@ -376,7 +392,8 @@ def _stats(stats, opened, kp, od, written, counts, pipes, budget, clock):
     if pipes:
         # ``pipe``: the first input that was read once; ``pipes``: every one of them, in list order, with its name
         stats.update(pipe=pipes[0].stats(), pipes=[dict(pipe.stats(), name=pipe.name) for pipe in pipes])
-    stats.update(inputs=len(kp.parts), input_records=[p.part.n for p in kp.parts], retid_inputs=sum(p.opened.remap is not None for p in kp.parts))
+    stats.update(inputs=len(kp.parts), input_records=[p.part.n for p in kp.parts], retid_inputs=sum(p.opened.remap is not None for p in kp.parts),
+                 retag_inputs=sum(p.opened.retag is not None for p in kp.parts), retag_records=sum(getattr(p.part, "retag_records", 0) for p in kp.parts))
     stats.update(ranges=len(kp.range_records), records=kp.n, blocks=written.blocks, stored_blocks=written.stored_blocks,
                  dynamic_blocks=written.dynamic_blocks, chunks=written.chunks, spans=od.spans, span_range_reads=counts["span_range_reads"],
                  range_records=kp.range_records, stream_bytes=max([od.stream_bytes] + [pipe.store.ledger.peak for pipe in pipes]), memory_bytes=budget,
@@ -386,7 +403,7 @@ def _stats(stats, opened, kp, od, written, counts, pipes, budget, clock):
 
 
 def sort_bam(bam_path, out_path, device="cuda", range_bytes=None, chunk_bytes=None, stats=None, tables="fixed", memory_bytes=None,
-             index_format="bai", pipe_bam=None):
+             index_format="bai", pipe_bam=None, retag=None):
     """Write the records of ``bam_path`` in coordinate order to ``out_path`` and its index to ``out_path + ".bai"`` (see the head of the
     module); returns ``out_path``.  ``index_format="csi"``: the index is ``out_path + ".csi"`` and no ``.bai`` is written -- the sorted file's
     bytes are the same.  Under "bai" a record that reaches position 2^29 is refused (SortWriteError, neither file written): a ``.bai``
@@ -412,7 +429,14 @@ def sort_bam(bam_path, out_path, device="cuda", range_bytes=None, chunk_bytes=No
     stream in as a path (/dev/fd/N of a duplicate) instead, whose descriptor is the call's own.  ``pipe_bam``: what becomes of a BAM
     that arrives on a pipe -- "spool" (the default): copied as it is into a file beside the output and sorted from there; "stream": a
     lone such pipe is taken in one pass, ``range_bytes`` compressed bytes a chunk (default textin.DEFAULT_PIPE_BAM_BYTES), and
-    ``stats["pipe"]`` has mode "in_core" or "spooled", holds="bam" and compressed_bytes; None: ``SVX_PIPE_BAM`` of the environment."""
+    ``stats["pipe"]`` has mode "in_core" or "spooled", holds="bam" and compressed_bytes; None: ``SVX_PIPE_BAM`` of the environment.
+    ``retag``: several inputs whose @RG or @PG IDs collide -- the same ID on different lines -- are merged as ``samtools merge`` does it:
+    the later input's ID becomes ID-<1-based input number> in the header (sort_header.merge_headers) and the RG:Z / PG:Z values of
+    that input's records are rewritten on the device (svx_record_retag_measure / svx_record_retag_write); such an input must be read
+    as BAM -- SAM text that would need it is refused --, and the run reads its BAM inputs twice.  Off (the default), a colliding @RG is
+    refused and a colliding @PG renamed in the header only.  None: ``SVX_SORT_RETAG=1`` of the environment turns it on.  stats:
+    retag_inputs (the inputs with a table), retag_records (the records whose bytes changed); both 0, and seconds["retag"] 0.0, where
+    nothing is renamed."""
     from . import kernels
     paths = input_paths(bam_path)
     torch, lib, dev, clock = index.on_device("sort_bam needs the GPU (svx_record_sort, svx_bgzf_deflate)", device, STAGES)
@@ -421,6 +445,7 @@ def sort_bam(bam_path, out_path, device="cuda", range_bytes=None, chunk_bytes=No
     if index_format not in index.FORMATS:
         raise ValueError("index_format: %r is none of %s" % (index_format, ", ".join(index.FORMATS)))
     stream_bam = textin.pipe_bam_setting(pipe_bam, "sort_bam")
+    retag = os.environ.get("SVX_SORT_RETAG") == "1" if retag is None else bool(retag)
     dv = _Dev(torch, lib, kernels, dev, clock)
     chunk_blocks = max(int(chunk_bytes or DEFAULT_CHUNK_BYTES) // BLOCK, 1)
     budget = None if memory_bytes is None else max(int(memory_bytes), 1)
@@ -431,7 +456,7 @@ def sort_bam(bam_path, out_path, device="cuda", range_bytes=None, chunk_bytes=No
         with torch.cuda.device(dev):
             if budget is None:                                  # half of what is free: the rest is for a range, its inflate workspace, keys and chunks
                 budget = max(int(torch.cuda.mem_get_info(dev)[0]) // 2, 1)
-            ins = _open_all(paths, dv, _Run(out_path, chunk_blocks, budget, range_bytes, pipes, clock, stream_bam))
+            ins = _open_all(paths, dv, _Run(out_path, chunk_blocks, budget, range_bytes, pipes, clock, stream_bam, retag))
             opened = ins.merged
             opened, kp, spanned = _key_passes(dv, ins, budget, range_bytes)
             od = _order(dv, opened, kp, spanned, budget)
@@ -490,6 +515,9 @@ def main(argv=None):
     ap.add_argument("--pipe-bam", choices=textin.PIPE_BAM, default=os.environ.get("SVX_PIPE_BAM") or "spool",
                     help="a BAM that arrives on a pipe (dorado aligner, pbmm2): spool -- copied into a file beside the output, then sorted -- or "
                          "stream -- a lone one taken in one pass, no file in between (default: $SVX_PIPE_BAM, or spool)")
+    ap.add_argument("--retag", action="store_true", default=os.environ.get("SVX_SORT_RETAG") == "1",
+                    help="several inputs whose @RG / @PG IDs collide: rename the later input's ID to ID-<input number> and rewrite its records' "
+                         "RG:Z / PG:Z tags (BAM inputs; they are read twice); without it a colliding @RG is refused (default: $SVX_SORT_RETAG=1)")
     ap.add_argument("--stats-json", default=None, help="also write the statistics to this file")
     args = ap.parse_args(argv)
     if args.tables not in TABLES:
@@ -501,7 +529,7 @@ def main(argv=None):
     stats = {}
     try:
         path = sort_bam(args.bam[0] if len(args.bam) == 1 else args.bam, args.output, device=args.device, chunk_bytes=args.chunk_bytes, stats=stats, tables=args.tables,
-                        memory_bytes=args.memory, pipe_bam=args.pipe_bam, **(dict(index_format="csi") if args.csi else {}))
+                        memory_bytes=args.memory, pipe_bam=args.pipe_bam, retag=args.retag, **(dict(index_format="csi") if args.csi else {}))
     except (SortWriteError, _lib.SvxError, OSError) as exc:
         print("svision_amd.sort: %s" % exc, file=sys.stderr)
         return 1
@@ -522,6 +550,9 @@ def main(argv=None):
     if len(args.bam) > 1:
         print("%s: %d inputs merged (records: %s), %d of them renumbered into the merged reference dictionary"
               % (path, len(args.bam), ", ".join(str(v) for v in stats.get("input_records", [])), stats.get("retid_inputs", 0)))
+        if stats.get("retag_inputs"):
+            print("%s: %d input(s) with renamed @RG / @PG IDs, the RG:Z / PG:Z tags of %d record(s) rewritten"
+                  % (path, stats["retag_inputs"], stats["retag_records"]))
     if stats.get("spans", 1) > 1:
         print("%s: the records exceed the budget of %d bytes (--memory): written in %d span(s), %d range(s) read again"
               % (path, stats["memory_bytes"], stats["spans"], stats["span_range_reads"]))

@@ -29,7 +29,9 @@ def sorted_header_text(text):
     return "@HD\tVN:1.6\tSO:coordinate\n" + text
 
 
-MergedHeader = collections.namedtuple("MergedHeader", "text references lengths maps")
+# ``renames``: per input the table its records need under ``retag``, {("RG", old ID): new ID, ("PG", old ID): new ID} with the IDs as
+# bytes -- empty for most inputs, and for all of them without ``retag``.
+MergedHeader = collections.namedtuple("MergedHeader", "text references lengths maps renames", defaults=((),))
 
 
 def _line_fields(line):
@@ -46,7 +48,7 @@ def _with_fields(line, new):
     return "\t".join(f[:3] + new[f[:2]] if i and len(f) > 2 and f[2] == ":" and f[:2] in new else f for i, f in enumerate(line.split("\t")))
 
 
-def merge_headers(parts):
+def merge_headers(parts, retag=False):
     """The headers of several inputs -> MergedHeader(the merged text, through :func:`sorted_header_text`; the merged references and
     lengths; per input an int32 table ``map[old refID] -> merged refID``).  ``parts``: per input (its name for messages, the header
     text, its references, their lengths) -- the dictionary a BAM carries in binary, a SAM in its @SQ lines; a headerless SAM part has
@@ -56,17 +58,23 @@ def merge_headers(parts):
       @SQ   the union by SN in order of first appearance, the inputs taken in list order; the first occurrence's whole line is kept
             (a reference a BAM's text has no line for gets ``@SQ SN LN``); the same SN with another LN: SortWriteError
       @RG   the union by ID, an identical line once; the same ID on another line: SortWriteError (the records' RG:Z tags would have
-            to be rewritten)
+            to be rewritten).  Under ``retag`` they are: the later input's line is renamed ID-<1-based input number>, the rule of
+            @PG; the first input to bring an ID keeps it; a new name that is itself taken -- by an earlier input or by a line of
+            the input's own -- is refused
       @PG   the union by ID, an identical line once; the same ID on another line: the later input's line is renamed ID-<1-based input
-            number>, and the PP fields of that input's other @PG lines follow.  The records' PG:Z tags are NOT rewritten
+            number>, and the PP fields of that input's other @PG lines follow.  The records' PG:Z tags are NOT rewritten, unless
+            under ``retag``
+    ``retag``: the result's ``renames`` holds per input what its records need, {("RG", old): new, ("PG", old): new} as bytes (the
+    caller rewrites the records' RG:Z / PG:Z values: svx_record_retag_measure / svx_record_retag_write); unset, every table is empty
+    and a renamed @PG line is a change of the header alone.
       other lines (@CO, ...): in input order, a line that is already there once
     A later input's new line goes behind the last line of its type so far (no such line: to the end), so the types stay together."""
     parts = [(name, text, list(refs), [int(v) for v in lens]) for name, text, refs, lens in parts]
     if len(parts) == 1:
         _name, text, refs, lens = parts[0]
-        return MergedHeader(sorted_header_text(text), refs, lens, [np.arange(len(refs), dtype=np.int32)])
+        return MergedHeader(sorted_header_text(text), refs, lens, [np.arange(len(refs), dtype=np.int32)], [{}])
     out, seen, sq_seen = [], set(), set()                       # the merged lines, the lines that are there, the SN that have a line
-    tid_of, owner, references, lengths, maps = {}, {}, [], [], []
+    tid_of, owner, references, lengths, maps, renames = {}, {}, [], [], [], []
     rg, pg = {}, {}                                             # ID -> (line, input's name)
 
     def add(line):
@@ -113,6 +121,8 @@ def merge_headers(parts):
                     sq_seen.add(ref)
         if k > 1:
             add_sq()
+        own_rg = {_line_fields(l).get("ID") for l in lines if l.startswith("@RG\t")}
+        rg_renamed = {}
         for i, l in enumerate(lines):
             kind, f = l[:3], _line_fields(l)
             if kind == "@HD":
@@ -124,11 +134,21 @@ def merge_headers(parts):
                     continue
                 sq_seen.add(f.get("SN"))
             if kind == "@RG" and "ID" in f:
+                new_id = f["ID"]
                 if k > 1 and f["ID"] in rg and rg[f["ID"]][0] != l:
-                    raise SortWriteError("%s and %s both have a read group %s, on different @RG lines -- one of them would need its records' "
-                                         "RG:Z tags rewritten, which this tool does not do: give the read groups distinct IDs"
-                                         % (rg[f["ID"]][1], name, f["ID"]))
-                rg.setdefault(f["ID"], (l, name))
+                    if not retag:
+                        raise SortWriteError("%s and %s both have a read group %s, on different @RG lines -- one of them would need its records' "
+                                             "RG:Z tags rewritten, which this tool does not do: give the read groups distinct IDs.  Under "
+                                             "retag (--retag, SVX_SORT_RETAG=1; sort_bam's retag) the later one is renamed and its BAM "
+                                             "records follow" % (rg[f["ID"]][1], name, f["ID"]))
+                    new_id = "%s-%d" % (f["ID"], k)
+                    if new_id in rg or new_id in own_rg:
+                        raise SortWriteError("%s and %s both have a read group %s, on different @RG lines, and the name %s that the later one "
+                                             "would take is in use too (%s): give the read groups distinct IDs"
+                                             % (rg[f["ID"]][1], name, f["ID"], new_id, rg[new_id][1] if new_id in rg else name))
+                    rg_renamed[f["ID"]] = new_id
+                    l = _with_fields(l, {"ID": new_id})
+                rg.setdefault(new_id, (l, name))
             if kind == "@PG" and "ID" in f:
                 change = {t: renamed[f[t]] for t in ("ID", "PP") if f.get(t) in renamed}
                 l = _with_fields(l, change) if change else l
@@ -139,9 +159,11 @@ def merge_headers(parts):
             elif l not in seen:
                 add(l)
         add_sq()                                                # (the first input's dictionary entries that its text has no line for)
+        renames.append({(tag, old.encode("latin-1")): new.encode("latin-1") for tag, table in (("RG", rg_renamed), ("PG", renamed))
+                        for old, new in table.items()} if retag else {})
     if not references:
         raise SortWriteError("%s: no input has an @SQ line: a BAM needs its reference dictionary" % parts[0][0])
-    return MergedHeader(sorted_header_text("\n".join(out) + "\n"), references, lengths, maps)
+    return MergedHeader(sorted_header_text("\n".join(out) + "\n"), references, lengths, maps, renames)
 
 
 def sorted_header_bytes(head):

@@ -28,12 +28,15 @@ from .textin import is_stream
 # ``pipe``: None, or the :class:`_Pipe` the input came through -- still to be read (PipeSource, BamPipeSource) or already in its spool file.
 # ``text``: None, or the textin.TextInput whose chunks a SamSource or PipeSource reads.
 # ``source``: the input's kind, chosen at open (the head of this module).
-Opened = collections.namedtuple("Opened", "path head first header room source remap pipe text", defaults=(None, None, None, None))
+# ``retag``: None, or the input's table of sort_header.merge_headers(retag=True), {("RG" / "PG", old ID): new ID}: a BAM input of several
+# whose @RG / @PG IDs collide with an earlier input's -- its records' RG:Z / PG:Z values are replaced (:func:`_retag`).
+Opened = collections.namedtuple("Opened", "path head first header room source remap pipe text retag", defaults=(None, None, None, None, None))
 
 # What the steps of one run share besides the device: where the output goes (a spool lies beside it), the output's chunk, the budget
 # for the records' bytes, ``pipes``: every :class:`_Pipe` the run opened, for sort_bam to close and to clean up behind, and the clock.
 # ``stream_bam``: a lone BAM on a pipe is taken in one pass (``pipe_bam="stream"``), not copied into a file first.
-_Run = collections.namedtuple("_Run", "out_path chunk_blocks budget range_bytes pipes clock stream_bam", defaults=(False,))
+# ``retag``: colliding @RG / @PG IDs of several inputs are renamed and the records follow (sort_bam's ``retag``).
+_Run = collections.namedtuple("_Run", "out_path chunk_blocks budget range_bytes pipes clock stream_bam retag", defaults=(False, False))
 
 
 def inflated_size(path):
@@ -62,11 +65,14 @@ class InputPass:
 
 
 class BamPass(InputPass):
-    """A BAM's: ``d_map`` besides, the input's ``remap`` on the device once :func:`_retid` has needed it."""
+    """A BAM's: ``d_map`` besides, the input's ``remap`` on the device once :func:`_retid` has needed it; ``d_retag``: its ``retag``
+    table likewise (:func:`_retag`), ``retag_records``: the records the key pass rewrote; ``read``: the record bytes as the file
+    holds them, which ``seen`` is not where records were rewritten."""
 
     def __init__(self, base=0):
         InputPass.__init__(self, base)
-        self.d_map = None
+        self.d_map = self.d_retag = None
+        self.retag_records = self.read = 0
 
 
 class SamPass(InputPass):
@@ -119,21 +125,56 @@ def _retid(dv, opened, part, d_bytes, d_off, d_tid_key):
         raise SortWriteError("%s: a record's reference index is outside its file's dictionary (%d references)" % (opened.path, len(opened.remap)))
 
 
+def _retag(dv, opened, part, d_bytes, d_off, count=False):
+    """The records at ``d_off`` [n + 1] in ``d_bytes`` of an input whose @RG / @PG IDs were renamed in the merged header -> (a new
+    buffer, the records' offsets in it [n + 1]): svx_record_retag_measure, an exclusive sum, svx_record_retag_write -- the first RG:Z
+    and PG:Z value that the input's table holds replaced, block_size with it; the status is read once.  The buffer has the 4
+    readable bytes behind its records that the gather and the scatter want.  ``count``: the key pass, which counts the records
+    that changed."""
+    torch, kernels = dv.torch, dv.kernels
+    if part.d_retag is None:
+        part.d_retag = kernels.retag_table(opened.retag, dv.dev)
+    n = int(d_off.shape[0]) - 1
+    d_status = torch.zeros(1, dtype=torch.int32, device=dv.dev)
+    d_len = kernels.record_retag_measure(d_bytes, d_off, part.d_retag, d_status)
+    d_new_off = torch.zeros(n + 1, dtype=torch.int64, device=dv.dev)
+    torch.cumsum(d_len, 0, out=d_new_off[1:])
+    total = int(d_new_off[n].item())
+    d_out = torch.empty(total + 4, dtype=torch.uint8, device=dv.dev)
+    d_out[total:] = 0
+    kernels.record_retag_write(d_bytes, d_off, part.d_retag, d_new_off, d_out, d_status)
+    if count:
+        part.retag_records += int((d_len != d_off[1:] - d_off[:-1]).sum().item())
+    bad = int(d_status.item())
+    dv.clock.lap("retag")
+    if bad:
+        raise SortWriteError("%s: a record's optional fields are malformed -- its RG:Z / PG:Z tags cannot be rewritten" % opened.path)
+    return d_out, d_new_off
+
+
 def _bam_measured(dv, opened, part, rng, room=None):
     """A walked range of a BAM -- a file's or a streamed pipe's -> Measured: svx_cigar_scan for the reference spans
     (index._index_fields), the records' lengths from their offsets up to the chain's exit, and, for an input with a ``remap``, the
     range's records and keys translated where they lie (:func:`_retid`), the host's tid too.  ``room``: the record bytes the file's ISIZE
-    fields add up to; more than that is refused before anything is rewritten."""
+    fields add up to; more than that -- of the bytes as they were read -- is refused before anything is rewritten.  An input with a
+    ``retag`` table: the range's records and offsets are then replaced by the rewritten ones (:func:`_retag`), so lengths, ``seen``
+    and everything behind see those."""
     first = sum(part.range_records)
     if not rng.n_rec:
         return Measured(first, np.empty(0, np.int64), None, None, None, None, None, None, None, 0)
     tid, pos, flag, span, rec_off = index._index_fields(dv.lib, dv.torch, dv.kernels, dv.dev, rng, dv.clock)
     at, last = int(rec_off[0]), int(rng.exit_off)
-    if room is not None and part.seen + last - at > room:
+    if room is not None and part.read + last - at > room:
         raise SortWriteError("%s: more record bytes than its BGZF blocks' ISIZE fields add up to (%d)" % (opened.path, room))
+    part.read += last - at
     if opened.remap is not None:
         _retid(dv, opened, part, rng.d_raw, rng.d_rec_off, rng.d_tid)
         tid = np.where(tid >= 0, opened.remap[np.maximum(tid, 0)], tid).astype(np.int32)
+    if opened.retag:
+        d_off = dv.torch.cat([rng.d_rec_off, dv.torch.tensor([last], dtype=dv.torch.int64, device=dv.dev)])
+        rng.d_raw, d_new_off = _retag(dv, opened, part, rng.d_raw, d_off, count=True)
+        rng.d_rec_off = d_new_off[:-1]
+        return Measured(first, np.diff(d_new_off.cpu().numpy()), None, tid, pos, flag, span, rng.d_tid, rng.d_pos, 0)
     length = np.diff(np.append(rec_off, np.uint64(last)).astype(np.int64))
     return Measured(first, length, None, tid, pos, flag, span, rng.d_tid, rng.d_pos, at)
 
@@ -163,7 +204,13 @@ class BamSource:
     One of several inputs is walked against ITS OWN dictionary (svx_bam_find_starts validates against it).  Where its table is not the
     identity, svx_record_retid -- a lane a record -- rewrites refID and next_refID of the range's records where they lie, and the
     sort's key with them, before the slice is kept; the host's tid goes through the table in NumPy.  Identical dictionaries, or one that
-    opens the merged one: no launch.  A reference index outside the file's dictionary: SortWriteError."""
+    opens the merged one: no launch.  A reference index outside the file's dictionary: SortWriteError.
+
+    One of several inputs whose @RG / @PG IDs collide with an earlier input's, under ``retag``: the merged header renamed them, and the
+    records' RG:Z / PG:Z values follow (:func:`_retag`: svx_record_retag_measure, an exclusive sum, svx_record_retag_write -- a wave a
+    record).  A rewritten record has another length, so the input's record bytes are known only behind its key pass: the run keeps no
+    byte in the key passes and reads its BAM inputs a second time (``fill``) or in spans (``again``), where the same rewriting gives the
+    same lengths; the ISIZE check stays on the bytes as read.  An input with no table: no launch, no allocation."""
     name, state, from_text, reads_once = "bam", BamPass, False, False
 
     def key_pass(self, dv, opened, range_bytes, part, d_stream):
@@ -182,7 +229,8 @@ class BamSource:
 
     def again(self, dv, opened, part, need):
         """The ranges ``need`` of a BAM read again: read, inflate, CRC, find_starts, the walk's counts and offsets; nothing is extracted.
-        An input with a ``remap``: the range's records translated where they lie before they are handed on (:func:`_retid`)."""
+        An input with a ``remap``: the range's records translated where they lie before they are handed on (:func:`_retid`); with a
+        ``retag`` table: the rewritten records and their offsets are handed on (:func:`_retag`)."""
         for k, rng in zip(need, index.record_ranges(opened.path, opened.head, dv.dev, dv.clock, places=[part.places[k] for k in need], extract=False,
                                                     first=opened.first)):
             if rng.n_rec != part.range_records[k]:
@@ -192,6 +240,8 @@ class BamSource:
             dv.clock.lap("walk")
             if opened.remap is not None:
                 _retid(dv, opened, part, rng.d_raw, d_src_off[:rng.n_rec], None)
+            if opened.retag:
+                rng.d_raw, d_src_off = _retag(dv, opened, part, rng.d_raw, d_src_off)
             yield k, rng.n_rec, rng.d_raw, d_src_off
             _release(rng)
             del rng, d_src_off
