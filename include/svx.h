@@ -521,6 +521,24 @@ int            svx_bam_walk_offsets(const uint8_t* d_raw, const uint64_t* d_star
  *                       reads the records byte by byte and nothing outside d_bytes[d_off[0] .. d_off[n]); write reads d_bytes
  *                       and d_table in aligned dwords as svx_record_scatter_segments reads d_src: both 4-byte aligned and
  *                       readable up to the next multiple of 4 behind their last byte.  n = 0 or m = 0 launches nothing
+ *   svx_record_tags_measure / svx_record_tags_write   optional fields removed from every record by their two-byte tag
+ *                       (svision_amd/sort.py under drop_tags / keep_tags; ABI 420, additive).  Records, offsets and the walk of
+ *                       the fields are those of svx_record_retag_measure, a wave per record.  d_table: a bitmap of
+ *                       SVX_RECORD_TAGS_TABLE_BYTES bytes, 4-byte aligned, read as dwords: bit (t0 | t1 << 8) -- bit k of the
+ *                       little-endian bitmap is bit k % 32 of dword k / 32 -- set = every field whose tag is the bytes t0 t1 is
+ *                       REMOVED, whatever its type and however often it occurs; a keep list is the complement.  The kept
+ *                       fields stay in the record's order, everything else of it byte for byte; block_size becomes the new
+ *                       length - 4.  measure: d_new_len[r] (int64) = the record's length without the removed fields.  write:
+ *                       exactly that many bytes at d_dst + d_new_off[r], d_new_off [n + 1] the exclusive sum of d_new_len: the
+ *                       fixed part with the fields in front of the first removed one, and every further maximal run of kept
+ *                       fields, is one copy by the scatter's copy routine; nothing else of d_dst is written.  d_status[0]
+ *                       (the caller zeroes it; a plain store of the one value): 0 = every record was well formed and, in
+ *                       write, every record had the length of its walk; 1 = a MALFORMED record (the list above: it keeps its
+ *                       length and is copied as it is), or, in write, d_new_off gives a record another length than its walk
+ *                       (nothing of that record is written; the others are).  SLACK: measure reads the records byte by byte
+ *                       and nothing outside d_bytes[d_off[0] .. d_off[n]) -- none; write reads d_bytes in aligned dwords as
+ *                       svx_record_scatter_segments reads d_src: 4-byte aligned and readable up to the next multiple of 4
+ *                       behind its last byte -- at most 3 bytes.  n = 0 launches nothing
  * No atomics in any of them: the output is a pure function of the input.  n = 0 is fine everywhere (d_off_out[0] = 0). */
 #define SVX_RECORD_SORT_TILE 2048u
 size_t         svx_record_sort_ws_bytes(uint32_t n);
@@ -542,6 +560,11 @@ int            svx_record_retag_measure(const void* d_bytes, const int64_t* d_of
                                         int32_t m, int64_t* d_new_len, int32_t* d_status, void* stream);
 int            svx_record_retag_write(const void* d_bytes, const int64_t* d_off, uint32_t n, const void* d_table, const int32_t* d_table_off,
                                       int32_t m, const int64_t* d_new_off, void* d_dst, int32_t* d_status, void* stream);
+#define SVX_RECORD_TAGS_TABLE_BYTES 8192u
+int            svx_record_tags_measure(const void* d_bytes, const int64_t* d_off, uint32_t n, const uint32_t* d_table, int64_t* d_new_len,
+                                       int32_t* d_status, void* stream);
+int            svx_record_tags_write(const void* d_bytes, const int64_t* d_off, uint32_t n, const uint32_t* d_table, const int64_t* d_new_off,
+                                     void* d_dst, int32_t* d_status, void* stream);
 /* BGZF members FROM inflated bytes (svx_deflate.hip; ABI 420, additive): the encoder of svision_amd/sort.py, which writes the
  * device-sorted BAM.
  *   svx_bgzf_deflate    block b = the bytes d_in[d_in_off[b] .. d_in_off[b + 1]) -- any offsets, no alignment, 0 .. 0xFF00 bytes a block --

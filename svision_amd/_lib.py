@@ -86,6 +86,8 @@ SYMBOLS = {
     "svx_record_retid": (ctypes.c_int, [_vp, _vp, _u32, _vp, _i32, _vp, _vp, _vp]),      # (ABI 420, additive: several inputs merged, svision_amd/sort.py)
     "svx_record_retag_measure": (ctypes.c_int, [_vp, _vp, _u32, _vp, _vp, _i32, _vp, _vp, _vp]),         # (ABI 420, additive: colliding @RG / @PG IDs renamed)
     "svx_record_retag_write": (ctypes.c_int, [_vp, _vp, _u32, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "svx_record_tags_measure": (ctypes.c_int, [_vp, _vp, _u32, _vp, _vp, _vp, _vp]),                     # (ABI 420, additive: optional fields removed by tag)
+    "svx_record_tags_write": (ctypes.c_int, [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp]),
     "svx_bgzf_deflate": (ctypes.c_int, [_vp, _vp, _u32, _vp, _vp, _vp, _vp]),     # (ABI 420, additive: svx_deflate.hip)
     "svx_bgzf_deflate_dyn_ws_bytes": (_sz, [_u32]),                      # (ABI 420, additive: dynamic Huffman tables)
     "svx_bgzf_deflate_dyn": (ctypes.c_int, [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _u64, _vp]),

@@ -232,7 +232,8 @@ def _write_sorted(options):
     ``--memory``: the device memory for the records' inflated bytes, beyond which the file is written in spans, a pass over the input
     for each (default: half of the free device memory), ``SVX_SORT_INDEX=csi`` is ``--csi``: the index written as a ``.csi``, the format for
     positions from 2^29 on, ``SVX_SORT_RETAG=1`` is ``--retag``: colliding @RG / @PG IDs of several inputs renamed and their records' tags
-    rewritten.  ``-b a.bam,b.bam,c.sam`` (:func:`_input_list`): the inputs merged into the one sorted
+    rewritten, ``SVX_SORT_DROP_TAGS=fi,fp,ri,rp`` / ``SVX_SORT_KEEP_TAGS=RG,NM`` are ``--drop-tags`` / ``--keep-tags``: optional fields
+    removed from every record of the sorted file (BAM inputs only; the caller reads none of them).  ``-b a.bam,b.bam,c.sam`` (:func:`_input_list`): the inputs merged into the one sorted
     file ``OUT/<first input's stem>.merged.sorted.bam``."""
     import json
     import subprocess

@@ -31,6 +31,9 @@
 //   svx_record_retag_measure    a WAVE per record walks the optional fields behind qual and finds the first RG:Z / PG:Z value that a
 //   svx_record_retag_write      table renames (the IDs of several inputs that collide, svision_amd/sort.py): the new length, then the
 //                               record with the value replaced and block_size set, in up to five copies (svx_recsort_core.hpp)
+//   svx_record_tags_measure     a WAVE per record walks the same chain and removes optional fields by their tag (svision_amd/sort.py,
+//   svx_record_tags_write       --drop-tags / --keep-tags): one bit a two-byte tag in a bitmap of 65,536; the new length, then the
+//                               record without them, a copy a run of kept fields, block_size set (svx_recsort_core.hpp)
 // No atomics, no cross-workgroup dependency inside a launch: the output is a pure function of the input, identical in every run.
 // A counter in LDS is written by ONE lane a round (the leader of its digit, in the wave's own row) with a barrier behind it.
 #include <hip/hip_runtime.h>
@@ -366,6 +369,26 @@ void record_retag_write_kernel(const uint8_t* __restrict__ bytes, const int64_t*
     svx_recsort::retag_write_record(bytes, off, table, new_off, dst, r, threadIdx.x & 63u, status);
 }
 
+// A wave per record, the retag pair's shape: measure follows the chain and sums the removed fields' bytes, write follows it again and
+// copies every run of kept fields by the wave.  Kinetics arrays (fi fp ri rp, B:C of the read's length) are skipped from their count.
+__global__ __launch_bounds__(WAVE * SEG_WAVES)
+void record_tags_measure_kernel(const uint8_t* __restrict__ bytes, const int64_t* __restrict__ off, uint32_t n, const uint32_t* __restrict__ table,
+                                int64_t* __restrict__ new_len, int32_t* __restrict__ status)
+{
+    const uint64_t r = (uint64_t)blockIdx.x * SEG_WAVES + (threadIdx.x >> 6);
+    if (r >= n) return;                                         // (whole waves: no barrier in this kernel)
+    svx_recsort::tags_measure_record(bytes, off, table, new_len, r, threadIdx.x & 63u, status);
+}
+
+__global__ __launch_bounds__(WAVE * SEG_WAVES)
+void record_tags_write_kernel(const uint8_t* __restrict__ bytes, const int64_t* __restrict__ off, uint32_t n, const uint32_t* __restrict__ table,
+                              const int64_t* __restrict__ new_off, uint8_t* __restrict__ dst, int32_t* __restrict__ status)
+{
+    const uint64_t r = (uint64_t)blockIdx.x * SEG_WAVES + (threadIdx.x >> 6);
+    if (r >= n) return;
+    svx_recsort::tags_write_record(bytes, off, table, new_off, dst, r, threadIdx.x & 63u, status);
+}
+
 struct SortWs {
     uint64_t* key[2];
     uint32_t* idx;
@@ -532,5 +555,31 @@ extern "C" int svx_record_retag_write(const void* d_bytes, const int64_t* d_off,
     const dim3 grid((uint32_t)(((uint64_t)n + SEG_WAVES - 1) / SEG_WAVES));
     hipLaunchKernelGGL(record_retag_write_kernel, grid, dim3(WAVE * SEG_WAVES), 0, static_cast<hipStream_t>(stream),
                        static_cast<const uint8_t*>(d_bytes), d_off, n, table, d_new_off, static_cast<uint8_t*>(d_dst), d_status);
+    return hipGetLastError() == hipSuccess ? SVX_OK : SVX_ELAUNCH;
+}
+
+static_assert(svx_recsort::TAGS_TABLE_WORDS * 4 == SVX_RECORD_TAGS_TABLE_BYTES, "include/svx.h names the table's size");
+
+extern "C" int svx_record_tags_measure(const void* d_bytes, const int64_t* d_off, uint32_t n, const uint32_t* d_table, int64_t* d_new_len,
+                                       int32_t* d_status, void* stream)
+{
+    if (n == 0) return SVX_OK;
+    if (!d_bytes || !d_off || !d_table || !d_new_len || !d_status) return SVX_EINVAL;
+    if (reinterpret_cast<uintptr_t>(d_table) & 3u) return SVX_EINVAL;
+    const dim3 grid((uint32_t)(((uint64_t)n + SEG_WAVES - 1) / SEG_WAVES));
+    hipLaunchKernelGGL(record_tags_measure_kernel, grid, dim3(WAVE * SEG_WAVES), 0, static_cast<hipStream_t>(stream),
+                       static_cast<const uint8_t*>(d_bytes), d_off, n, d_table, d_new_len, d_status);
+    return hipGetLastError() == hipSuccess ? SVX_OK : SVX_ELAUNCH;
+}
+
+extern "C" int svx_record_tags_write(const void* d_bytes, const int64_t* d_off, uint32_t n, const uint32_t* d_table, const int64_t* d_new_off,
+                                     void* d_dst, int32_t* d_status, void* stream)
+{
+    if (n == 0) return SVX_OK;
+    if (!d_bytes || !d_off || !d_table || !d_new_off || !d_dst || !d_status) return SVX_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(d_bytes) | reinterpret_cast<uintptr_t>(d_table)) & 3u) return SVX_EINVAL;
+    const dim3 grid((uint32_t)(((uint64_t)n + SEG_WAVES - 1) / SEG_WAVES));
+    hipLaunchKernelGGL(record_tags_write_kernel, grid, dim3(WAVE * SEG_WAVES), 0, static_cast<hipStream_t>(stream),
+                       static_cast<const uint8_t*>(d_bytes), d_off, n, d_table, d_new_off, static_cast<uint8_t*>(d_dst), d_status);
     return hipGetLastError() == hipSuccess ? SVX_OK : SVX_ELAUNCH;
 }

@@ -1,6 +1,6 @@
-// svx_recsort_core.hpp -- a lane's share of scatter_segments_kernel, of record_retid_kernel and of the two record_retag kernels
-// (svx_recsort.hip), host- and device-compilable: the host programs tools/hostwave/scatter_main.cpp, retid_main.cpp and
-// retag_main.cpp run this very code, lane by lane, under AddressSanitizer.
+// svx_recsort_core.hpp -- a lane's share of scatter_segments_kernel, of record_retid_kernel, of the two record_retag kernels and of
+// the two record_tags kernels (svx_recsort.hip), host- and device-compilable: the host programs tools/hostwave/scatter_main.cpp,
+// retid_main.cpp, retag_main.cpp and tags_main.cpp run this very code, lane by lane, under AddressSanitizer.
 //
 // A wave of 64 lanes copies one segment.  The DESTINATION decides the alignment, as in gather_segments_kernel: single bytes up to
 // its first dword boundary, whole dwords -- each assembled from the one or two aligned source dwords that hold its bytes --,
@@ -170,9 +170,43 @@ SVX_RS_HD int32_t retag_lookup(const RetagTable& tb, uint8_t t0, uint8_t t1, con
     return -1;
 }
 
-// The plan of the record rec[0 .. len): nothing outside those bytes is read, byte by byte.  Malformed: shorter than 36 bytes,
-// block_size + 4 != len, the fixed part with name, CIGAR, seq and qual longer than the record, a field header cut by the end, an
-// unknown type or B subtype, a value or a B array past the end, a Z / H without NUL.
+// Where the optional fields of the record rec[0 .. len) begin, behind qual; 0: shorter than 36 bytes, block_size + 4 != len, or the
+// fixed part with name, CIGAR, seq and qual longer than the record.  Byte loads inside the record.
+SVX_RS_HD uint64_t aux_start(const uint8_t* rec, int64_t len)
+{
+    if (len < 36 || (int64_t)load_le32(rec) + 4 != len) return 0;
+    const uint64_t l_name = rec[12], n_cigar = (uint64_t)rec[16] | (uint64_t)rec[17] << 8, l_seq = (uint32_t)load_le32(rec + 20);
+    const uint64_t p = 36 + l_name + 4 * n_cigar + (l_seq + 1) / 2 + l_seq;
+    return p > (uint64_t)len ? 0 : p;
+}
+
+// One step of the chain: the field that begins at rec[p], p < end, of a record that ends at rec[end] -> the offset behind it, 0: a
+// field header cut by the end, an unknown type or B subtype, a value or a B array past the end, a Z / H without NUL (whose NUL,
+// where there is one, is the byte in front of the offset returned).  The same loads and the same answer in every lane; the lanes
+// share only the search for the NUL, 64 bytes a ballot.  A B array is skipped in one step from its count.
+SVX_RS_HD uint64_t field_next(const uint8_t* rec, uint64_t p, uint64_t end, uint32_t lane)
+{
+    if (p + 3 > end) return 0;
+    const uint8_t type = rec[p + 2];
+    const uint64_t v = p + 3;
+    const uint32_t fixed = retag_fixed_size(type);
+    if (fixed) return v + fixed > end ? 0 : v + fixed;
+    if (type == 'Z' || type == 'H') {
+        for (uint64_t q = v; q < end; q += WAVE) {              // 64 bytes a step: the lowest lane that holds a NUL
+            const uint64_t mask = ballot_nul(rec + q, end - q < WAVE ? end - q : WAVE, lane);
+            if (mask) return q + lowest_bit(mask) + 1;
+        }
+        return 0;
+    }
+    if (type != 'B' || v + 5 > end) return 0;
+    const uint32_t elem = retag_fixed_size(rec[v]);
+    if (!elem || rec[v] == 'A') return 0;
+    const uint64_t count = (uint32_t)load_le32(rec + v + 1);
+    return count * elem > end - (v + 5) ? 0 : v + 5 + count * elem;
+}
+
+// The plan of the record rec[0 .. len): nothing outside those bytes is read, byte by byte.  Malformed: what aux_start and
+// field_next refuse.
 SVX_RS_HD RetagPlan retag_plan(const uint8_t* rec, int64_t len, const RetagTable& tb, uint32_t lane)
 {
     RetagPlan plan;
@@ -181,50 +215,28 @@ SVX_RS_HD RetagPlan retag_plan(const uint8_t* rec, int64_t len, const RetagTable
     plan.bad = true;
     plan.at[0] = plan.at[1] = plan.old_len[0] = plan.old_len[1] = 0;
     plan.entry[0] = plan.entry[1] = -1;
-    if (len < 36 || (int64_t)load_le32(rec) + 4 != len) return plan;
+    uint64_t p = aux_start(rec, len);
+    if (!p) return plan;
     const uint64_t end = (uint64_t)len;
-    const uint64_t l_name = rec[12], n_cigar = (uint64_t)rec[16] | (uint64_t)rec[17] << 8, l_seq = (uint32_t)load_le32(rec + 20);
-    uint64_t p = 36 + l_name + 4 * n_cigar + (l_seq + 1) / 2 + l_seq;
-    if (p > end) return plan;
     bool done_rg = false, done_pg = false;
     uint32_t n = 0;
     int64_t grow = 0;
     while (p < end) {
-        if (p + 3 > end) return plan;
-        const uint8_t t0 = rec[p], t1 = rec[p + 1], type = rec[p + 2];
-        const uint64_t v = p + 3;
-        const uint32_t fixed = retag_fixed_size(type);
-        if (fixed) {
-            if (v + fixed > end) return plan;
-            p = v + fixed;
-        } else if (type == 'Z' || type == 'H') {
-            uint64_t nul = end;
-            for (uint64_t q = v; q < end; q += WAVE) {          // 64 bytes a step: the lowest lane that holds a NUL
-                const uint64_t mask = ballot_nul(rec + q, end - q < WAVE ? end - q : WAVE, lane);
-                if (mask) { nul = q + lowest_bit(mask); break; }
+        const uint64_t next = field_next(rec, p, end, lane);
+        if (!next) return plan;
+        const uint8_t t0 = rec[p], t1 = rec[p + 1];
+        const bool rg = t0 == 'R' && t1 == 'G', pg = t0 == 'P' && t1 == 'G';
+        if (rec[p + 2] == 'Z' && ((rg && !done_rg) || (pg && !done_pg))) {
+            const uint64_t v = p + 3, nul = next - 1;
+            const int32_t e = retag_lookup(tb, t0, t1, rec + v, nul - v);
+            if (e >= 0) {
+                plan.at[n] = v; plan.old_len[n] = nul - v; plan.entry[n] = e;
+                grow += (int64_t)(tb.off[2 * e + 2] - tb.off[2 * e + 1]) - (int64_t)(nul - v);
+                ++n;
+                if (rg) done_rg = true; else done_pg = true;
             }
-            if (nul == end) return plan;
-            const bool rg = t0 == 'R' && t1 == 'G', pg = t0 == 'P' && t1 == 'G';
-            if (type == 'Z' && ((rg && !done_rg) || (pg && !done_pg))) {
-                const int32_t e = retag_lookup(tb, t0, t1, rec + v, nul - v);
-                if (e >= 0) {
-                    plan.at[n] = v; plan.old_len[n] = nul - v; plan.entry[n] = e;
-                    grow += (int64_t)(tb.off[2 * e + 2] - tb.off[2 * e + 1]) - (int64_t)(nul - v);
-                    ++n;
-                    if (rg) done_rg = true; else done_pg = true;
-                }
-            }
-            p = nul + 1;
-        } else if (type == 'B') {
-            if (v + 5 > end) return plan;
-            const uint32_t elem = retag_fixed_size(rec[v]);
-            if (!elem || rec[v] == 'A') return plan;
-            const uint64_t count = (uint32_t)load_le32(rec + v + 1);
-            if (count * elem > end - (v + 5)) return plan;
-            p = v + 5 + count * elem;                           // skipped in one step from its count
-        } else {
-            return plan;
         }
+        p = next;
     }
     plan.n = n;
     plan.new_len = (uint64_t)((int64_t)end + grow);
@@ -276,6 +288,89 @@ SVX_RS_HD void retag_write_record(const uint8_t* bytes, const int64_t* off, cons
         from = plan.at[k] + plan.old_len[k];
     }
     copy_segment(rec + from, out + to, (uint64_t)len - from, lane);
+}
+
+// ---- record_tags_measure_kernel's and record_tags_write_kernel's share of one record (tools/hostwave/tags_main.cpp) ----
+// Optional fields removed by their tag.  A WAVE per record, the chain followed as above (aux_start, field_next).  The table is a
+// bitmap over ALL 65,536 two-byte values, 2,048 dwords: bit (t0 | t1 << 8) set = a field of the tag (t0, t1) is REMOVED.  One
+// dword load and a shift a field, the same in every lane, whatever bytes a record's tags hold; a keep list is the complement, made
+// on the host, so the kernels know one rule.
+constexpr uint32_t TAGS_TABLE_WORDS = 2048;
+
+SVX_RS_HD bool tags_removed(const uint32_t* table, uint8_t t0, uint8_t t1)
+{
+    const uint32_t k = (uint32_t)t0 | (uint32_t)t1 << 8;
+    return (table[k >> 5] >> (k & 31u)) & 1u;
+}
+
+// The length of the record rec[0 .. len) without the fields that `table` removes; *bad: malformed (what aux_start and field_next
+// refuse; the length is then the record's own).  Byte loads inside the record.  The same in every lane.
+SVX_RS_HD uint64_t tags_new_len(const uint8_t* rec, int64_t len, const uint32_t* table, uint32_t lane, bool* bad)
+{
+    const uint64_t end = len < 0 ? 0 : (uint64_t)len;
+    *bad = true;
+    uint64_t p = aux_start(rec, len), removed = 0;
+    if (!p) return end;
+    while (p < end) {
+        const uint64_t next = field_next(rec, p, end, lane);
+        if (!next) return end;
+        if (tags_removed(table, rec[p], rec[p + 1])) removed += next - p;
+        p = next;
+    }
+    *bad = false;
+    return end - removed;
+}
+
+// Lane `lane` of the wave of record r, measure: new_len[r] = the record's length without the removed fields; a malformed record
+// keeps its length and sets *status (a plain store of the one value).
+SVX_RS_HD void tags_measure_record(const uint8_t* bytes, const int64_t* off, const uint32_t* table, int64_t* new_len, uint64_t r, uint32_t lane,
+                                   int32_t* status)
+{
+    bool bad;
+    const uint64_t n = tags_new_len(bytes + off[r], off[r + 1] - off[r], table, lane, &bad);
+    if (lane == 0) {
+        new_len[r] = (int64_t)n;
+        if (bad) *status = 1;
+    }
+}
+
+// Lane `lane` of the wave of record r, write: the record without the removed fields and with its block_size set goes to
+// dst[new_off[r] .. new_off[r + 1]).  The chain is walked for the length first: where new_off does not give the record that
+// length, nothing is written and *status is set.  Then it is walked again, and the fixed part with the fields up to the first
+// removed one, and every further maximal run of kept fields, is ONE copy_segment (any skew of source and destination) -- the
+// removed fields have no bound, so no plan holds them; the walk is the plan.  A malformed record is copied as it is and sets *status,
+// a record that loses nothing is one copy.
+SVX_RS_HD void tags_write_record(const uint8_t* bytes, const int64_t* off, const uint32_t* table, const int64_t* new_off, uint8_t* dst, uint64_t r,
+                                 uint32_t lane, int32_t* status)
+{
+    const uint8_t* rec = bytes + off[r];
+    const int64_t len = off[r + 1] - off[r];
+    bool bad;
+    const uint64_t new_len = tags_new_len(rec, len, table, lane, &bad);
+    if (bad && lane == 0) *status = 1;
+    if (new_off[r + 1] - new_off[r] != (int64_t)new_len) {
+        if (lane == 0) *status = 1;
+        return;
+    }
+    uint8_t* out = dst + new_off[r];
+    const uint64_t end = (uint64_t)len;
+    if (bad || new_len == end) {
+        copy_segment(rec, out, new_len, lane);
+        return;
+    }
+    if (lane < 4) out[lane] = (uint8_t)((uint32_t)(new_len - 4) >> (8 * lane));             // block_size
+    uint64_t from = 4, to = 4, p = aux_start(rec, len);        // rec[from .. p): the run of kept bytes that is open
+    while (p < end) {
+        const uint64_t next = field_next(rec, p, end, lane);
+        if (!next) return;                                      // (not reached: the first walk went through the same bytes)
+        if (tags_removed(table, rec[p], rec[p + 1])) {
+            if (p > from) copy_segment(rec + from, out + to, p - from, lane);
+            to += p - from;
+            from = next;
+        }
+        p = next;
+    }
+    if (end > from) copy_segment(rec + from, out + to, end - from, lane);
 }
 
 }  // namespace svx_recsort

@@ -1004,6 +1004,79 @@ def record_retag_write(d_bytes, d_off, table, d_new_off, out, status):
     return out
 
 
+TAGS_TABLE_BYTES = 8192             # SVX_RECORD_TAGS_TABLE_BYTES: a bit for every two-byte tag value
+TAGS_ALWAYS_KEPT = ("CG",)          # the real CIGAR of a record with more than 65,535 operations: never removed
+
+
+def tags_bitmap(tags, keep):
+    """``tags``: 2-character tags (str or bytes) -> the table of svx_record_tags_measure on the host, int32 [2048]: bit
+    (t0 | t1 << 8) set = a field of that tag is removed.  ``keep`` unset: the listed tags are removed; set: every tag BUT the listed
+    ones -- an empty list removes all.  ``CG`` is never removed: naming it in a drop list is an error, a keep list implies it."""
+    keys = []
+    for tag in tuple(tags) + (TAGS_ALWAYS_KEPT if keep else ()):
+        raw = tag.encode("latin-1") if isinstance(tag, str) else bytes(tag)
+        if len(raw) != 2:
+            raise _lib.SvxError("a tag is two bytes: %r" % (tag,))
+        if not keep and raw.decode("latin-1") in TAGS_ALWAYS_KEPT:
+            raise _lib.SvxError("%s is never removed" % raw.decode("latin-1"))
+        keys.append(raw[0] | raw[1] << 8)
+    bits = np.full(TAGS_TABLE_BYTES, 0xFF if keep else 0, np.uint8)
+    for k in keys:
+        if keep:
+            bits[k >> 3] &= 0xFF ^ (1 << (k & 7))
+        else:
+            bits[k >> 3] |= 1 << (k & 7)
+    return bits.view("<i4")
+
+
+def tags_table(tags, keep, device):
+    """:func:`tags_bitmap` on the device -> int32 [2048], what :func:`record_tags_measure` and :func:`record_tags_write` take."""
+    return torch.from_numpy(tags_bitmap(tags, keep).copy()).to(device)
+
+
+def _require_tags(d_bytes, d_off, table, status):
+    for t, name in ((d_bytes, "d_bytes"), (d_off, "d_off"), (table, "table"), (status, "status")):
+        _require_cuda(t, name)
+    if d_bytes.dtype != torch.uint8 or d_off.dtype != torch.int64 or d_off.dim() != 1 or d_off.shape[0] < 1 or status.dtype != torch.int32 \
+            or status.numel() < 1:
+        raise _lib.SvxError("d_bytes must be uint8, d_off int64 [n + 1], status int32 [1]")
+    if table.dtype != torch.int32 or table.dim() != 1 or table.shape[0] * 4 != TAGS_TABLE_BYTES or not table.is_contiguous():
+        raise _lib.SvxError("a tags table is int32 [%d], contiguous (tags_table)" % (TAGS_TABLE_BYTES // 4))
+    n = int(d_off.shape[0]) - 1
+    if n > 0xFFFFFFFF:
+        raise _lib.SvxError("svx_record_tags takes up to 2^32 - 1 records")
+    return n
+
+
+def record_tags_measure(d_bytes, d_off, table, status):
+    """The n BAM records d_bytes[d_off[r]:d_off[r + 1]] (uint8; int64 [n + 1], any byte offsets) -> int64 [n]: every record's length
+    without the optional fields that ``table`` (:func:`tags_table`) removes.  ``status``: int32 [1], set to 1 where a record is
+    malformed (it keeps its length).  See include/svx.h svx_record_tags_measure."""
+    lib = _lib.load()
+    n = _require_tags(d_bytes, d_off, table, status)
+    d_new_len = torch.empty(n, dtype=torch.int64, device=d_bytes.device)
+    _lib.check(lib.svx_record_tags_measure(d_bytes.data_ptr(), d_off.data_ptr(), n, table.data_ptr(), d_new_len.data_ptr(), status.data_ptr(),
+                                           _stream_ptr(d_bytes.device)), "svx_record_tags_measure")
+    return d_new_len
+
+
+def record_tags_write(d_bytes, d_off, table, d_new_off, out, status):
+    """The records of :func:`record_tags_measure` without those fields -> ``out`` (uint8), record r at byte d_new_off[r] (int64
+    [n + 1], the exclusive sum of measure's lengths; ``out`` holds at least d_new_off[n] bytes, nothing else of it is written),
+    block_size set.  ``status``: set to 1 where a record is malformed (copied as it is) or d_new_off gives it another length than
+    measure (not copied).  ``d_bytes``: readable up to the next multiple of 4 bytes behind its end.  See include/svx.h
+    svx_record_tags_write."""
+    lib = _lib.load()
+    n = _require_tags(d_bytes, d_off, table, status)
+    for t, name in ((d_new_off, "d_new_off"), (out, "out")):
+        _require_cuda(t, name)
+    if d_new_off.dtype != torch.int64 or d_new_off.shape != d_off.shape or out.dtype != torch.uint8 or out.dim() != 1:
+        raise _lib.SvxError("d_new_off must be int64 [n + 1], out uint8")
+    _lib.check(lib.svx_record_tags_write(d_bytes.data_ptr(), d_off.data_ptr(), n, table.data_ptr(), d_new_off.data_ptr(), out.data_ptr(),
+                                         status.data_ptr(), _stream_ptr(d_bytes.device)), "svx_record_tags_write")
+    return out
+
+
 # ---- BGZF members from inflated bytes (svx_deflate.hip; the writer: svision_amd/sort.py) ----
 BGZF_SLOT = 65536                    # SVX_BGZF_SLOT: bytes of a member's slot in svx_bgzf_deflate's output
 BGZF_BLOCK_MAX = 0xFF00              # SVX_BGZF_BLOCK_MAX: the largest block the encoder takes (htslib's block size)

@@ -60,6 +60,15 @@ the stability of the one svx_record_sort over the inputs' keys end to end.
             that fits then fills the stream input by input (the source's ``fill``; :func:`_key_passes`)
 A failure names the input it came from; "changed while it was sorted" names the input that changed.
 
+Optional fields removed.  ``drop_tags`` / ``keep_tags`` (``--drop-tags fi,fp,ri,rp``, ``--keep-tags RG,NM,SA,MD``; ``SVX_SORT_DROP_TAGS`` /
+``SVX_SORT_KEEP_TAGS``; off by default) remove optional fields from every record as it is sorted -- the kinetics arrays, base
+modifications and move tables that pbmm2 and dorado carry over from unaligned BAMs and that are often most of a record.  The two files
+are, byte for byte, those of the same inputs whose records had those fields removed beforehand (:func:`tag_filter` has the rules;
+``CG`` always stays).  A wave a record on the device (sort_sources._tags), in the key pass and again per range of a span.  Records only
+get shorter, so ``room`` stays the ISIZE sum: the stream is allocated once, the shortened records are kept as the key passes go, and no
+input is read twice; whether the file is written in spans is decided on the unfiltered size.  An input read as SAM text is refused
+under the switch, and a lone BAM on a pipe is sorted from its spool copy under either ``pipe_bam``.
+
 A corrupt block, a CRC mismatch, a malformed or cut chain, a device allocation or a write that fails raises SortWriteError (a
 ValueError); no file and no temporary is left behind.
 
@@ -73,6 +82,7 @@ sort_out.BgzfWriter -> ``_bai`` -> sort_out.commit_pair -> ``_stats``.  Which re
 """
 import collections
 import os
+import re
 import sys
 
 import numpy as np
@@ -80,12 +90,12 @@ import numpy as np
 from . import _lib, index, textin
 from .sort_header import MergedHeader, SortWriteError, merge_headers, sorted_header_bytes, sorted_header_text     # noqa: F401  (their names here are in use)
 from .sort_out import BLOCK, DEFAULT_CHUNK_BYTES, STREAM_SLACK, BgzfWriter, DeviceEncode, Spool, _Dev, block_cuts, chunk_cuts, commit_pair, spool_copy, spool_path   # noqa: F401
-from .sort_sources import Opened, PipeStore, SamSource, StreamLedger, _open, _pipe_spooled, _rec_base, _Run, inflated_size, keeps_in_core   # noqa: F401
+from .sort_sources import Opened, PipeStore, SamSource, StreamLedger, TagFilter, _open, _pipe_spooled, _rec_base, _Run, inflated_size, keeps_in_core   # noqa: F401
 from .textin import DEFAULT_SAM_CHUNK_BYTES, SAM_READ_THREADS, input_paths, is_stream    # noqa: F401
 
 TABLES = ("fixed", "dynamic")                                   # the encoder: svx_bgzf_deflate / svx_bgzf_deflate_dyn
 STAGES = ("read", "upload", "inflate", "crc", "find_starts", "walk", "scan", "read_back", "keep", "join", "sort", "gather", "scatter", "deflate",
-          "pack", "download", "write", "index", "lines", "measure", "encode", "host_lines", "retid", "spool", "retag")
+          "pack", "download", "write", "index", "lines", "measure", "encode", "host_lines", "retid", "spool", "retag", "tags")
 
 
 # ---- the plan of a sort in spans (host, NumPy) ----
@@ -143,6 +153,55 @@ def parse_memory(text):
     return int(digits) * scale
 
 
+_TAG = re.compile(r"[A-Za-z][A-Za-z0-9]\Z")
+TAGS_ALWAYS_KEPT = "CG"             # the real CIGAR of a record with more than 65,535 operations
+
+
+def parse_tags(value, name):
+    """A list of optional-field tags -- a list or tuple of 2-character strings, or ONE comma-separated string ("" is the empty list)
+    -> a tuple of them.  A tag is ``[A-Za-z][A-Za-z0-9]``; anything else, or a tag that is listed twice: ValueError, naming ``name``."""
+    if isinstance(value, str):
+        items = value.split(",") if value.strip() else []
+    elif isinstance(value, (list, tuple)):
+        items = list(value)
+    else:
+        raise ValueError("%s: a list of tags or one comma-separated string, not %r" % (name, value))
+    for tag in items:
+        if not isinstance(tag, str) or not _TAG.match(tag):
+            raise ValueError("%s: %r is no tag -- a letter followed by a letter or a digit (fi, MM, X0)" % (name, tag))
+    twice = sorted({tag for tag in items if items.count(tag) > 1})
+    if twice:
+        raise ValueError("%s: %s is listed twice" % (name, ", ".join(twice)))
+    return tuple(items)
+
+
+def tag_filter(drop_tags=None, keep_tags=None, environ=None):
+    """sort_bam's ``drop_tags`` / ``keep_tags`` -> the run's TagFilter(mode, tags), or None: off.
+
+      drop_tags  every optional field whose two-byte tag is listed is removed, whatever its type and however often it occurs; an
+                 empty list removes nothing: off
+      keep_tags  every field whose tag is NOT listed is removed; an empty list removes all fields
+      CG         is never removed: it holds the real CIGAR of a record with more than 65,535 operations.  Naming it in ``drop_tags``
+                 is an error, and every keep list implies it
+    The two exclude each other.  Both None: ``SVX_SORT_DROP_TAGS`` / ``SVX_SORT_KEEP_TAGS`` of ``environ`` (os.environ) are read, comma-
+    separated, an empty value being unset; an argument that is given wins over the environment.  Errors are ValueError."""
+    names = ("drop_tags", "keep_tags")
+    if drop_tags is None and keep_tags is None:
+        environ = os.environ if environ is None else environ
+        drop_tags, keep_tags = (environ.get(name) or None for name in ("SVX_SORT_DROP_TAGS", "SVX_SORT_KEEP_TAGS"))
+        names = ("SVX_SORT_DROP_TAGS", "SVX_SORT_KEEP_TAGS")
+    if drop_tags is not None and keep_tags is not None:
+        raise ValueError("%s and %s exclude each other: a list to drop, or a list to keep" % names)
+    if drop_tags is not None:
+        tags = parse_tags(drop_tags, names[0])
+        if TAGS_ALWAYS_KEPT in tags:
+            raise ValueError("%s: %s is never removed -- it holds the CIGAR of a record with more than 65,535 operations" % (names[0], TAGS_ALWAYS_KEPT))
+        return TagFilter("drop", tags) if tags else None
+    if keep_tags is not None:
+        return TagFilter("keep", parse_tags(keep_tags, names[1]))
+    return None
+
+
 # ---- the steps ----
 # Every input opened, and the one file they make: ``merged`` is an Opened whose head (references, lengths), header bytes and room are
 # the output's -- of one input: that input's own --, ``label`` names the inputs in a message.
@@ -170,14 +229,26 @@ def _open_all(paths, dv=None, run=None):
     usable; a BAM part whose table is not the identity carries it as ``remap`` --, ``room`` the sum where every part's is known.
     Under ``run.retag`` a BAM part whose @RG / @PG IDs were renamed carries its table as ``retag``: its records change their length, so
     the run's ``room`` is None -- the road of a mixed BAM + SAM run; the part's own ``room`` stays its ISIZE sum, for the check of the
-    bytes as read.  A part read as text that would need a rename is refused."""
+    bytes as read.  A part read as text that would need a rename is refused.  Under ``run.tags`` every part carries the filter as
+    ``tags``; its records only get shorter, so every ``room`` stays the ISIZE sum -- an upper bound --, and a part read as text is
+    refused: text is encoded straight into the resident stream."""
     from .io import sam
     if paths.count("-") > 1:
         raise SortWriteError("%s is named twice: standard input is one stream" % sam.STREAM_NAME)
+    tags = None if run is None else run.tags
+
+    def filtered(o):
+        if tags is None:
+            return o
+        if o.source.from_text:                                  # (before a pipe among them is spooled)
+            raise SortWriteError("%s: the input is read as SAM text, whose records' optional fields are not filtered (--%s-tags, SVX_SORT_%s_TAGS; "
+                                 "sort_bam's %s_tags) -- convert it to BAM (`samtools view -b`, also in a pipe)"
+                                 % (o.path, tags.mode, tags.mode.upper(), tags.mode))
+        return o._replace(tags=tags)
     if len(paths) == 1:
-        opened = _open(paths[0], run=run)
+        opened = filtered(_open(paths[0], run=run))
         return Inputs([opened], opened, opened.path if opened.pipe is None else opened.pipe.name)
-    opened = [_open(p, alone=False, run=run) for p in paths]
+    opened = [filtered(_open(p, alone=False, run=run)) for p in paths]
     merged = merge_headers([(o.path, o.head.text if o.source.from_text else o.head.header_text, o.head.references, o.head.lengths) for o in opened],
                            retag=bool(run is not None and run.retag))
     for o, table in zip(opened, merged.renames):
@@ -393,7 +464,10 @@ def _stats(stats, opened, kp, od, written, counts, pipes, budget, clock):
         # ``pipe``: the first input that was read once; ``pipes``: every one of them, in list order, with its name
         stats.update(pipe=pipes[0].stats(), pipes=[dict(pipe.stats(), name=pipe.name) for pipe in pipes])
     stats.update(inputs=len(kp.parts), input_records=[p.part.n for p in kp.parts], retid_inputs=sum(p.opened.remap is not None for p in kp.parts),
-                 retag_inputs=sum(p.opened.retag is not None for p in kp.parts), retag_records=sum(getattr(p.part, "retag_records", 0) for p in kp.parts))
+                 retag_inputs=sum(p.opened.retag is not None for p in kp.parts), retag_records=sum(getattr(p.part, "retag_records", 0) for p in kp.parts),
+                 tags_mode=next((p.opened.tags.mode for p in kp.parts if p.opened.tags is not None), None),
+                 tags_records=sum(getattr(p.part, "tags_records", 0) for p in kp.parts), tags_bytes=sum(getattr(p.part, "tags_bytes", 0) for p in kp.parts))
+    stats.update(range_reads=sum(p.part.range_reads for p in kp.parts))
     stats.update(ranges=len(kp.range_records), records=kp.n, blocks=written.blocks, stored_blocks=written.stored_blocks,
                  dynamic_blocks=written.dynamic_blocks, chunks=written.chunks, spans=od.spans, span_range_reads=counts["span_range_reads"],
                  range_records=kp.range_records, stream_bytes=max([od.stream_bytes] + [pipe.store.ledger.peak for pipe in pipes]), memory_bytes=budget,
@@ -403,7 +477,7 @@ def _stats(stats, opened, kp, od, written, counts, pipes, budget, clock):
 
 
 def sort_bam(bam_path, out_path, device="cuda", range_bytes=None, chunk_bytes=None, stats=None, tables="fixed", memory_bytes=None,
-             index_format="bai", pipe_bam=None, retag=None):
+             index_format="bai", pipe_bam=None, retag=None, drop_tags=None, keep_tags=None):
     """Write the records of ``bam_path`` in coordinate order to ``out_path`` and its index to ``out_path + ".bai"`` (see the head of the
     module); returns ``out_path``.  ``index_format="csi"``: the index is ``out_path + ".csi"`` and no ``.bai`` is written -- the sorted file's
     bytes are the same.  Under "bai" a record that reaches position 2^29 is refused (SortWriteError, neither file written): a ``.bai``
@@ -414,7 +488,8 @@ def sort_bam(bam_path, out_path, device="cuda", range_bytes=None, chunk_bytes=No
     bytes on the device (default: half of the device memory that is free at the call); a file whose records exceed it is written in
     spans, a pass over the input for each (see the head of the module) -- the same two files.  ``stats``: a dict that receives
     ranges, records, blocks, stored_blocks, dynamic_blocks, compressed_bytes, inflated_bytes, chunks, spans (1: in one piece),
-    span_range_reads (ranges read again over all spans; 0 in one piece), range_records (the records every range of the pass
+    span_range_reads (ranges read again over all spans; 0 in one piece), range_reads (the ranges and chunks read over all passes of
+    the run's inputs: ``ranges`` where every input was read once, twice that where a run in one piece read its inputs a second time), range_records (the records every range of the pass
     completed), stream_bytes (the largest record buffer allocated), inputs, input_records (the records of every input), retid_inputs
     (the inputs whose records were renumbered: svx_record_retid) and the seconds per stage.  ``bam_path`` may be SAM text: then
     ``range_bytes`` is the text bytes of a chunk, and stats also has input="sam" and host_lines, the lines io/sam.py encoded.
@@ -436,9 +511,17 @@ def sort_bam(bam_path, out_path, device="cuda", range_bytes=None, chunk_bytes=No
     as BAM -- SAM text that would need it is refused --, and the run reads its BAM inputs twice.  Off (the default), a colliding @RG is
     refused and a colliding @PG renamed in the header only.  None: ``SVX_SORT_RETAG=1`` of the environment turns it on.  stats:
     retag_inputs (the inputs with a table), retag_records (the records whose bytes changed); both 0, and seconds["retag"] 0.0, where
-    nothing is renamed."""
+    nothing is renamed.  ``drop_tags`` / ``keep_tags``: optional fields are removed from every record as it is sorted -- a list or tuple
+    of 2-character tags, or one comma-separated string; the listed fields go, or all but the listed ones (:func:`tag_filter`: the two
+    exclude each other, ``CG`` always stays, a bad list is a ValueError before anything is opened).  The two files are those of the
+    same inputs with the fields removed beforehand.  BAM inputs only: an input read as SAM text is refused; a lone BAM on a pipe
+    keeps its spool copy under ``pipe_bam="stream"`` too; a record with malformed optional fields refuses the run.  No input is read
+    twice for it, and whether the file is written in spans is decided on the unfiltered size.  Both None: ``SVX_SORT_DROP_TAGS`` /
+    ``SVX_SORT_KEEP_TAGS`` of the environment.  stats: tags_mode ("drop", "keep" or None), tags_records (the records whose bytes
+    changed), tags_bytes (the bytes removed); None, 0, 0 and seconds["tags"] 0.0 where the switch is off."""
     from . import kernels
     paths = input_paths(bam_path)
+    tags = tag_filter(drop_tags, keep_tags)
     torch, lib, dev, clock = index.on_device("sort_bam needs the GPU (svx_record_sort, svx_bgzf_deflate)", device, STAGES)
     if tables not in TABLES:
         raise ValueError("tables: %r is none of %s" % (tables, ", ".join(TABLES)))
@@ -456,7 +539,7 @@ def sort_bam(bam_path, out_path, device="cuda", range_bytes=None, chunk_bytes=No
         with torch.cuda.device(dev):
             if budget is None:                                  # half of what is free: the rest is for a range, its inflate workspace, keys and chunks
                 budget = max(int(torch.cuda.mem_get_info(dev)[0]) // 2, 1)
-            ins = _open_all(paths, dv, _Run(out_path, chunk_blocks, budget, range_bytes, pipes, clock, stream_bam, retag))
+            ins = _open_all(paths, dv, _Run(out_path, chunk_blocks, budget, range_bytes, pipes, clock, stream_bam, retag, tags))
             opened = ins.merged
             opened, kp, spanned = _key_passes(dv, ins, budget, range_bytes)
             od = _order(dv, opened, kp, spanned, budget)
@@ -518,8 +601,17 @@ def main(argv=None):
     ap.add_argument("--retag", action="store_true", default=os.environ.get("SVX_SORT_RETAG") == "1",
                     help="several inputs whose @RG / @PG IDs collide: rename the later input's ID to ID-<input number> and rewrite its records' "
                          "RG:Z / PG:Z tags (BAM inputs; they are read twice); without it a colliding @RG is refused (default: $SVX_SORT_RETAG=1)")
+    ap.add_argument("--drop-tags", default=None, metavar="TAGS",
+                    help="remove these optional fields from every record, comma-separated: fi,fp,ri,rp (BAM inputs; CG cannot be named; "
+                         "default: $SVX_SORT_DROP_TAGS)")
+    ap.add_argument("--keep-tags", default=None, metavar="TAGS",
+                    help="remove every optional field but these (and CG): RG,NM,SA,MD; an empty list removes all (default: $SVX_SORT_KEEP_TAGS)")
     ap.add_argument("--stats-json", default=None, help="also write the statistics to this file")
     args = ap.parse_args(argv)
+    try:
+        tags = tag_filter(args.drop_tags, args.keep_tags)
+    except ValueError as exc:
+        ap.error(str(exc))
     if args.tables not in TABLES:
         ap.error("SVX_SORT_TABLES=%s: fixed or dynamic" % args.tables)
     if args.pipe_bam not in textin.PIPE_BAM + ("0",):
@@ -529,7 +621,8 @@ def main(argv=None):
     stats = {}
     try:
         path = sort_bam(args.bam[0] if len(args.bam) == 1 else args.bam, args.output, device=args.device, chunk_bytes=args.chunk_bytes, stats=stats, tables=args.tables,
-                        memory_bytes=args.memory, pipe_bam=args.pipe_bam, retag=args.retag, **(dict(index_format="csi") if args.csi else {}))
+                        memory_bytes=args.memory, pipe_bam=args.pipe_bam, retag=args.retag,
+                        **({"%s_tags" % tags.mode: tags.tags} if tags is not None else {}), **(dict(index_format="csi") if args.csi else {}))
     except (SortWriteError, _lib.SvxError, OSError) as exc:
         print("svision_amd.sort: %s" % exc, file=sys.stderr)
         return 1
@@ -553,6 +646,9 @@ def main(argv=None):
         if stats.get("retag_inputs"):
             print("%s: %d input(s) with renamed @RG / @PG IDs, the RG:Z / PG:Z tags of %d record(s) rewritten"
                   % (path, stats["retag_inputs"], stats["retag_records"]))
+    if stats.get("tags_records"):
+        print("%s: optional fields removed (--%s-tags): %d record(s) changed, %d bytes removed"
+              % (path, stats["tags_mode"], stats["tags_records"], stats["tags_bytes"]))
     if stats.get("spans", 1) > 1:
         print("%s: the records exceed the budget of %d bytes (--memory): written in %d span(s), %d range(s) read again"
               % (path, stats["memory_bytes"], stats["spans"], stats["span_range_reads"]))

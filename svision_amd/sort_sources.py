@@ -30,13 +30,19 @@ from .textin import is_stream
 # ``source``: the input's kind, chosen at open (the head of this module).
 # ``retag``: None, or the input's table of sort_header.merge_headers(retag=True), {("RG" / "PG", old ID): new ID}: a BAM input of several
 # whose @RG / @PG IDs collide with an earlier input's -- its records' RG:Z / PG:Z values are replaced (:func:`_retag`).
-Opened = collections.namedtuple("Opened", "path head first header room source remap pipe text retag", defaults=(None, None, None, None, None))
+# ``tags``: None, or the run's :class:`TagFilter`: optional fields are removed from the input's records (:func:`_tags`; BAM inputs only).
+Opened = collections.namedtuple("Opened", "path head first header room source remap pipe text retag tags", defaults=(None, None, None, None, None, None))
+
+# Which optional fields a run removes (sort_bam's ``drop_tags`` / ``keep_tags``): ``mode`` "drop" -- the fields whose tag is in ``tags``
+# go -- or "keep" -- all others go; ``CG`` stays in either mode.
+TagFilter = collections.namedtuple("TagFilter", "mode tags")
 
 # What the steps of one run share besides the device: where the output goes (a spool lies beside it), the output's chunk, the budget
 # for the records' bytes, ``pipes``: every :class:`_Pipe` the run opened, for sort_bam to close and to clean up behind, and the clock.
 # ``stream_bam``: a lone BAM on a pipe is taken in one pass (``pipe_bam="stream"``), not copied into a file first.
 # ``retag``: colliding @RG / @PG IDs of several inputs are renamed and the records follow (sort_bam's ``retag``).
-_Run = collections.namedtuple("_Run", "out_path chunk_blocks budget range_bytes pipes clock stream_bam retag", defaults=(False, False))
+# ``tags``: None, or the :class:`TagFilter` of the run.
+_Run = collections.namedtuple("_Run", "out_path chunk_blocks budget range_bytes pipes clock stream_bam retag tags", defaults=(False, False, None))
 
 
 def inflated_size(path):
@@ -52,10 +58,11 @@ class InputPass:
     """What the key pass over ONE input leaves, filled as it goes: per range ``range_records`` and ``places``; ``seen``: the inflated
     record bytes so far; what the join takes of the ranges (``host``, ``d_keys``, ``lens``: per range the host fields, the device keys,
     the records' lengths; emptied behind it); ``base``: the stream offset of its first record; and behind the join its ``n`` records'
-    slices of the run's ``off_in`` / ``d_off_in`` -- offsets in the one stream -- and, while it is filled, the run's ``d_stream``."""
+    slices of the run's ``off_in`` / ``d_off_in`` -- offsets in the one stream -- and, while it is filled, the run's ``d_stream``.
+    ``range_reads``: the ranges (chunks) of the input read so far, over all its passes -- ``len(range_records)`` where it was read once."""
 
     def __init__(self, base=0):
-        self.range_records, self.places, self.seen, self.n, self.base = [], [], 0, 0, base
+        self.range_records, self.places, self.seen, self.n, self.base, self.range_reads = [], [], 0, 0, base, 0
         self.host, self.d_keys, self.lens = [], [], []
         self.off_in = self.d_off_in = self.d_stream = None
 
@@ -67,12 +74,13 @@ class InputPass:
 class BamPass(InputPass):
     """A BAM's: ``d_map`` besides, the input's ``remap`` on the device once :func:`_retid` has needed it; ``d_retag``: its ``retag``
     table likewise (:func:`_retag`), ``retag_records``: the records the key pass rewrote; ``read``: the record bytes as the file
-    holds them, which ``seen`` is not where records were rewritten."""
+    holds them, which ``seen`` is not where records were rewritten; ``d_tags``: the bitmap of the run's :class:`TagFilter`
+    (:func:`_tags`), ``tags_records`` / ``tags_bytes``: the records the key pass shortened and the bytes it removed."""
 
     def __init__(self, base=0):
         InputPass.__init__(self, base)
-        self.d_map = self.d_retag = None
-        self.retag_records = self.read = 0
+        self.d_map = self.d_retag = self.d_tags = None
+        self.retag_records = self.read = self.tags_records = self.tags_bytes = 0
 
 
 class SamPass(InputPass):
@@ -152,13 +160,40 @@ def _retag(dv, opened, part, d_bytes, d_off, count=False):
     return d_out, d_new_off
 
 
+def _tags(dv, opened, part, d_bytes, d_off, count=False):
+    """The records at ``d_off`` [n + 1] in ``d_bytes`` of an input under the run's :class:`TagFilter` -> (a new buffer, the records'
+    offsets in it [n + 1]): svx_record_tags_measure, an exclusive sum, svx_record_tags_write -- every optional field that the filter
+    removes gone, block_size with it; the status is read once.  The buffer has the 4 readable bytes behind its records that the
+    gather and the scatter want.  ``count``: the key pass, which counts the records that changed and the bytes that went."""
+    torch, kernels = dv.torch, dv.kernels
+    if part.d_tags is None:
+        part.d_tags = kernels.tags_table(opened.tags.tags, opened.tags.mode == "keep", dv.dev)
+    n = int(d_off.shape[0]) - 1
+    d_status = torch.zeros(1, dtype=torch.int32, device=dv.dev)
+    d_len = kernels.record_tags_measure(d_bytes, d_off, part.d_tags, d_status)
+    d_new_off = torch.zeros(n + 1, dtype=torch.int64, device=dv.dev)
+    torch.cumsum(d_len, 0, out=d_new_off[1:])
+    total = int(d_new_off[n].item())
+    d_out = torch.empty(total + 4, dtype=torch.uint8, device=dv.dev)
+    d_out[total:] = 0
+    kernels.record_tags_write(d_bytes, d_off, part.d_tags, d_new_off, d_out, d_status)
+    if count:
+        part.tags_records += int((d_len != d_off[1:] - d_off[:-1]).sum().item())
+        part.tags_bytes += int((d_off[n] - d_off[0]).item()) - total
+    bad = int(d_status.item())
+    dv.clock.lap("tags")
+    if bad:
+        raise SortWriteError("%s: a record's optional fields are malformed -- they cannot be filtered (--drop-tags / --keep-tags)" % opened.path)
+    return d_out, d_new_off
+
+
 def _bam_measured(dv, opened, part, rng, room=None):
     """A walked range of a BAM -- a file's or a streamed pipe's -> Measured: svx_cigar_scan for the reference spans
     (index._index_fields), the records' lengths from their offsets up to the chain's exit, and, for an input with a ``remap``, the
     range's records and keys translated where they lie (:func:`_retid`), the host's tid too.  ``room``: the record bytes the file's ISIZE
     fields add up to; more than that -- of the bytes as they were read -- is refused before anything is rewritten.  An input with a
     ``retag`` table: the range's records and offsets are then replaced by the rewritten ones (:func:`_retag`), so lengths, ``seen``
-    and everything behind see those."""
+    and everything behind see those.  An input under a :class:`TagFilter`: likewise, behind the retag (:func:`_tags`)."""
     first = sum(part.range_records)
     if not rng.n_rec:
         return Measured(first, np.empty(0, np.int64), None, None, None, None, None, None, None, 0)
@@ -170,9 +205,12 @@ def _bam_measured(dv, opened, part, rng, room=None):
     if opened.remap is not None:
         _retid(dv, opened, part, rng.d_raw, rng.d_rec_off, rng.d_tid)
         tid = np.where(tid >= 0, opened.remap[np.maximum(tid, 0)], tid).astype(np.int32)
-    if opened.retag:
-        d_off = dv.torch.cat([rng.d_rec_off, dv.torch.tensor([last], dtype=dv.torch.int64, device=dv.dev)])
-        rng.d_raw, d_new_off = _retag(dv, opened, part, rng.d_raw, d_off, count=True)
+    if opened.retag or opened.tags:
+        d_new_off = dv.torch.cat([rng.d_rec_off, dv.torch.tensor([last], dtype=dv.torch.int64, device=dv.dev)])
+        if opened.retag:
+            rng.d_raw, d_new_off = _retag(dv, opened, part, rng.d_raw, d_new_off, count=True)
+        if opened.tags:
+            rng.d_raw, d_new_off = _tags(dv, opened, part, rng.d_raw, d_new_off, count=True)
         rng.d_rec_off = d_new_off[:-1]
         return Measured(first, np.diff(d_new_off.cpu().numpy()), None, tid, pos, flag, span, rng.d_tid, rng.d_pos, 0)
     length = np.diff(np.append(rec_off, np.uint64(last)).astype(np.int64))
@@ -210,7 +248,13 @@ class BamSource:
     records' RG:Z / PG:Z values follow (:func:`_retag`: svx_record_retag_measure, an exclusive sum, svx_record_retag_write -- a wave a
     record).  A rewritten record has another length, so the input's record bytes are known only behind its key pass: the run keeps no
     byte in the key passes and reads its BAM inputs a second time (``fill``) or in spans (``again``), where the same rewriting gives the
-    same lengths; the ISIZE check stays on the bytes as read.  An input with no table: no launch, no allocation."""
+    same lengths; the ISIZE check stays on the bytes as read.  An input with no table: no launch, no allocation.
+
+    Under the run's :class:`TagFilter` (``drop_tags`` / ``keep_tags``) every range's records lose the optional fields it removes
+    (:func:`_tags`: svx_record_tags_measure, an exclusive sum, svx_record_tags_write -- a wave a record), behind the renumbering and
+    the retag.  Records only get shorter, so the ISIZE sum stays an upper bound of the input's record bytes: ``room`` stays that sum,
+    the stream is allocated once and the shortened records are kept end to end as the key passes go -- no second read; whether the
+    run is written in spans is decided on the unfiltered size.  In spans ``again`` filters the range's records again: the same lengths."""
     name, state, from_text, reads_once = "bam", BamPass, False, False
 
     def key_pass(self, dv, opened, range_bytes, part, d_stream):
@@ -218,6 +262,7 @@ class BamSource:
         once by the ISIZE sum -- every range's slice goes straight to its place in it, from byte ``part.base`` on --, or None: no byte is
         kept."""
         for rng in index.record_ranges(opened.path, opened.head, dv.dev, dv.clock, range_bytes, first=opened.first):
+            part.range_reads += 1
             m = _bam_measured(dv, opened, part, rng, opened.room)
             if d_stream is not None and m.length.size:
                 at, need = part.base + part.seen, int(m.length.sum())
@@ -230,9 +275,11 @@ class BamSource:
     def again(self, dv, opened, part, need):
         """The ranges ``need`` of a BAM read again: read, inflate, CRC, find_starts, the walk's counts and offsets; nothing is extracted.
         An input with a ``remap``: the range's records translated where they lie before they are handed on (:func:`_retid`); with a
-        ``retag`` table: the rewritten records and their offsets are handed on (:func:`_retag`)."""
+        ``retag`` table: the rewritten records and their offsets are handed on (:func:`_retag`); under a :class:`TagFilter`: the
+        filtered ones (:func:`_tags`)."""
         for k, rng in zip(need, index.record_ranges(opened.path, opened.head, dv.dev, dv.clock, places=[part.places[k] for k in need], extract=False,
                                                     first=opened.first)):
+            part.range_reads += 1
             if rng.n_rec != part.range_records[k]:
                 yield k, rng.n_rec, None, None                  # (the caller refuses it; no offsets are taken of a range that changed)
                 return
@@ -242,6 +289,8 @@ class BamSource:
                 _retid(dv, opened, part, rng.d_raw, d_src_off[:rng.n_rec], None)
             if opened.retag:
                 rng.d_raw, d_src_off = _retag(dv, opened, part, rng.d_raw, d_src_off)
+            if opened.tags:
+                rng.d_raw, d_src_off = _tags(dv, opened, part, rng.d_raw, d_src_off)
             yield k, rng.n_rec, rng.d_raw, d_src_off
             _release(rng)
             del rng, d_src_off
@@ -319,6 +368,7 @@ def _sam_encode_chunk(dv, opened, part, k, first, base, d_out, d_status):
     except textin.ReadError as exc:
         raise SortWriteError("%s changed while it was sorted: %s" % (exc.path, exc.what)) from None
     d_text, d_line_off, n_lines = textin.upload_lines(torch, kernels, dv.dev, dv.clock, chunk)
+    part.range_reads += 1
     if n_lines != part.range_records[k]:
         return n_lines
     d_len = torch.from_numpy(part.host_lens[k]).to(dv.dev)
@@ -359,6 +409,7 @@ class SamSource:
         (:meth:`fill`)."""
         part.reader = textin.ChunkReader(dv.torch, dv.lib, dv.clock)
         for chunk in part.reader.chunks(opened.text, range_bytes):
+            part.range_reads += 1
             d_text, d_line_off, n_lines = textin.upload_lines(dv.torch, dv.kernels, dv.dev, dv.clock, chunk)
             _keep_measured(part, chunk.place, _sam_measured(dv, opened, part, chunk, d_text, d_line_off, n_lines))
             del d_text, d_line_off
@@ -575,6 +626,7 @@ class PipeSource(SamSource):
             store.to_spool()
         d_status = torch.zeros(1, dtype=torch.int32, device=dev)
         for chunk in part.reader.chunks(opened.text, range_bytes):
+            part.range_reads += 1
             d_text, d_line_off, n_lines = textin.upload_lines(torch, kernels, dev, clock, chunk)
             m = _sam_measured(dv, opened, part, chunk, d_text, d_line_off, n_lines)
             need = int(m.length.sum())
@@ -626,6 +678,7 @@ class BamPipeSource(BamSource):
         store = pipe.on_device(dv, lambda: pipe.bam_header)
         chunks = textin.member_chunks(dv.torch, opened.text, range_bytes)
         for rng in index.stream_ranges(chunks, opened.head, opened.first, dv.dev, dv.clock, name=opened.path):
+            part.range_reads += 1
             m = _bam_measured(dv, opened, part, rng)
             if m.length.size:
                 need = int(m.length.sum())
@@ -702,6 +755,7 @@ def _open_pipe(inp, alone, run):
                 default the bytes are copied as they are into the spool file and the BAM road sorts that file -- one write and one read
                 of compressed BAM more, room for it beside the output, and nothing runs on the device until the aligner has ended.
                 Alone and under ``run.stream_bam``: its header read from the stream and the rest left waiting for :class:`BamPipeSource`
+                -- unless the run has a :class:`TagFilter`: the filter is the BAM road's, so the copy is kept under either setting
       refused   other gzip data (compressed SAM: ``pigz -dc x.sam.gz | ... -`` is the road), no byte at all (``<stdin>: no input``)"""
     from .io import sam
     pipe = _Pipe(inp, run)
@@ -712,7 +766,7 @@ def _open_pipe(inp, alone, run):
     if inp.peek_kind == sam.STREAM_SAM:
         return _open_sam(inp, alone, pipe)
     pipe.holds = "bam"
-    if alone and run.stream_bam:
+    if alone and run.stream_bam and run.tags is None:          # (a tag filter works on the copy: the BAM road, under either setting)
         try:
             got = inp.reader.bam_header()
             pipe.bam_header = got.head
